@@ -16,18 +16,25 @@ step's 32 mosaics are all-gathered (RCCL over xGMI, asynchronously, overlapping 
 rank ends up holding the whole batch -- the one exchange the path has, INSIDE the timed region; `value` includes it and
 `config.no_exchange_mpix_s` gives the same run without it.  N = 1: the rank already holds the batch, no exchange.
 
-Every timed region is checked: after it, status() of every plan and pair (seam scan + the fused sweep's sticky
-time-out count) and a bit-for-bit comparison of EVERY output buffer with the result of a separately created
-single-pair plan (the unfused launch sequence that tests/test_gpu_golden.py compares with the oracle at this size);
-N > 1 also checks the gathered blocks of all ranks by checksum.  `outputs_verified` reports it (all ranks).
+A plain run sets up, warms up, times --steps steps (timed region 1) and prints the line; after every timed region
+status() of every plan and pair is checked (seam scan + the fused sweep's sticky time-out count).  --dump-outputs DIR
+writes what the last timed step computed (a fixed sample of every mosaic and its per-channel sums) for comparing builds.
 
-Prints ONE JSON line (rank 0).  `value` comes from timed region 1 (all sequences in flight).  `roofline` describes
-the dominant kernel (largest share of device time) in timed region 2, where one sequence is in flight so that a
-launch's duration is the kernel's own, timed with HIP events on the launch stream; `pipeline` gives the byte
-accounting for the whole pair at the `value` rate.  `cpu_baseline` (N=1, rank 0) times the oracle's CPU restatement
-on a bounded sample of the same workload.
+--full adds everything else, each part as before: a bit-for-bit comparison of EVERY output buffer after every timed
+region with the result of a separately created single-pair plan (the unfused launch sequence that
+tests/test_gpu_golden.py compares with the oracle at this size; N > 1 also checks the gathered blocks of all ranks by
+checksum; `outputs_verified` reports it, all ranks, and is null in a plain run), the pilot and timed region 2 behind
+`kernels` and `roofline`, the region without the exchange (N > 1), the single-pair and single-batch figures and the
+CPU baseline.
+
+Prints ONE JSON line (rank 0).  `value` and `ms_per_step` come from timed region 1 (all sequences in flight).
+`roofline` (--full) describes the dominant kernel (largest share of device time) in timed region 2, where one sequence
+is in flight so that a launch's duration is the kernel's own, timed with HIP events on the launch stream; `pipeline`
+gives the byte accounting for the whole pair at the `value` rate.  `cpu_baseline` (--full, N=1, rank 0) times the
+oracle's CPU restatement on a bounded sample of the same workload.
 """
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -65,7 +72,27 @@ def parse():
     ap.add_argument("--stagger-ms", type=float, default=0.0, help="delay (host sleep) in front of the first launch sequence of lanes 1, 2, ... "
                     "of every timed region, inside the region: the lanes then run out of phase (A/B switch, see DESIGN.md 5)")
     ap.add_argument("--verbose", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the output check against single-pair plans, the per-kernel table and "
+                    "roofline (pilot + timed region 2), the exchange-free region (N>1), the single-pair and single-batch figures and "
+                    "the CPU baseline; a plain run only warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what their last step computed to DIR/*.npy: "
+                    "a fixed seeded sample of every pair's mosaic (mosaic_sample.npy, pairs x samples, float32), the flat indices "
+                    "sampled (sample_index.npy, float64) and every mosaic's per-channel sum over all pixels (mosaic_sum.npy, float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SEED = 20240607  # the sample of every mosaic that --dump-outputs writes: fixed, so that runs and builds compare
+DUMP_BYTES = 60_000_000  # what --dump-outputs writes, at most (sample + indices + sums)
+
+
+def dump_sample_index(numel, n_pairs):
+    """Flat indices (sorted, unique, int64) of the mosaic elements --dump-outputs samples: the same for every pair and run."""
+    import numpy as np
+    n = max(1, min(numel, 1 << 18, (DUMP_BYTES - 24 * n_pairs) // (4 * n_pairs + 8)))
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, numel, n, dtype=np.int64))
 
 
 def cpu_baseline(sample_frame, verbose=False):
@@ -221,8 +248,9 @@ def main():
     for ln in range(S):
         lanes.append({"plan": capi.Plan(cw, ch, max_pairs=B * G), "stream": torch.cuda.Stream(device=dev),
                       "outs": [[torch.empty((3, ch, cw), dtype=tdt, device=dev) for _ in range(B * G)] for _ in range(2)],
-                      "holds": [None, None], "last": None})
+                      "holds": [None, None], "launch": [None, None], "last": None})
     plan = lanes[0]["plan"]
+    launch_order = itertools.count()  # which launch wrote an output buffer last (--dump-outputs)
     gather = None
     if use_gather:
         # finished mosaics travel as unsigned char through pipeline.MosaicGather -- the class the gloo tests cover; one block
@@ -255,6 +283,7 @@ def main():
                     for q, i in enumerate(idx):
                         blks[q // per][i - lo].copy_(outs[q])
             L["holds"][slot] = idx
+            L["launch"][slot] = next(launch_order)
             L["last"] = slot
             if gather_steps is not None:
                 ev = torch.cuda.Event()
@@ -312,8 +341,9 @@ def main():
 
     # ---- reference results for the output check: every local pair through a single-pair plan (unfused sweeps, plain
     # launch sequence; compared with the oracle at this very size by tests/test_gpu_golden.py) ------------------------
+    compare = args.full and not args.no_verify  # the bit-for-bit output check is part of --full; status() is always checked
     ref_out, ref_q = {}, {}
-    if not args.no_verify:
+    if compare:
         one = capi.Plan(cw, ch)
         for i in range(lo, hi):
             ref_out[i] = one.pair(pair_in[i][0], pair_in[i][1], 0.0, 0.0, pair_in[i][4], 0, 0)
@@ -336,14 +366,14 @@ def main():
             except capi.StitchError as e:
                 checks["bad"].append(f"{tag}: lane {ln}: {e}")
                 L["plan"].clear_fault()
-            if args.no_verify:
+            if not compare:
                 continue
             for slot in range(2):
                 for q, i in enumerate(L["holds"][slot] or []):
                     checks["buffers"] += 1
                     if not torch.equal(L["outs"][slot][q], ref_out[i]):
                         checks["bad"].append(f"{tag}: lane {ln} slot {slot} pair {i} differs from the single-pair plan")
-        if gather_step is not None and not args.no_verify:
+        if gather_step is not None and compare:
             # the gathered batch of the last step: this rank's own checksums travel by all-gather, every block is checked
             mine = torch.tensor([ref_q.get(lo + j, 0) for j in range(n_max)], dtype=torch.int64, device=cdev)
             allq = torch.empty(world * n_max, dtype=torch.int64, device=cdev)
@@ -363,6 +393,88 @@ def main():
         if args.verbose:
             print(f"[bench rank {rank}] {msg}", file=sys.stderr, flush=True)
 
+    def full_regions():
+        """--full: the figures that take runs of their own, after timed region 1."""
+        elapsed_noex = None
+        if use_gather:
+            elapsed_noex = timed(lambda n_: run_steps(0, n_, False), K)
+            verify("region 1 (no exchange)")
+        # timed region 2 -> `roofline`: ONE sequence in flight (kernels do not overlap, so a launch's duration is the kernel's
+        # own), HIP events around the dominant kernel's launches only, on the launch stream
+        if not args.no_kernel_events:
+            plan.set_profiling_kernel(dom)
+        plan.read_profile()
+
+        def one_lane(n_):
+            for k in range(n_):
+                run_seq(k * S, seqs[0], copies=G)
+
+        elapsed_one = timed(one_lane, K)
+        prof = plan.read_profile()
+        plan.set_profiling(False)
+        verify("region 2")
+        log("region 2 done")
+        # single pair in flight (config 2 as a latency figure)
+        single_ms = None
+        if world == 1 and not args.no_single:
+            for k in range(2):
+                run_seq(k * S, seqs[0], n=1)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for k in range(5):
+                run_seq(k * S, seqs[0], n=1)
+            torch.cuda.synchronize()
+            single_ms = (time.perf_counter() - t1) / 5 * 1e3
+
+        # ONE step -- the whole batch of P pairs, start to finish, nothing else in flight: this rank's share as its own launch
+        # sequence(s) (no coalescing with other steps), the step's exchange included when N > 1; max over ranks, best of three
+        def one_step(k):
+            evs = [run_seq(k * nb + j, seqs[j], [k] if use_gather else None) for j in range(nb)]
+            if use_gather:
+                with torch.cuda.stream(gstream):
+                    for ev in evs:
+                        gstream.wait_event(ev)
+                    gather.submit(k)
+
+        single_batch_ms = min(timed(lambda n_, k=k: one_step(k), 1) for k in range(3)) * 1e3
+        verify("single batch", 2 if use_gather else None)
+        return elapsed_noex, elapsed_one, prof, single_ms, single_batch_ms
+
+    def dump_outputs(out_dir):
+        """The mosaics the last timed step wrote (every pair of the step, all ranks): a fixed sample of each, as float32, and
+        each one's per-channel sums over all pixels, as float64; rank 0 writes them."""
+        import numpy as np
+        held = sorted((L["launch"][slot], ln, slot) for ln, L in enumerate(lanes) for slot in range(2) if L["holds"][slot] is not None)
+        last = {}
+        for _, ln, slot in held:  # in launch order: a pair's latest output wins
+            for q, i in enumerate(lanes[ln]["holds"][slot]):
+                last[i] = lanes[ln]["outs"][slot][q]
+        missing = [i for i in range(lo, hi) if i not in last]
+        if missing:
+            raise SystemExit(f"--dump-outputs: the outputs of pairs {missing} were overwritten within the step "
+                             "(more launch sequences per step than two per stream)")
+        index = dump_sample_index(3 * ch * cw, P)
+        idx_dev = torch.from_numpy(index).to(dev)
+        sample = torch.zeros((n_max, index.size), dtype=torch.float32, device=dev)
+        sums = torch.zeros((n_max, 3), dtype=torch.float64, device=dev)
+        for j, i in enumerate(range(lo, hi)):
+            sample[j] = last[i].reshape(-1)[idx_dev].float()
+            sums[j] = last[i].double().sum(dim=(1, 2))
+        if use_dist:  # every rank's block of n_max rows (ragged shards padded), in rank order
+            sample, sums = sample.to(cdev), sums.to(cdev)
+            all_s = torch.empty((world * n_max, index.size), dtype=torch.float32, device=cdev)
+            all_m = torch.empty((world * n_max, 3), dtype=torch.float64, device=cdev)
+            dist.all_gather_into_tensor(all_s, sample)
+            dist.all_gather_into_tensor(all_m, sums)
+            rows = [r * n_max + j for r in range(world) for j in range(pipeline.shard_range(P, r, world)[1] - pipeline.shard_range(P, r, world)[0])]
+            sample, sums = all_s[rows], all_m[rows]
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            np.save(os.path.join(out_dir, "mosaic_sample.npy"), sample.cpu().numpy())
+            np.save(os.path.join(out_dir, "mosaic_sum.npy"), sums.cpu().numpy())
+            np.save(os.path.join(out_dir, "sample_index.npy"), index.astype(np.float64))
+        log(f"outputs of the last timed step written to {out_dir}")
+
     # ---- warm-up ---------------------------------------------------------------------------------------------------
     log(f"warm-up: {W} step(s), {n_local} pairs per step, {G} step(s) per launch sequence, {S} lane(s)")
     run_steps(0, W, use_gather)
@@ -380,69 +492,30 @@ def main():
         drain()
         verify("warm-up (second attempt)", None)
 
-    # pilot (lane 0, every launch bracketed by HIP events; ~10 % overhead, so never the timed region): per-kernel
+    # pilot (--full; lane 0, every launch bracketed by HIP events; ~10 % overhead, so never the timed region): per-kernel
     # table and the choice of the dominant kernel
-    plan.set_profiling(True)
-    plan.read_profile()
     PILOT = 3
-    for k in range(PILOT):
-        run_seq(k * S, seqs[0], copies=G)
-    torch.cuda.synchronize()
-    pilot = plan.read_profile()
-    dom = max(pilot, key=lambda k_: pilot[k_][0])
-    plan.set_profiling(False)
+    if args.full:
+        plan.set_profiling(True)
+        plan.read_profile()
+        for k in range(PILOT):
+            run_seq(k * S, seqs[0], copies=G)
+        torch.cuda.synchronize()
+        pilot = plan.read_profile()
+        dom = max(pilot, key=lambda k_: pilot[k_][0])
+        plan.set_profiling(False)
+        log("pilot done")
 
-    log("pilot done")
     # timed region 1 -> `value`: every launch sequence of K steps in flight over S streams (+ the exchange, N > 1)
     elapsed = timed(lambda n_: run_steps(0, n_, use_gather), K)
     verify("region 1", (K - 1) if use_gather else None)
-    elapsed_noex = None
-    if use_gather:
-        elapsed_noex = timed(lambda n_: run_steps(0, n_, False), K)
-        verify("region 1 (no exchange)")
-
-    log("region 1 done")
-    # timed region 2 -> `roofline`: ONE sequence in flight (kernels do not overlap, so a launch's duration is the kernel's
-    # own), HIP events around the dominant kernel's launches only, on the launch stream
-    if not args.no_kernel_events:
-        plan.set_profiling_kernel(dom)
-    plan.read_profile()
-    def one_lane(n_):
-        for k in range(n_):
-            run_seq(k * S, seqs[0], copies=G)
-
-    elapsed_one = timed(one_lane, K)
-    prof = plan.read_profile()
-    plan.set_profiling(False)
-    verify("region 2")
-    seam = plan.status(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs)
     n_seq0 = (seqs[0][1] - seqs[0][0]) * G
-
-    log("region 2 done")
-    # single pair in flight (config 2 as a latency figure)
-    single_ms = None
-    if world == 1 and not args.no_single:
-        for k in range(2):
-            run_seq(k * S, seqs[0], n=1)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for k in range(5):
-            run_seq(k * S, seqs[0], n=1)
-        torch.cuda.synchronize()
-        single_ms = (time.perf_counter() - t1) / 5 * 1e3
-
-    # ONE step -- the whole batch of P pairs, start to finish, nothing else in flight: this rank's share as its own launch
-    # sequence(s) (no coalescing with other steps), the step's exchange included when N > 1; max over ranks, best of three
-    def one_step(k):
-        evs = [run_seq(k * nb + j, seqs[j], [k] if use_gather else None) for j in range(nb)]
-        if use_gather:
-            with torch.cuda.stream(gstream):
-                for ev in evs:
-                    gstream.wait_event(ev)
-                gather.submit(k)
-
-    single_batch_ms = min(timed(lambda n_, k=k: one_step(k), 1) for k in range(3)) * 1e3
-    verify("single batch", 2 if use_gather else None)
+    log("region 1 done")
+    if args.full:
+        elapsed_noex, elapsed_one, prof, single_ms, single_batch_ms = full_regions()
+    seam = plan.status(0)
 
     ok = torch.tensor([0 if checks["bad"] else 1], dtype=torch.int32, device=cdev)
     per_rank = [[n_local, nb, G, S]]
@@ -453,10 +526,9 @@ def main():
         all_ = torch.empty(dist.get_world_size() * 4, dtype=torch.int64, device=cdev)
         dist.all_gather_into_tensor(all_, mine_)
         per_rank = all_.view(-1, 4).tolist()
-    verified = bool(ok.item()) and not args.no_verify
+    verified = (bool(ok.item()) and compare) if args.full else None  # None: a plain run compares no outputs
     for msg in checks["bad"]:
         print(f"[bench] rank {rank}: OUTPUT CHECK FAILED: {msg}", file=sys.stderr)
-
     if rank == 0:
         mpix_pair = cw * ch / 1e6
         value = mpix_pair * K * P / elapsed
@@ -490,27 +562,30 @@ def main():
                        "forms": sorted(forms), "backend": ("gloo REHEARSAL on one GPU: not a scaling measurement" if rehearsal else "nccl (RCCL)") if use_dist else None,
                        "per_rank": [{"rank": r_, "pairs_per_step": v[0], "sequences_per_step": v[1], "steps_per_sequence": v[2], "lanes": v[3],
                                      "gather_input_blocks": (v[3] + 1) * v[2] if use_gather else 0} for r_, v in enumerate(per_rank)],
-                       "single_batch_ms": round(single_batch_ms, 4),
-                       "single_batch_note": f"ONE step of {P} pairs start to finish with nothing else in flight (no coalescing with other steps"
-                                            + (", its all-gather included" if use_gather else "") + "), max over ranks, best of 3",
                        "mpix_per_pair": round(mpix_pair, 3),
                        "ms_per_pair_per_gpu": round(elapsed / K / n_local * 1e3, 4),
-                       "one_sequence_in_flight_ms_per_pair": round(elapsed_one / K / n_seq0 * 1e3, 4),
-                       "one_sequence_in_flight_mpix_s": round(mpix_pair * K * n_seq0 / elapsed_one, 1),
-                       "single_pair_in_flight_ms": round(single_ms, 4) if single_ms else None,
-                       "single_pair_in_flight_mpix_s": round(mpix_pair / single_ms * 1e3, 1) if single_ms else None,
                        "input_frame_mpix_per_s": round(2 * F * F / 1e6 * K * P / elapsed, 2),
                        "exchange": (f"every step's {P} finished mosaics cast to uint8 and all-gathered (RCCL, asynchronous, overlapping the "
                                     f"next step) inside the timed region: {n_max * 3 * ch * cw * (world - 1) / 1e9:.2f} GB into every rank per step")
                                    if use_gather else "none (one rank holds the whole batch)" if world == 1 else "none (--no-gather)",
-                       "no_exchange_mpix_s": round(mpix_pair * K * P / elapsed_noex, 2) if elapsed_noex else None,
                        "warmup_handoff_faults": len(warmup_faults),
                        "output_check": {"timed_regions_checked": checks["regions"], "buffers_compared": checks["buffers"],
-                                        "against": "single-pair plan (separate launch sequence), bit for bit; status() of every plan and pair",
+                                        "against": "single-pair plan (separate launch sequence), bit for bit; status() of every plan and pair"
+                                                   if compare else "status() of every plan and pair (outputs compared with --full only)",
                                         "failures": len(checks["bad"])},
                        "seam": list(seam.as_tuple())},
         }
-        if prof[dom][1] > 0:
+        if args.full:
+            line["config"].update({
+                "single_batch_ms": round(single_batch_ms, 4),
+                "single_batch_note": f"ONE step of {P} pairs start to finish with nothing else in flight (no coalescing with other steps"
+                                     + (", its all-gather included" if use_gather else "") + "), max over ranks, best of 3",
+                "one_sequence_in_flight_ms_per_pair": round(elapsed_one / K / n_seq0 * 1e3, 4),
+                "one_sequence_in_flight_mpix_s": round(mpix_pair * K * n_seq0 / elapsed_one, 1),
+                "single_pair_in_flight_ms": round(single_ms, 4) if single_ms else None,
+                "single_pair_in_flight_mpix_s": round(mpix_pair / single_ms * 1e3, 1) if single_ms else None,
+                "no_exchange_mpix_s": round(mpix_pair * K * P / elapsed_noex, 2) if elapsed_noex else None})
+        if args.full and prof[dom][1] > 0:
             ms, launches, _ = prof[dom]
             bytes_per_launch = per_kernel[dom] * n_seq0 * K / launches  # region 2: K launch sequences of n_seq0 pairs
             avg_s = ms / launches / 1e3
@@ -565,7 +640,7 @@ def main():
                             "achieved_GBps_per_gpu": round(stages["total"] / pair_s / 1e9 / world, 1),
                             "frac_of_hbm_peak": round(stages["total"] / pair_s / 1e9 / world / HBM_PEAK_GBS, 4),
                             "owned_bytes_per_pair_all_kernels": sum(per_kernel.values())}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_frame, args.verbose)
             # the reference's OWN loop on the same pair (unsigned char frames, one thread: ~2 minutes, so not inside this run):
             # timed once on a GPU box's host by scripts/bench_reference_config2.py, which also compares the MI355X result with it

@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p $out
 for v in "$@"; do
   if [ "$v" = default ]; then unset STITCH_LIB; else export STITCH_LIB=$PWD/computervisionimagestich2_amd/csrc/ab/libstitch_$v.so; fi
-  timeout -k 10 240 python bench.py --steps 10 --no-cpu-baseline $AB_ARGS > $out/bench_$v.json 2> $out/bench_$v.err
+  timeout -k 10 240 python bench.py --full --steps 10 --no-cpu-baseline $AB_ARGS > $out/bench_$v.json 2> $out/bench_$v.err
   echo "variant $v rc=$?"
   python - $out/bench_$v.json $v <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p $out
 for spec in "$@"; do
   v=${spec%%:*}; envs=${spec#*:}
-  env $envs timeout -k 10 240 python bench.py --steps 10 --no-cpu-baseline $AB_ARGS > $out/bench_$v.json 2> $out/bench_$v.err
+  env $envs timeout -k 10 240 python bench.py --full --steps 10 --no-cpu-baseline $AB_ARGS > $out/bench_$v.json 2> $out/bench_$v.err
   echo "variant $v ($envs) rc=$?"
   python - $out/bench_$v.json $v <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ AB=$PWD/computervisionimagestich2_amd/csrc/ab
 for lib in default "$@"; do
     if [ "$lib" = default ]; then unset STITCH_LIB; else export STITCH_LIB=$AB/libstitch_$lib.so; fi
     python scripts/experiments/exp_project.py
-    python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-single --no-verify 2>/dev/null | python -c "
+    python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-single --no-verify 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('   bench', d['value'], d['unit'], 'frac', d['roofline']['frac'])"
 done

@@ -3,10 +3,10 @@
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/r3run1; mkdir -p $o
 if [ -z "$SKIP_TESTS" ]; then python -m pytest tests -m gpu -x -q > $o/tests.log 2>&1; tail -3 $o/tests.log; fi
-python bench.py --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err; tail -2 $o/bench.err
-python bench.py --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err; tail -2 $o/bench_p4.err
-python bench.py --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline --no-coalesce > $o/bench_p4_nocoalesce.json 2> $o/bench_p4_nocoalesce.err
-STITCH_FORCE_DIST=1 python bench.py --steps 12 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4_forcedist.json 2> $o/bench_p4_forcedist.err; tail -2 $o/bench_p4_forcedist.err
+python bench.py --full --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err; tail -2 $o/bench.err
+python bench.py --full --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err; tail -2 $o/bench_p4.err
+python bench.py --full --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline --no-coalesce > $o/bench_p4_nocoalesce.json 2> $o/bench_p4_nocoalesce.err
+STITCH_FORCE_DIST=1 python bench.py --full --steps 12 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4_forcedist.json 2> $o/bench_p4_forcedist.err; tail -2 $o/bench_p4_forcedist.err
 for f in bench bench_p4 bench_p4_nocoalesce bench_p4_forcedist; do python - $o/$f.json <<'PY'
 import json,sys
 try:

@@ -3,8 +3,8 @@
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/r3run2; mkdir -p $o
 if [ -z "$SKIP_TESTS" ]; then python -m pytest tests -m gpu -x -q > $o/tests.log 2>&1; tail -3 $o/tests.log; fi
-python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $o/bench.json 2> $o/bench.err; tail -2 $o/bench.err
-python bench.py --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err; tail -2 $o/bench_p4.err
+python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $o/bench.json 2> $o/bench.err; tail -2 $o/bench.err
+python bench.py --full --steps 20 --warmup 3 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err; tail -2 $o/bench_p4.err
 for f in bench bench_p4; do python - $o/$f.json <<'PY'
 import json,sys
 try:

@@ -19,7 +19,7 @@ done
 echo "== bench A/B: collapse lockstep / swizzle"
 for v in "" "STITCH_C4_LOCKSTEP=0" "STITCH_C4_SWIZZLE=0" "STITCH_C4_LOCKSTEP=0 STITCH_C4_SWIZZLE=0"; do
   n=$(echo "x$v" | tr -c 'A-Za-z0-9=' '_')
-  env $v timeout -k 10 300 python bench.py --steps 10 --no-cpu-baseline --no-single > $O/bench_$n.json 2> $O/bench_$n.err
+  env $v timeout -k 10 300 python bench.py --full --steps 10 --no-cpu-baseline --no-single > $O/bench_$n.json 2> $O/bench_$n.err
   python - $O/bench_$n.json "$v" <<'PY'
 import json, sys
 try:
@@ -34,7 +34,7 @@ echo "== FETCH_SIZE / WRITE_SIZE of the collapse kernels"
 for v in "" "STITCH_C4_LOCKSTEP=0 STITCH_C4_SWIZZLE=0" "STITCH_C4_SWIZZLE=0"; do
   n=$(echo "x$v" | tr -c 'A-Za-z0-9=' '_')
   for C in FETCH_SIZE WRITE_SIZE; do
-    ( export $v _x=1; rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_${n}_$C -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-single --no-verify --streams 1 --batch 16 > $O/pmc_${n}_$C.json 2> $O/pmc_${n}_$C.err )
+    ( export $v _x=1; rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_${n}_$C -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-single --no-verify --streams 1 --batch 16 > $O/pmc_${n}_$C.json 2> $O/pmc_${n}_$C.err )
     python - $O/pmc_${n}_$C $C "$v" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*/*counter_collection.csv")

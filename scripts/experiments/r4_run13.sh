@@ -12,7 +12,7 @@ for c in "4421 2315 1536 2048" "6144 4096 4096 4096"; do
 done
 for v in "" "STITCH_C4_SWIZZLE=2" "STITCH_CROWS_L0=64" "STITCH_C4_SWIZZLE=2 STITCH_CROWS_L0=64"; do
   n=$(echo "default $v" | tr ' =' '__')
-  ( [ -n "$v" ] && export $v; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-single > $O/bench_$n.json 2> $O/bench_$n.err )
+  ( [ -n "$v" ] && export $v; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-single > $O/bench_$n.json 2> $O/bench_$n.err )
   python - $O/bench_$n.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

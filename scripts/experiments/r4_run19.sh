@@ -17,7 +17,7 @@ echo "== pitch pad: batch headline"
 AB_ARGS="--no-single" bash scripts/experiments/ab_env.sh $O "pad0:STITCH_X=0" "pad64:STITCH_PITCH_PAD=64" "pad192:STITCH_PITCH_PAD=192" "pad0b:STITCH_X=0" "pad320:STITCH_PITCH_PAD=320"
 echo "== pitch pad: config 5"
 for pad in 0 64 192; do
-  STITCH_PITCH_PAD=$pad timeout -k 10 300 python bench.py --frame 16384 --pairs-per-step 1 --batch 1 --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-single > $O/c5_$pad.json 2> $O/c5_$pad.err
+  STITCH_PITCH_PAD=$pad timeout -k 10 300 python bench.py --full --frame 16384 --pairs-per-step 1 --batch 1 --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-single > $O/c5_$pad.json 2> $O/c5_$pad.err
   python - $O/c5_$pad.json $pad <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d['config']; k=d['kernels']

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r4ad; rm -rf $O; mkdir -p $O
 for pad in 0 18432 6144 0; do
-  STITCH_PITCH_PAD=$pad timeout -k 10 300 python bench.py --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-single --pairs-per-step 16 > $O/b_$pad.json 2> $O/b_$pad.err
+  STITCH_PITCH_PAD=$pad timeout -k 10 300 python bench.py --full --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-single --pairs-per-step 16 > $O/b_$pad.json 2> $O/b_$pad.err
   python - $O/b_$pad.json $pad <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d['config']; k=d['kernels']

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r4ae; rm -rf $O; mkdir -p $O
 for i in $(seq 1 ${SOAK_N:-40}); do
   t0=$(date +%s.%N)
-  timeout -k 10 180 python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-single > $O/b_$i.json 2> $O/b_$i.err; rc=$?
+  timeout -k 10 180 python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-single > $O/b_$i.json 2> $O/b_$i.err; rc=$?
   t1=$(date +%s.%N)
   python - $O/b_$i.json $i $rc 0 <<'PY'
 import json,sys

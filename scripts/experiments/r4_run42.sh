@@ -5,7 +5,7 @@ O=gpurun_out/r4ao; rm -rf $O; mkdir -p $O
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_benchpath.py tests/test_gpu_band.py -x -q -m gpu > $O/pytest.log 2>&1; tail -2 $O/pytest.log
 for v in prev new prev new; do
   if [ $v = new ]; then unset STITCH_LIB; else export STITCH_LIB=$PWD/computervisionimagestich2_amd/csrc/ab/libstitch_prev.so; fi
-  timeout -k 10 240 python bench.py --steps 10 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout -k 10 240 python bench.py --full --steps 10 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
   python - $O/bench_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c = d["config"]; k = d["kernels"]

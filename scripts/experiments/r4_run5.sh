@@ -19,7 +19,7 @@ done
 echo "== request sizes of the collapse kernels (TCC_EA0_RDREQ by size)"
 for C in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"; do
   n=$(echo "$C" | tr ' ' '_')
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$n -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-single --no-verify --streams 1 --batch 16 > $O/pmc_$n.json 2> $O/pmc_$n.err
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$n -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-single --no-verify --streams 1 --batch 16 > $O/pmc_$n.json 2> $O/pmc_$n.err
   python - $O/pmc_$n <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)

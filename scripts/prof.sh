@@ -4,7 +4,8 @@
 # single-pair plan and would add launches of other shapes to the per-symbol averages); then the plain bench line on the same box
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-rm -rf gpurun_out/prof && mkdir -p gpurun_out/prof
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python3 bench.py --no-cpu-baseline --no-single --no-verify --streams 1 > gpurun_out/prof/bench_under_rocprof.json 2> gpurun_out/prof/bench_under_rocprof.err
-python bench.py --verbose > gpurun_out/prof/bench.json 2> gpurun_out/prof/bench.err
-tail -2 gpurun_out/prof/bench.err
+OUT=${1:?usage: scripts/prof.sh <output directory, relative to the repository root>}
+rm -rf $OUT && mkdir -p $OUT
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --no-cpu-baseline --no-single --no-verify --streams 1 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+python bench.py --full --verbose > $OUT/bench.json 2> $OUT/bench.err
+tail -2 $OUT/bench.err

@@ -3,13 +3,13 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/r3final; rm -rf $o; mkdir -p $o
 # 1. kernel trace + stats of the bench with one sequence in flight, then the plain default line (same box)
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -- python3 bench.py --no-cpu-baseline --no-single --no-verify --streams 1 > $o/bench_under_rocprof.json 2> $o/bench_under_rocprof.err
-python bench.py --steps 20 --warmup 5 --verbose > $o/bench.json 2> $o/bench.err; tail -3 $o/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -- python3 bench.py --full --no-cpu-baseline --no-single --no-verify --streams 1 > $o/bench_under_rocprof.json 2> $o/bench_under_rocprof.err
+python bench.py --full --steps 20 --warmup 5 --verbose > $o/bench.json 2> $o/bench.err; tail -3 $o/bench.err
 # 2. one rank's share of the 8-GPU run (4 pairs per step): coalesced, not coalesced, with the RCCL path forced on the one rank
-python bench.py --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err
-python bench.py --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline --no-coalesce > $o/bench_p4_nocoalesce.json 2> $o/bench_p4_nocoalesce.err
-STITCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4_forcedist.json 2> $o/bench_p4_forcedist.err
-python bench.py --steps 20 --warmup 5 --pixel u8 --no-cpu-baseline > $o/bench_u8.json 2> $o/bench_u8.err
+python bench.py --full --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4.json 2> $o/bench_p4.err
+python bench.py --full --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline --no-coalesce > $o/bench_p4_nocoalesce.json 2> $o/bench_p4_nocoalesce.err
+STITCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --pairs-per-step 4 --no-cpu-baseline > $o/bench_p4_forcedist.json 2> $o/bench_p4_forcedist.err
+python bench.py --full --steps 20 --warmup 5 --pixel u8 --no-cpu-baseline > $o/bench_u8.json 2> $o/bench_u8.err
 for f in bench bench_p4 bench_p4_nocoalesce bench_p4_forcedist bench_u8; do python - $o/$f.json <<'PY'
 import json,sys
 try:

@@ -6,11 +6,11 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/c5; rm -rf $O; mkdir -p $O
 ARGS="--frame 16384 --pairs-per-step 1 --batch 1 --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-single --no-verify"
-timeout -k 10 500 python3 bench.py $ARGS > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 600 $O/bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py $ARGS --no-kernel-events > $O/bench_under_rocprof.json 2> $O/trace.err
+timeout -k 10 500 python3 bench.py --full $ARGS > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 600 $O/bench.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full $ARGS --no-kernel-events > $O/bench_under_rocprof.json 2> $O/trace.err
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv 2>/dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -- python3 bench.py $ARGS --no-kernel-events > $O/pmc_$C.json 2> $O/pmc_$C.err
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -- python3 bench.py --full $ARGS --no-kernel-events > $O/pmc_$C.json 2> $O/pmc_$C.err
   python - $O/pmc_$C $C > $O/pmc_$C.csv <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)

@@ -9,7 +9,7 @@ for seed in ${FUZZ_SEEDS:-401 402 403}; do
 done
 FUZZ_GENERAL=1 FUZZ_BIG=1 timeout -k 10 900 python scripts/fuzz_pairs.py 501 ${FUZZ_NBIG:-40} > $O/big_501.log 2>&1; tail -1 $O/big_501.log
 grep -h "MISMATCH" $O/*.log | head -20
-timeout -k 10 600 python bench.py --verbose > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+timeout -k 10 600 python bench.py --full --verbose > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
 python - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c = d["config"]

@@ -71,3 +71,15 @@ def test_importing_bench_does_not_import_torch():
     code = "import sys; sys.path.insert(0, %r); import bench; assert 'torch' not in sys.modules; print('ok')" % ROOT
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    # --dump-outputs samples the same elements in every run, and 32 mosaics of the metric's size stay under 64 MB
+    sys.path.insert(0, ROOT)
+    import bench
+    numel = 3 * 4096 * 6144
+    a, b = bench.dump_sample_index(numel, 32), bench.dump_sample_index(numel, 32)
+    assert a.dtype.name == "int64" and (a == b).all() and (a[1:] > a[:-1]).all() and a[0] >= 0 and a[-1] < numel
+    assert a.size * (4 * 32 + 8) + 24 * 32 <= 64_000_000 and a.size > 200_000
+    small = bench.dump_sample_index(1000, 5)
+    assert small.size <= 1000 and (small[1:] > small[:-1]).all()
