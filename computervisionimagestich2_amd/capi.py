@@ -90,6 +90,10 @@ def lib():
         L.stitch_plan_destroy.argtypes = [C.c_void_p]
         L.stitch_blend_opts_default.restype = None
         L.stitch_bmp_file_bytes.restype = C.c_size_t
+        vp, i32 = C.c_void_p, C.c_int
+        L.stitch_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
+        L.stitch_dev_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp]
+        L.stitch_dev_match_l1_ratio_many.argtypes = [vp, i32, C.c_double, vp]
         _lib = L
     return _lib
 
@@ -370,6 +374,79 @@ def shift_points(x, y, ox, oy):
     ix, iy = np.empty(x.size, np.int32), np.empty(x.size, np.int32)
     _chk(lib().stitch_shift_points(_p(x), _p(y), _p(ix), _p(iy), x.size, int(ox), int(oy)))
     return x, y, ix, iy
+
+
+# ---- descriptor matching: ImageProcess::getImgPair (ImageProcess.cpp:273-351) -----------------------------------------------
+DESCRIPTOR_DIM = 128  # STITCH_DESCRIPTOR_DIM (DESCRIPTOR_SUM, ImageProcess.h:20)
+RATIO_THRESHOLD = 0.5  # ImageProcess.h:22
+
+
+class MatchDesc(C.Structure):
+    """stitch_match_desc: one (data, query) set of a batched match (device pointers)."""
+    _fields_ = [("db", C.c_void_p), ("query", C.c_void_p), ("n_db", C.c_int32), ("n_query", C.c_int32), ("nn", C.c_void_p),
+                ("dist2", C.c_void_p), ("pairs", C.c_void_p), ("count", C.c_void_p)]
+
+
+def _desc_rows(a):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != DESCRIPTOR_DIM:
+        raise ValueError(f"expected (n, {DESCRIPTOR_DIM}) float32 descriptors, got {a.shape}")
+    return a
+
+
+def match(db, query, ratio=RATIO_THRESHOLD):
+    """Exact L1 two-nearest-neighbour search of every `query` row among the `db` rows with the ratio test of getImgPair.
+    Returns (pairs, nn, d0, d1): pairs (count, 2) int32 of (db index, query index) in query order; per query the index of
+    the nearest row (-1 without data) and the two smallest distances (NaN where there is no such neighbour)."""
+    db, query = _desc_rows(db), _desc_rows(query)
+    nq = query.shape[0]
+    nn = np.empty(nq, np.int32)
+    dist2 = np.empty((nq, 2), np.float32)
+    pairs = np.empty((max(nq, 1), 2), np.int32)
+    count = C.c_int32(0)
+    _chk(lib().stitch_match_l1_ratio(_p(db), db.shape[0], _p(query), nq, C.c_double(ratio), _p(nn), _p(dist2), _p(pairs),
+                                     C.byref(count)))
+    return pairs[:count.value].copy(), nn, dist2[:, 0].copy(), dist2[:, 1].copy()
+
+
+def _tdesc(t):
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == DESCRIPTOR_DIM):
+        raise ValueError(f"expected a contiguous (n, {DESCRIPTOR_DIM}) float32 device tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _match_outputs(db, query, want_dist=True):
+    import torch
+    nq, dev = query.shape[0], query.device
+    return dict(pairs=torch.empty((max(nq, 1), 2), dtype=torch.int32, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev),
+                nn=torch.empty(nq, dtype=torch.int32, device=dev),
+                dist2=torch.empty((nq, 2), dtype=torch.float32, device=dev) if want_dist else None)
+
+
+def _mdesc(db, query, o):
+    return MatchDesc(_dp(db), _dp(query), db.shape[0], query.shape[0], _dp(o["nn"]),
+                     _dp(o["dist2"]) if o["dist2"] is not None else None, _dp(o["pairs"]), _dp(o["count"]))
+
+
+def dev_match(db, query, ratio=RATIO_THRESHOLD, want_dist=True):
+    """match() on device tensors, enqueued on torch's current stream (no synchronisation).  Returns a dict of device
+    tensors: pairs ((n_query, 2) int32, the first `count` rows valid), count ((1,) int32), nn, dist2 ((n_query, 2) or None)."""
+    db, query = _tdesc(db), _tdesc(query)
+    o = _match_outputs(db, query, want_dist)
+    d = _mdesc(db, query, o)
+    _chk(lib().stitch_dev_match_l1_ratio(d.db, d.n_db, d.query, d.n_query, C.c_double(ratio), d.nn, d.dist2, d.pairs, d.count,
+                                         _stream()))
+    return o
+
+
+def dev_match_many(sets, ratio=RATIO_THRESHOLD, want_dist=True):
+    """Many (db, query) pairs of device tensors in one launch sequence; returns one dict per set as dev_match does."""
+    sets = [(_tdesc(a), _tdesc(b)) for a, b in sets]
+    outs = [_match_outputs(a, b, want_dist) for a, b in sets]
+    arr = (MatchDesc * max(len(sets), 1))(*[_mdesc(a, b, o) for (a, b), o in zip(sets, outs)])
+    _chk(lib().stitch_dev_match_l1_ratio_many(arr, len(sets), C.c_double(ratio), _stream()))
+    return outs
 
 
 # ---- device-resident entry points (torch tensors on the HIP device) --------------------------------------------

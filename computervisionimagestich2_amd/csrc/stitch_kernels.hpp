@@ -92,5 +92,6 @@ __device__ __forceinline__ void bilinear3(const PX* __restrict__ src, int w, int
 #include "k_coarse.inc"  // all levels below a size threshold in one launch: REDUCE to the top, top blend, collapse back up
 #include "k_equalize.inc"  // equalisation and luminance mix (E1-E3, M1)
 #include "k_synth.inc"  // synthetic frames and small utility kernels
+#include "k_match.inc"  // exact L1 two-nearest-neighbour descriptor matching with the ratio test (getImgPair)
 
 }  // namespace sk

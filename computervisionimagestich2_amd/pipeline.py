@@ -642,3 +642,69 @@ class LocalBandGroup:
         for b in self.bands:
             b.seam = b.band.status()
         return [st["out"] for st in state]
+
+
+# ---- descriptor matching: ImageProcess::matching's use of getImgPair (ImageProcess.cpp:117-137, :177-198) ------------------
+MATCH_THRESHOLD = 20  # THRESHOLD, ImageProcess.h:18: frames i, j are neighbours when getImgPair(imgs[i], imgs[j]) has >= 20 pairs
+
+
+def feature_order(descriptors, keypoints=None):
+    """The order of Image::features, a std::map<std::vector<float>, VlSiftKeypoint> filled by siftAlgorithm
+    (ImageProcess.cpp:44-99): descriptors sorted lexicographically as float vectors, an identical descriptor kept once -- the
+    first inserted (std::map::insert keeps the existing entry).  `descriptors` (n, 128) in insertion order, `keypoints` any
+    array with n rows (or None).  Returns (ordered descriptors, ordered keypoints or None, index into the inputs)."""
+    import numpy as np
+    d = np.ascontiguousarray(descriptors, dtype=np.float32)
+    if d.ndim != 2 or d.shape[1] != capi.DESCRIPTOR_DIM:
+        raise ValueError(f"expected (n, {capi.DESCRIPTOR_DIM}) descriptors, got {d.shape}")
+    order = np.lexsort(d.T[::-1])  # stable: equal descriptors stay in insertion order
+    s = d[order]
+    keep = np.ones(len(order), bool)
+    keep[1:] = np.any(s[1:] != s[:-1], axis=1)  # float ==, as the map's equivalence !(a < b) && !(b < a) (so -0 == +0)
+    idx = order[keep]
+    return d[idx], (np.asarray(keypoints)[idx] if keypoints is not None else None), idx
+
+
+def _device_sets(desc_sets):
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return [torch.as_tensor(d, dtype=torch.float32).to(dev).contiguous().reshape(-1, capi.DESCRIPTOR_DIM) for d in desc_sets]
+
+
+def match_counts(desc_sets, ratio=capi.RATIO_THRESHOLD):
+    """N x N int matrix: [i][j] = the number of pairs getImgPair(imgs[i], imgs[j]) returns (data = frame i, queries = frame j;
+    0 on the diagonal) for map-ordered descriptor sets, all ordered pairs in one batched launch sequence.  stichingMat[i][j]
+    of matching() is `counts >= MATCH_THRESHOLD` (the reference skips the call for [i][j] once [j][i] is set, which only
+    saves work: the flag is set either way)."""
+    import numpy as np
+    import torch
+    sets = _device_sets(desc_sets)
+    n = len(sets)
+    ij = [(i, j) for i in range(n) for j in range(n) if i != j]
+    outs = capi.dev_match_many([(sets[i], sets[j]) for i, j in ij], ratio, want_dist=False)
+    counts = np.zeros((n, n), np.int64)
+    if ij:
+        got = torch.cat([o["count"] for o in outs]).cpu().numpy()
+        for (i, j), c in zip(ij, got):
+            counts[i, j] = int(c)
+    return counts
+
+
+def pair_lists(desc_src, kp_src, desc_dst, kp_dst, ratio=capi.RATIO_THRESHOLD):
+    """The two point lists matching() hands to RANSAC for a stitched neighbour (ImageProcess.cpp:177-198): srcToDstPair =
+    getImgPair(src, dst), dstToSrcPair = getImgPair(dst, src); the longer list wins (srcToDst on a strict >, else dstToSrc) and
+    the other becomes its mirror.  Descriptors in map order, keypoints with the same rows (e.g. (n, 2) x/y).  Returns
+    (src_to_dst, dst_to_src), each a pair of arrays (ImgPair.src keypoints, ImgPair.dst keypoints)."""
+    import numpy as np
+    kp_src, kp_dst = np.asarray(kp_src), np.asarray(kp_dst)
+    a, b = _device_sets([desc_src, desc_dst])
+    o_sd, o_ds = capi.dev_match_many([(a, b), (b, a)], ratio, want_dist=False)
+    p_sd = o_sd["pairs"][: int(o_sd["count"].item())].cpu().numpy()
+    p_ds = o_ds["pairs"][: int(o_ds["count"].item())].cpu().numpy()
+    s2d = (kp_src[p_sd[:, 0]], kp_dst[p_sd[:, 1]])  # ImgPair(A = src keypoint[nn], B = dst keypoint[q])
+    d2s = (kp_dst[p_ds[:, 0]], kp_src[p_ds[:, 1]])
+    if len(p_sd) > len(p_ds):
+        d2s = (s2d[1], s2d[0])
+    else:
+        s2d = (d2s[1], d2s[0])
+    return s2d, d2s

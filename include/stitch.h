@@ -473,6 +473,42 @@ int stitch_dev_check_fastdiv(float w, unsigned long long *tested, unsigned long 
  * w, h even, 256 <= w, 4 <= h, both <= 16384.  Returns the samples compared and the number that differ -- which must be 0. */
 int stitch_dev_check_collapse_taps(int w, int h, int probe, unsigned long long *compared, unsigned long long *mismatches);
 
+/* ---- descriptor matching: ImageProcess::getImgPair (ImageProcess.cpp:273-351) ------------------------------------------------
+ * Descriptors are row-major n x STITCH_DESCRIPTOR_DIM float32 rows, finite.  A caller of the reference fills `db` from imgA.features
+ * and `query` from imgB.features, both in the std::map's order.  For every query row q the call finds, over all
+ * data rows, the two smallest L1 distances d0 <= d1 -- each the sequential fp32 sum of _vl_distance_l1_f (vl/mathop.c:307-318) --
+ * and the index of d0, and accepts q where (float)(d0 / d1) < ratio (RATIO_THRESHOLD 0.5, ImageProcess.h:22).  The search is
+ * exact; the reference's kd-forest gives the same answer on descriptors in [0, 1), which is all VLFeat's SIFT produces (outside
+ * that range its squared split-distance bound can prune a true neighbour; this search does not).
+ *   nn      n_query int32: index of d0, or -1 without data rows (may be NULL).  Equal distances: the lowest index wins.  The
+ *           reference does not pin the index of a REJECTED query (its traversal order decides among ties); an accepted query
+ *           has d0 < d1, so its index is unique.
+ *   dist2   2 * n_query floats: d0, d1 per query (may be NULL); NaN where there is no such neighbour (d1 with one data row, as
+ *           VLFeat reports it; both with none).
+ *   pairs   up to 2 * n_query int32: (data index, query index) per accepted query, in query order -- the ImgPair list
+ *           (A.keypoint[data], B.keypoint[query]).
+ *   count   number of accepted queries.
+ * n_db == 0 or n_query == 0 is STITCH_OK with *count = 0 (the reference asserts in vl_kdforest_build instead).  Ties cannot change
+ * the accepted list: a tied nearest distance gives ratio 1, two zero distances 0/0 = NaN, one data row d1 = NaN -- all rejected. */
+#define STITCH_DESCRIPTOR_DIM 128 /* DESCRIPTOR_SUM, ImageProcess.h:20 */
+int stitch_match_l1_ratio(const float *db, int n_db, const float *query, int n_query, double ratio, int32_t *nn, float *dist2,
+                          int32_t *pairs, int32_t *count);
+/* The same on DEVICE pointers (count too), enqueued on `stream` with stream-ordered scratch; no host synchronisation. */
+int stitch_dev_match_l1_ratio(const float *d_db, int n_db, const float *d_query, int n_query, double ratio, int32_t *d_nn,
+                              float *d_dist2, int32_t *d_pairs, int32_t *d_count, void *stream);
+/* Many independent (data, query) sets -- e.g. the all-pairs loop of ImageProcess::matching (ImageProcess.cpp:117-137) -- in one
+ * launch sequence (three kernels per 16 sets).  Entries may share data or query buffers; every pointer is a device pointer. */
+typedef struct stitch_match_desc {
+    const float *db;
+    const float *query;
+    int32_t n_db, n_query;
+    int32_t *nn;    /* may be NULL */
+    float *dist2;   /* may be NULL */
+    int32_t *pairs; /* 2 * n_query int32 */
+    int32_t *count; /* one int32 */
+} stitch_match_desc;
+int stitch_dev_match_l1_ratio_many(const stitch_match_desc *descs, int n, double ratio, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
