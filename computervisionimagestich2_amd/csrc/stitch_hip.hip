@@ -225,7 +225,7 @@ struct Tuning {
     static Tuning from_env() {
         Tuning t{};
         t.wavefront = env_int("STITCH_WAVEFRONT");
-        t.no_fuse = std::getenv("STITCH_NO_FUSE") != nullptr;
+        t.no_fuse = env_int("STITCH_NO_FUSE") > 0;
         t.no_src_fuse = env_int("STITCH_NO_SRC_FUSE") > 0;
         t.no_zero_tiles = env_int("STITCH_NO_ZERO_TILES") > 0;
         t.crows_l0 = env_int("STITCH_CROWS_L0");
@@ -234,9 +234,9 @@ struct Tuning {
         t.xbyf_wgs = env_int("STITCH_XBYF_WGS");
         t.xbyf_spin_limit = env_int("STITCH_XBYF_SPIN_LIMIT");
         t.xbyf_early = env_int("STITCH_XBYF_EARLY");
-        t.y2 = std::getenv("STITCH_Y2") != nullptr;
+        t.y2 = env_int("STITCH_Y2") > 0;
         t.recompute = env_int("STITCH_RECOMPUTE");
-        t.stamp = std::getenv("STITCH_WAVEFRONT_STAMP") != nullptr;
+        t.stamp = env_int("STITCH_WAVEFRONT_STAMP") > 0;
         t.gate64 = env_int("STITCH_GATE64") > 0;
         t.coarse = env_int("STITCH_COARSE");
         t.single_fast = env_int("STITCH_SINGLE_FAST");
@@ -980,7 +980,7 @@ int dev_project(const PX* d_src, int w, int h, float fov_deg, PX* d_dst, void* s
     // source row depends on the output row alone -- and it runs at 0.52 of the roofline, 0.073 ms at 4096 x 3072 against 0.092
     // through LDS; unsigned char: 0.063 -> 0.050)
     bool tiled = (w % 4) == 0 && (unsigned long long)w * h * 3 * sizeof(PX) < 0xfffffff0ULL && (reinterpret_cast<uintptr_t>(d_src) % 4) == 0 &&
-                 !(pp.flag && sizeof(PX) == 4) && !std::getenv("STITCH_PROJECT1");
+                 !(pp.flag && sizeof(PX) == 4) && !(Tuning::env_int("STITCH_PROJECT1") > 0);
     if (tiled) {
         // the box of a tile, as the kernel derives it, over the tiles that can have the largest one (those farthest from the
         // axis and from the middle: the four corner tiles), plus a margin of two rows and two chunks.  `along` = the axis k
@@ -1373,7 +1373,7 @@ int host_pair(const PX* frame, int fw, int fh, const double pm[8], float offx, f
 
 // planes of n bytes that can be moved as 32-bit words (the four-pixels-per-work-item kernels); STITCH_BYTE_KERNELS=1: never
 bool words_ok(const void* base, size_t n) {
-    return (n % 4) == 0 && (reinterpret_cast<uintptr_t>(base) % 4) == 0 && !std::getenv("STITCH_BYTE_KERNELS");
+    return (n % 4) == 0 && (reinterpret_cast<uintptr_t>(base) % 4) == 0 && !(Tuning::env_int("STITCH_BYTE_KERNELS") > 0);
 }
 
 // The mix's divides by `den` as multiplications by its reciprocal plus one fma correction -- only where that is PROVEN equal for
@@ -1382,7 +1382,7 @@ bool words_ok(const void* base, size_t n) {
 // (num, den); the last few verdicts are kept).  STITCH_NO_FASTDIV=1: always divide.
 MixK mix_params(double num, double den) {
     MixK k{num, den, 0.0};
-    static const bool off = std::getenv("STITCH_NO_FASTDIV") != nullptr;
+    static const bool off = Tuning::env_int("STITCH_NO_FASTDIV") > 0;  // read once per process
     if (off || !(den == den) || den == 0.0 || std::isinf(den) || !(num == num) || std::isinf(num)) return k;
     struct Verdict {
         double num, den;

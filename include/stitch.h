@@ -191,9 +191,13 @@ int stitch_plan_fast_paths(const stitch_plan *plan);
 int stitch_plan_call_forms(const stitch_plan *plan, int n_pairs);
 /* First pyramid level of the COARSE_LEVELS launch (0 = none: every level has its own launch sequence). */
 int stitch_plan_coarse_from(const stitch_plan *plan);
-/* Tuning / A-B switches, read from the environment when a plan is created (none of them changes a result bit).  The
- * host-buffer entry points read them again on every call and key their workspace cache on the values, so a switch that
- * changes between two calls takes effect at once:
+/* Tuning / A-B switches, read from the environment when a plan is created (none of them changes a result bit).  A flag
+ * switch ("=1") is on when it is set to a number above 0: "=0" means off.  The host-buffer entry points read the plan
+ * switches below again on every call and key their workspace cache on the values, so a switch that changes between two
+ * calls takes effect at once.  The exceptions are read at other times and say so: STITCH_NO_FASTDIV, STITCH_COPY_THREADS and
+ * STITCH_PLAN_CACHE once per process (the first call that needs them), STITCH_BAND_* when a band is created,
+ * STITCH_BYTE_KERNELS and STITCH_PROJECT1 on every call of the kernels they select.  tests/switch_table.py lists every
+ * switch with the call forms and shapes the test suite runs it on.
  *   STITCH_WAVEFRONT=<n>      fused sweep on exactly n finest levels (0 = never)
  *   STITCH_NO_FUSE=1          blur and decimation as separate kernels, level-0 mask materialised
  *   STITCH_NO_SRC_FUSE=1      materialise level 0 (k_compose) instead of gathering it from the frames where it is needed
@@ -241,12 +245,23 @@ int stitch_plan_coarse_from(const stitch_plan *plan);
  *                             storer sweeps take): 0 = never (a pair of >= 800 bands then runs the batch's fused sweep, as until round 4),
  *                             1 = at the first four levels whatever their size (tests); default: where the
  *                             separate sweeps are bound by their bytes, from STITCH_XBYM_MPIX megapixels per plane (default 20)
+ *   STITCH_XBYM_MPIX=<n>      megapixels per plane from which a lone pair's level takes k_vv_xby_m when STITCH_XBYM is unset (default 20;
+ *                             0 = every level of the first four that the form can take)
  *   STITCH_XBYM_STAMP=1       diagnostics: per-tile time stamps of the five wavefronts of one band of k_vv_xby_m, printed at plan destruction
  *   STITCH_COARSE_LDS=0       coarse levels in global memory (k_coarse) instead of LDS (k_coarse_lds, where the levels fit into 144 KB)
  *   STITCH_GATE64=1           implicit level-0 mask, source fusion and zero-tile flags only for level heights that are multiples
  *                             of 64 (the round-2 behaviour; A/B runs)
  *   STITCH_NO_FASTDIV=1       luminance mix: always the IEEE divide (default: reciprocal + fma correction where the host has
- *                             shown it equal for every operand the mix can meet, once per (num, den))
+ *                             shown it equal for every operand the mix can meet, once per (num, den)).  Read once per process
+ *   STITCH_BYTE_KERNELS=1     equalise / luminance mix / finish: one byte per work-item (k_hist, ...) even where a plane can be
+ *                             moved as 32-bit words (k_hist4, ...: w * h a multiple of 4, a 4-byte aligned image)
+ *   STITCH_COPY_THREADS=<n>   host-buffer entry points: threads (0..16, default 4) of the chunked staging copier for copies of 4 MB
+ *                             and more; 0 = one plain hipMemcpy.  Read once per process
+ *   STITCH_PROJECT1=1         projection: k_project (one pixel per work-item) instead of the LDS-tiled k_project_lds
+ *   STITCH_PLAN_CACHE=<n>     idle workspaces the host-buffer entry points keep (default 8).  Read once per process
+ *   STITCH_BAND_PLANES=1      band split (stitch_band_*): materialised level-0 planes and mask.  Read when a band is created
+ *   STITCH_BAND_PLAIN=1       band split: anticausal y sweep and decimation as two kernels.  Read when a band is created
+ *   STITCH_WAVEFRONT_STAMP=1, STITCH_COARSE_STAMP=1, STITCH_D7_STAMP_MODE=<n>: diagnostics like the other *_STAMP switches
  *   STITCH_Y2=1               causal y sweep always with two columns per work-item (default: one column where a launch has
  *                             fewer than 1.5 wavefronts per SIMD)
  *   STITCH_RECOMPUTE=<0|1|2>  fused levels: 0 (default) = the causal x sweep writes its samples and the fused sweep reads
