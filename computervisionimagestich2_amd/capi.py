@@ -94,6 +94,10 @@ def lib():
         L.stitch_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
         L.stitch_dev_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp]
         L.stitch_dev_match_l1_ratio_many.argtypes = [vp, i32, C.c_double, vp]
+        L.stitch_dev_ransac_many.argtypes = [vp, i32, vp, vp]
+        L.stitch_ransac.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        L.stitch_ransac_rand.restype = None
+        L.stitch_ransac_rand.argtypes = [C.c_uint32, vp, i32]
         _lib = L
     return _lib
 
@@ -447,6 +451,84 @@ def dev_match_many(sets, ratio=RATIO_THRESHOLD, want_dist=True):
     arr = (MatchDesc * max(len(sets), 1))(*[_mdesc(a, b, o) for (a, b), o in zip(sets, outs)])
     _chk(lib().stitch_dev_match_l1_ratio_many(arr, len(sets), C.c_double(ratio), _stream()))
     return outs
+
+# ---- map estimation: ImageProcess::RANSAC (ImageProcess.cpp:395-529) -----------------------------------------------------
+RANSAC_ROUNDS, RANSAC_THRESHOLD, RANSAC_SEED, RANSAC_INFO = 72, 4.0, 666666, 5
+RANSAC_OK, RANSAC_TOO_FEW, RANSAC_NO_CONSENSUS, RANSAC_DRAW_CAP = 0, 1, 2, 3
+
+
+class RansacOpts(C.Structure):
+    """stitch_ransac_opts; the defaults are the reference's values."""
+    _fields_ = [("rounds", C.c_int32), ("threshold", C.c_float), ("seed", C.c_uint32), ("max_draws", C.c_int32)]
+
+    def __init__(self, rounds=0, threshold=RANSAC_THRESHOLD, seed=RANSAC_SEED, max_draws=0):
+        super().__init__(int(rounds), float(threshold), int(seed), int(max_draws))
+
+
+class RansacDesc(C.Structure):
+    """stitch_ransac_desc: one list of a batched estimation (device pointers)."""
+    _fields_ = [("src_x", C.c_void_p), ("src_y", C.c_void_p), ("dst_x", C.c_void_p), ("dst_y", C.c_void_p), ("pairs", C.c_void_p),
+                ("count", C.c_void_p), ("n_max", C.c_int32), ("mirror", C.c_int32), ("p", C.c_void_p), ("inliers", C.c_void_p),
+                ("info", C.c_void_p)]
+
+
+def ransac_rand(n, seed=RANSAC_SEED):
+    """The first n values of rand() after srand(seed) as the library generates them (host hook) -> int32 array."""
+    out = np.empty(int(n), np.int32)
+    lib().stitch_ransac_rand(C.c_uint32(int(seed)), _p(out), int(n))
+    return out
+
+
+def ransac(src_x, src_y, dst_x, dst_y, mirror=False, opts=None):
+    """ImageProcess::RANSAC on one list of pairs (src point i, dst point i) given as host arrays.  Returns (p, inliers, info):
+    the 8 doubles of the map src -> dst (NaN when info[0] != RANSAC_OK), the winning inlier indices in increasing order, and
+    info = [status, n, winning round, winning count, rand() values consumed]."""
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (src_x, src_y, dst_x, dst_y)]
+    n = a[0].size
+    if any(v.size != n for v in a):
+        raise ValueError("the four coordinate arrays differ in length")
+    p, inl, info = np.empty(8, np.float64), np.empty(max(n, 1), np.int32), np.empty(RANSAC_INFO, np.int32)
+    o = opts if opts is not None else RansacOpts()
+    _chk(lib().stitch_ransac(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), n, int(bool(mirror)), C.byref(o), _p(p), _p(inl), _p(info)))
+    return p, inl[:max(int(info[3]), 0)].copy(), info
+
+
+def _tvec(t, dtype, what):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError(f"expected a contiguous {dtype} device tensor for {what}")
+    return t
+
+
+def dev_ransac_many(lists, opts=None, want_inliers=True):
+    """Many lists in one launch sequence on torch's current stream (no synchronisation).  Each entry is a dict of device
+    tensors: src_x, src_y, dst_x, dst_y (float32 keypoint coordinates of the two frames) and optionally pairs ((n_max, 2)
+    int32 of (src row, dst row), e.g. dev_match's output), count ((1,) int32) and mirror (bool).  Without pairs, pair i is
+    (src i, dst i).  Returns (p, info, inliers): (n, 8) float64, (n, 5) int32, and a list of int32 tensors (the winning indices,
+    then -1) or None."""
+    import torch
+    n = len(lists)
+    dev = lists[0]["src_x"].device if n else torch.device("cuda", torch.cuda.current_device())
+    p = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    info = torch.empty((n, RANSAC_INFO), dtype=torch.int32, device=dev)
+    descs, inl = [], []
+    for i, e in enumerate(lists):
+        xy = [_tvec(e[k], torch.float32, k) for k in ("src_x", "src_y", "dst_x", "dst_y")]
+        pairs, count = e.get("pairs"), e.get("count")
+        if pairs is not None:
+            n_max = _tvec(pairs, torch.int32, "pairs").numel() // 2
+        else:
+            n_max = min(v.numel() for v in xy)
+        if count is not None:
+            _tvec(count, torch.int32, "count")
+        inl.append(torch.empty(n_max, dtype=torch.int32, device=dev) if want_inliers else None)
+        descs.append(RansacDesc(_dp(xy[0]), _dp(xy[1]), _dp(xy[2]), _dp(xy[3]), _dp(pairs) if pairs is not None else None,
+                                _dp(count) if count is not None else None, n_max, int(bool(e.get("mirror", False))),
+                                C.c_void_p(p.data_ptr() + 64 * i), _dp(inl[-1]) if want_inliers else None,
+                                C.c_void_p(info.data_ptr() + 4 * RANSAC_INFO * i)))
+    arr = (RansacDesc * max(n, 1))(*descs)
+    o = opts if opts is not None else RansacOpts()
+    _chk(lib().stitch_dev_ransac_many(arr, n, C.byref(o), _stream()))
+    return p, info, (inl if want_inliers else None)
 
 
 # ---- device-resident entry points (torch tensors on the HIP device) --------------------------------------------

@@ -2530,3 +2530,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 
 #include "stitch_band.inc"
 #include "stitch_match.inc"
+#include "stitch_ransac.inc"

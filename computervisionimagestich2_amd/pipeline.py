@@ -1,5 +1,5 @@
 """Host-side drivers above the C ABI: the benchmark configurations of BASELINE.json, the panorama chain of
-ImageProcess::matching (ImageProcess.cpp:159-268, hot-path calls only), and the sharding of independent pairs
+ImageProcess::matching (ImageProcess.cpp:159-268, hot-path calls only; from features alone: panorama_from_features), and the sharding of independent pairs
 across the GPUs of a node (one process per GPU, torch.distributed; backend "nccl" is RCCL over xGMI).
 
 Nothing here computes pixels: every per-pixel operation is a HIP kernel reached through capi.
@@ -708,3 +708,125 @@ def pair_lists(desc_src, kp_src, desc_dst, kp_dst, ratio=capi.RATIO_THRESHOLD):
     else:
         s2d = (d2s[1], d2s[0])
     return s2d, d2s
+
+
+# ---- map estimation and the whole of matching() from features (ImageProcess.cpp:101-268) -------------------------------------
+def pair_maps(desc_src, kp_src, desc_dst, kp_dst, ratio=capi.RATIO_THRESHOLD, opts=None):
+    """forward_H and backward_H of a stitched neighbour (ImageProcess.cpp:177-202) from map-ordered descriptors and (n, 2) x/y
+    keypoints of the frame in the mosaic (src) and of the frame to warp (dst): both getImgPair calls, the longer-list rule and
+    both RANSAC runs are enqueued back to back -- the rule is decided on the device from the two counts -- and the maps are read
+    back once at the end.  Returns (p_fwd, p_bwd, info): 8 doubles each and the two info rows (forward, backward)."""
+    import numpy as np
+    import torch
+    a, b = _device_sets([desc_src, desc_dst])
+    dev = a.device
+    ks = torch.as_tensor(np.ascontiguousarray(kp_src, dtype=np.float32)).to(dev).reshape(-1, 2)
+    kd = torch.as_tensor(np.ascontiguousarray(kp_dst, dtype=np.float32)).to(dev).reshape(-1, 2)
+    ns = ks.shape[0]
+    x, y = torch.cat([ks[:, 0], kd[:, 0]]).contiguous(), torch.cat([ks[:, 1], kd[:, 1]]).contiguous()  # src rows, then dst rows
+    o_sd, o_ds = capi.dev_match_many([(a, b), (b, a)], ratio, want_dist=False)
+    cap = max(o_sd["pairs"].shape[0], o_ds["pairs"].shape[0])
+
+    def padded(t):
+        return torch.cat([t, t.new_zeros((cap - t.shape[0], 2))]) if t.shape[0] < cap else t
+    sd, ds = padded(o_sd["pairs"]), padded(o_ds["pairs"])
+    # srcToDstPair as (row of a src keypoint, row of a dst keypoint): getImgPair(src, dst) itself when it is the longer list
+    # (strictly), else the mirror of getImgPair(dst, src) (:185-198); dstToSrcPair is its mirror either way
+    use_sd = o_sd["count"] > o_ds["count"]
+    s2d = torch.where(use_sd, torch.stack([sd[:, 0], sd[:, 1] + ns], 1), torch.stack([ds[:, 1], ds[:, 0] + ns], 1)).contiguous()
+    count = torch.where(use_sd, o_sd["count"], o_ds["count"]).contiguous()
+    lst = dict(src_x=x, src_y=y, dst_x=x, dst_y=y, pairs=s2d, count=count)
+    p, info, _ = capi.dev_ransac_many([dict(lst, mirror=True), dict(lst, mirror=False)], opts, want_inliers=False)
+    got = torch.cat([p, info.to(torch.float64)], 1).cpu().numpy()  # the one read-back
+    return got[0, :8].copy(), got[1, :8].copy(), got[:, 8:].astype(np.int64)
+
+
+def stitch_order(counts, threshold=MATCH_THRESHOLD):
+    """The host logic of matching() (ImageProcess.cpp:101-175) and getMiddleIndex (:353-393) restated literally from the
+    N x N matrix of getImgPair counts (match_counts): returns (start frame, [(srcIndex, dstIndex), ...]) -- dstIndex is warped
+    onto the mosaic that already holds srcIndex."""
+    n = len(counts)
+    mat = [[False] * n for _ in range(n)]
+    nxt = [[] for _ in range(n)]
+    for i in range(n):
+        for j in range(n):
+            if i == j:
+                continue
+            if mat[j][i]:
+                mat[i][j] = True
+                nxt[i].append(j)
+                continue
+            if counts[i][j] >= threshold:
+                mat[i][j] = True
+                nxt[i].append(j)
+    # getMiddleIndex: walk from an edge frame (exactly one neighbour; frame 0 without one) and take the middle of the walk
+    edge = 0
+    for i in range(n):
+        if len(nxt[i]) == 1:
+            edge = i
+            break
+    next_one = edge
+    que = []
+    for _index in range(n):
+        if not que:
+            que.append(edge)
+        for i in range(n):
+            if next_one == i:
+                continue
+            if mat[next_one][i]:
+                if i < len(que):  # the reference compares the frame index i with the queue POSITIONS j = 0 .. size-1 (:377-382)
+                    continue
+                if i != edge:
+                    que.append(i)
+                next_one = i
+                break
+    start = que[len(que) // 2]
+    order = []
+    wait = [start]
+    while wait:
+        src = wait.pop(0)
+        for dst in reversed(nxt[src]):
+            if not mat[src][dst]:
+                continue
+            mat[src][dst] = mat[dst][src] = False
+            wait.append(dst)
+            order.append((src, dst))
+    return start, order
+
+
+def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False):
+    """ImageProcess::matching (ImageProcess.cpp:101-268) from the frames and their SIFT features alone: frames is a list of
+    (3, H, W) uint8 device tensors (unprojected), features a list of (descriptors (n, 128), keypoints (n, 2) x/y) in the
+    std::map's order (feature_order).  Neighbour matrix, stitch order, per step both maps (pair_maps), the stitch step and the
+    feature updates of :226-227.  Returns the final mosaic (and, with return_steps, what every step used and produced)."""
+    import numpy as np
+    desc = [np.ascontiguousarray(d, dtype=np.float32) for d, _ in features]
+    kps = [np.array(k, dtype=np.float32).reshape(-1, 2) for _, k in features]
+    start, order = stitch_order(match_counts(desc))
+    proj = {}
+
+    def projected(i):
+        if i not in proj:
+            proj[i] = capi.dev_project(frames[i])
+        return proj[i]
+
+    result = projected(start)
+    pre = start
+    steps = []
+    for src, dst in order:
+        p_fwd, p_bwd, info = pair_maps(desc[src], kps[src], desc[dst], kps[dst])
+        if info[0][0] != capi.RANSAC_OK or info[1][0] != capi.RANSAC_OK:
+            raise capi.StitchError(-1, f"frames {src} -> {dst}: no map (RANSAC status {int(info[0][0])} / {int(info[1][0])}, {int(info[0][1])} pairs)")
+        result, g, _seam = capi.dev_step(projected(dst), p_fwd, p_bwd, result, opts)
+        # :226-227: the warped frame's keypoints go through the forward map, those of the frame stitched before move by the offsets
+        x, y, _, _ = capi.map_points(kps[dst][:, 0], kps[dst][:, 1], p_fwd, g.min_x, g.min_y)
+        kps[dst] = np.stack([x, y], 1)
+        x, y, _, _ = capi.shift_points(kps[pre][:, 0], kps[pre][:, 1], g.ox, g.oy)
+        kps[pre] = np.stack([x, y], 1)
+        pre = dst
+        steps.append(dict(start=start, src=dst, p=p_bwd, p_fwd=p_fwd, offx=g.min_x, offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch,
+                          out=result, info=info))
+    if finish:
+        result = result.clone() if return_steps and steps else result
+        capi.dev_finish(result, num, den)
+    return (result, steps) if return_steps else result

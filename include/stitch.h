@@ -524,6 +524,62 @@ typedef struct stitch_match_desc {
 } stitch_match_desc;
 int stitch_dev_match_l1_ratio_many(const stitch_match_desc *descs, int n, double ratio, void *stream);
 
+/* ---- map estimation: ImageProcess::RANSAC (ImageProcess.cpp:395-529) -----------------------------------------------------------
+ * From a list of ImgPair (src keypoint, dst keypoint) the reference estimates the bilinear map dst = f(src),
+ *   X = p0 x + p1 y + p2 x y + p3,  Y = p4 x + p5 y + p6 x y + p7   (p in the order every stitch_warp_* call takes),
+ * and this call gives the same 8 doubles bit for bit:
+ *   - srand(seed) on every call, then `rounds` rounds (:397-403; 72 = ceil(log(1-0.99)/log(1-0.5^4))); the generator is glibc's
+ *     rand() restated (TYPE_3 additive feedback), not the host's libc: the result does not depend on the C library in use;
+ *   - per round 4 distinct indices `rand() % n`, redrawn on a repeat (:409-418); the fit of the 4 pairs in draw order
+ *     (getHomographyMat :439-462 = CImg's LU solve, CImg.h:25911-25953, 25401-25420); the inliers over ALL pairs (:473-497:
+ *     the map in double, rounded to float, float distance < threshold);
+ *   - the EARLIEST round with the largest inlier count wins (:427); the final fit over its inliers in index order
+ *     (getInlinerHomography :500-529: LU for exactly 4 inliers, otherwise CImg's SVD pseudo-inverse, CImg.h:25293-25302,
+ *     25755-25895) with every sum over the inliers added serially in index order.
+ * Where the reference has no answer the list gets a status in info[0], its p is 8 NaNs, the call still returns STITCH_OK and
+ * the other lists of the batch are computed:
+ *   STITCH_RANSAC_TOO_FEW       n < 4: the reference never returns (its redraw loop cannot find a fourth distinct index)
+ *   STITCH_RANSAC_NO_CONSENSUS  no round has an inlier, e.g. identical source points or non-finite coordinates (points on one line still
+ *                               give their pivot rows as inliers): the reference solves
+ *                               an empty system and terminates with a CImgArgumentException
+ *   STITCH_RANSAC_DRAW_CAP      the index walk used max_draws values of rand() before the last round was drawn
+ * info[5] = {status, n, winning round (-1 without), inliers of the winner, values of rand() consumed}. */
+#define STITCH_RANSAC_ROUNDS 72         /* k of ImageProcess.cpp:398 */
+#define STITCH_RANSAC_THRESHOLD 4.0f    /* RANSAC_THRESHOLD, ImageProcess.h:32 */
+#define STITCH_RANSAC_SEED 666666u      /* ImageProcess.cpp:397 */
+#define STITCH_RANSAC_INFO 5
+#define STITCH_RANSAC_OK 0
+#define STITCH_RANSAC_TOO_FEW 1
+#define STITCH_RANSAC_NO_CONSENSUS 2
+#define STITCH_RANSAC_DRAW_CAP 3
+typedef struct stitch_ransac_opts { /* NULL: the reference's values */
+    int32_t rounds;    /* 0: STITCH_RANSAC_ROUNDS; at most 16384                                                     */
+    float threshold;   /* STITCH_RANSAC_THRESHOLD; an inlier has distance < threshold (NaN or <= 0: none)            */
+    uint32_t seed;     /* STITCH_RANSAC_SEED                                                                         */
+    int32_t max_draws; /* bound of the index walk; 0: 32 * rounds + 4096 (a walk over n = 4 uses 8.3 per round)      */
+} stitch_ransac_opts;
+/* One list on DEVICE pointers.  ImgPair i is (src[pairs[2i]], dst[pairs[2i+1]]) -- the (data index, query index) rows
+ * stitch_dev_match_l1_ratio writes, with src = the data frame's keypoints and dst = the query frame's -- or with mirror != 0
+ * ImgPair(dst[...], src[...]), the mirrored list of ImageProcess.cpp:185-198.  The indices are trusted. */
+typedef struct stitch_ransac_desc {
+    const float *src_x, *src_y, *dst_x, *dst_y; /* keypoint coordinate arrays of the two frames                          */
+    const int32_t *pairs; /* 2 * n_max int32; NULL: row i with row i                                                     */
+    const int32_t *count; /* device int32, the number of pairs (clamped to 0 .. n_max); NULL: n_max pairs               */
+    int32_t n_max;        /* capacity of `pairs`; up to 65536 pairs per list are tested                                  */
+    int32_t mirror;
+    double *p;            /* out: 8 doubles                                                                              */
+    int32_t *inliers;     /* out, may be NULL: n_max int32, the winning list in increasing order, then -1               */
+    int32_t *info;        /* out: STITCH_RANSAC_INFO int32                                                               */
+} stitch_ransac_desc;
+/* Many independent lists (the two of a stitched neighbour, ImageProcess.cpp:201-202; the N(N-1) of an all-pairs verification)
+ * in one launch sequence per 16 lists, enqueued on `stream` with stream-ordered scratch; no host synchronisation. */
+int stitch_dev_ransac_many(const stitch_ransac_desc *descs, int n, const stitch_ransac_opts *opts, void *stream);
+/* One list on HOST arrays of n floats (ImgPair i = (src i, dst i), or mirrored); inliers may be NULL; waits for the result. */
+int stitch_ransac(const float *src_x, const float *src_y, const float *dst_x, const float *dst_y, int n, int mirror,
+                  const stitch_ransac_opts *opts, double p[8], int32_t *inliers, int32_t info[STITCH_RANSAC_INFO]);
+/* Verification hook, host only: the first n values of rand() after srand(seed) as the kernels generate them. */
+void stitch_ransac_rand(uint32_t seed, int32_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif
