@@ -98,6 +98,14 @@ def lib():
         L.stitch_ransac.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
         L.stitch_ransac_rand.restype = None
         L.stitch_ransac_rand.argtypes = [C.c_uint32, vp, i32]
+        L.stitch_dev_sift_many.argtypes = [vp, i32, vp, vp]
+        L.stitch_sift.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp]
+        L.stitch_sift_filter.argtypes = [C.c_double, vp]
+        L.stitch_sift_expn_table.restype = None
+        L.stitch_sift_expn_table.argtypes = [vp]
+        L.stitch_sift_elem.restype = None
+        L.stitch_sift_elem.argtypes = [C.c_double, vp]
+        L.stitch_dev_project_gray_u8.argtypes = [vp, i32, i32, C.c_float, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -531,6 +539,88 @@ def dev_ransac_many(lists, opts=None, want_inliers=True):
     return p, info, (inl if want_inliers else None)
 
 
+# ---- SIFT: ImageProcess::siftAlgorithm (ImageProcess.cpp:44-99) over vl/sift.c --------------------------------------------
+SIFT_OK, SIFT_OVERFLOW, SIFT_STATUS = 0, 1, 4
+SIFT_KP_DTYPE = np.dtype([("o", "<i4"), ("ix", "<i4"), ("iy", "<i4"), ("is", "<i4"), ("x", "<f4"), ("y", "<f4"), ("s", "<f4"),
+                          ("sigma", "<f4")])  # StitchSiftKeypoint = VlSiftKeypoint after vl_sift_detect
+
+
+class SiftOpts(C.Structure):
+    """StitchSiftOpts; the defaults are the reference's values (octaves < 0: VLFeat's automatic rule)."""
+    _fields_ = [("octaves", C.c_int32), ("levels", C.c_int32), ("first_octave", C.c_int32), ("peak_thresh", C.c_double),
+                ("edge_thresh", C.c_double), ("norm_thresh", C.c_double), ("magnif", C.c_double), ("window_size", C.c_double)]
+
+    def __init__(self, octaves=4, levels=2, first_octave=0, peak_thresh=0.0, edge_thresh=10.0, norm_thresh=0.0, magnif=3.0,
+                 window_size=2.0):
+        super().__init__(int(octaves), int(levels), int(first_octave), float(peak_thresh), float(edge_thresh), float(norm_thresh),
+                         float(magnif), float(window_size))
+
+
+class SiftDesc(C.Structure):
+    """stitch_sift_desc: one frame of a batched extraction (device pointers)."""
+    _fields_ = [("image", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("is_f32", C.c_int32),
+                ("keypoints", C.c_void_p), ("kp_cap", C.c_int32), ("feat_cap", C.c_int32), ("feat_kp", C.c_void_p),
+                ("feat_angle", C.c_void_p), ("feat_desc", C.c_void_p), ("counts", C.c_void_p), ("status", C.c_void_p)]
+
+
+def sift(gray, opts=None, kp_cap=8192, feat_cap=None):
+    """siftAlgorithm's VLFeat sequence on one (H, W) uint8 gray image given as a host array.  Returns a dict: kp (SIFT_KP_DTYPE
+    records in detection order), fkp (keypoint index per feature row), angle (float64), desc ((n, 128) float32, the reference's
+    insertion order), status ([status, keypoints found, rows found, octaves run]).  status[0] == SIFT_OVERFLOW: the capacities
+    were too small, status[1:3] say what is needed."""
+    g = np.ascontiguousarray(gray, dtype=np.uint8)
+    if g.ndim != 2:
+        raise ValueError("expected an (H, W) gray image")
+    feat_cap = 2 * kp_cap if feat_cap is None else feat_cap
+    kp = np.zeros(max(kp_cap, 1), SIFT_KP_DTYPE)
+    fkp, ang = np.zeros(max(feat_cap, 1), np.int32), np.zeros(max(feat_cap, 1), np.float64)
+    desc = np.zeros((max(feat_cap, 1), DESCRIPTOR_DIM), np.float32)
+    counts, status = np.zeros(2, np.int32), np.zeros(SIFT_STATUS, np.int32)
+    o = opts if opts is not None else SiftOpts()
+    _chk(lib().stitch_sift(_p(g), g.shape[1], g.shape[0], C.byref(o), _p(kp), int(kp_cap), _p(fkp), _p(ang), _p(desc), int(feat_cap),
+                           _p(counts), _p(status)))
+    nk, nf = int(counts[0]), int(counts[1])
+    return dict(kp=kp[:nk].copy(), fkp=fkp[:nf].copy(), angle=ang[:nf].copy(), desc=desc[:nf].copy(), status=status)
+
+
+def dev_sift_many(images, opts=None, kp_cap=8192, feat_cap=None):
+    """Many gray frames -- (H, W) uint8 or float32 device tensors with contiguous rows, sizes may differ -- in one launch sequence
+    per 16 frames and octave on torch's current stream (no synchronisation).  Returns a list of dicts of device tensors: kp
+    ((kp_cap, 8) int32: the StitchSiftKeypoint records, columns 4..7 are float32 bits), fkp, angle, desc, counts ((2,) int32) and
+    status ((4,) int32); sift_unpack turns one into host arrays."""
+    import torch
+    n = len(images)
+    feat_cap = 2 * kp_cap if feat_cap is None else feat_cap
+    outs, descs = [], []
+    for t in images:
+        if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.dtype in (torch.uint8, torch.float32)):
+            raise ValueError("expected (H, W) uint8 or float32 device tensors with contiguous rows")
+        dev = t.device
+        o = dict(kp=torch.empty((max(kp_cap, 1), 8), dtype=torch.int32, device=dev),
+                 fkp=torch.empty(max(feat_cap, 1), dtype=torch.int32, device=dev),
+                 angle=torch.empty(max(feat_cap, 1), dtype=torch.float64, device=dev),
+                 desc=torch.empty((max(feat_cap, 1), DESCRIPTOR_DIM), dtype=torch.float32, device=dev),
+                 head=torch.empty(2 + SIFT_STATUS, dtype=torch.int32, device=dev))
+        o["counts"], o["status"] = o["head"][:2], o["head"][2:]
+        outs.append(o)
+        descs.append(SiftDesc(_dp(t), t.shape[1], t.shape[0], t.stride(0) * t.element_size(), int(t.dtype == torch.float32),
+                              _dp(o["kp"]), int(kp_cap), int(feat_cap), _dp(o["fkp"]), _dp(o["angle"]), _dp(o["desc"]),
+                              _dp(o["head"]), C.c_void_p(o["head"].data_ptr() + 8)))
+    arr = (SiftDesc * max(n, 1))(*descs)
+    op = opts if opts is not None else SiftOpts()
+    _chk(lib().stitch_dev_sift_many(arr, n, C.byref(op), _stream()))
+    return outs
+
+
+def sift_unpack(out):
+    """One entry of dev_sift_many as host arrays (this waits for the stream): the dict capi.sift returns."""
+    head = out["head"].cpu().numpy()
+    nk, nf = int(head[0]), int(head[1])
+    kp = out["kp"][:nk].cpu().numpy().view(SIFT_KP_DTYPE).reshape(-1)
+    return dict(kp=kp, fkp=out["fkp"][:nf].cpu().numpy(), angle=out["angle"][:nf].cpu().numpy(), desc=out["desc"][:nf].cpu().numpy(),
+                status=head[2:].copy())
+
+
 # ---- device-resident entry points (torch tensors on the HIP device) --------------------------------------------
 def _tsfx(t):
     import torch
@@ -563,6 +653,20 @@ def dev_project(src, fov_deg=15.0, out=None):
     _, h, w = src.shape
     _chk(getattr(lib(), "stitch_dev_project_" + _tsfx(src))(_dp(src), w, h, C.c_float(fov_deg), _dp(out), _stream()))
     return out
+
+
+def dev_project_gray(src, fov_deg=15.0):
+    """readFile's per-image chain on the device (ImageProcess.cpp:18-20) -> (projected (3,H,W), gray (H,W) uint8, gray float32)."""
+    import torch
+    src = _timg(src)
+    if src.dtype != torch.uint8:
+        raise TypeError("expected a uint8 frame")
+    _, h, w = src.shape
+    out = torch.empty_like(src)
+    g = torch.empty((h, w), dtype=torch.uint8, device=src.device)
+    f = torch.empty((h, w), dtype=torch.float32, device=src.device)
+    _chk(lib().stitch_dev_project_gray_u8(_dp(src), w, h, C.c_float(fov_deg), _dp(out), _dp(g), _dp(f), _stream()))
+    return out, g, f
 
 
 def dev_warp(src, p, offx, offy, canvas):

@@ -2531,3 +2531,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_band.inc"
 #include "stitch_match.inc"
 #include "stitch_ransac.inc"
+#include "stitch_sift.inc"

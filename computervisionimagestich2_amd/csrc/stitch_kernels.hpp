@@ -94,5 +94,6 @@ __device__ __forceinline__ void bilinear3(const PX* __restrict__ src, int w, int
 #include "k_synth.inc"  // synthetic frames and small utility kernels
 #include "k_match.inc"  // exact L1 two-nearest-neighbour descriptor matching with the ratio test (getImgPair)
 #include "k_ransac.inc"  // RANSAC over matched keypoints: glibc rand() walk, 4-point LU fits, consensus count, SVD least squares
+#include "k_sift.inc"    // SIFT extraction: scale space, DoG extrema, refinement, gradients, orientations, descriptors
 
 }  // namespace sk

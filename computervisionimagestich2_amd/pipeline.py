@@ -830,3 +830,38 @@ def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, d
         result = result.clone() if return_steps and steps else result
         capi.dev_finish(result, num, den)
     return (result, steps) if return_steps else result
+
+
+# ---- SIFT on the device: ImageProcess::ImageProcess (ImageProcess.cpp:12-25) and siftAlgorithm (:44-99) ----------------------
+def sift_features(frames, opts=None, kp_cap=4096, feat_cap=None):
+    """Projection -> gray -> SIFT for a list of (3, H, W) uint8 device tensors (unprojected), all frames in one launch sequence,
+    then ONE read-back (counts, status, feature rows and their keypoints' x / y of every frame, packed) for the std::map's order
+    (feature_order; the lexicographic order stays on the host).  Returns the list of (descriptors (n, 128), keypoints (n, 2)
+    x/y) in map order that panorama_from_features takes."""
+    import torch
+    grays = [capi.dev_project_gray(f)[1] for f in frames]
+    outs = capi.dev_sift_many(grays, opts, kp_cap, feat_cap)
+    packed = []
+    for o in outs:
+        xy = o["kp"][:, 4:6].contiguous().view(torch.float32)[o["fkp"].long().clamp_(0, o["kp"].shape[0] - 1)]  # rows past the count are unused
+        packed += [o["head"].view(torch.float32), o["desc"].reshape(-1), xy.reshape(-1)]
+    host = torch.cat(packed).cpu().numpy() if packed else None  # waits for the stream
+    feats, pos = [], 0
+    for i, o in enumerate(outs):
+        cap = o["desc"].shape[0]
+        head = host[pos:pos + 6].view("int32")
+        desc = host[pos + 6:pos + 6 + cap * capi.DESCRIPTOR_DIM].reshape(cap, capi.DESCRIPTOR_DIM)
+        xy = host[pos + 6 + cap * capi.DESCRIPTOR_DIM:pos + 6 + cap * (capi.DESCRIPTOR_DIM + 2)].reshape(cap, 2)
+        pos += 6 + cap * (capi.DESCRIPTOR_DIM + 2)
+        if head[2] != capi.SIFT_OK:
+            raise capi.StitchError(-1, f"frame {i}: SIFT capacities too small ({int(head[3])} keypoints, {int(head[4])} features found)")
+        d, k, _ = feature_order(desc[:head[1]], xy[:head[1]])
+        feats.append((d, k))
+    return feats
+
+
+def panorama_from_frames(frames, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, sift_opts=None, kp_cap=4096,
+                         feat_cap=None):
+    """The whole of ImageProcess::ImageProcess plus matching() from decoded frames alone: sift_features (kp_cap / feat_cap are
+    its per-frame capacities; a frame that needs more raises StitchError with the counts found), then panorama_from_features."""
+    return panorama_from_features(frames, sift_features(frames, sift_opts, kp_cap, feat_cap), opts, finish, num, den, return_steps)

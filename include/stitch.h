@@ -580,6 +580,69 @@ int stitch_ransac(const float *src_x, const float *src_y, const float *dst_x, co
 /* Verification hook, host only: the first n values of rand() after srand(seed) as the kernels generate them. */
 void stitch_ransac_rand(uint32_t seed, int32_t *out, int n);
 
+/* ---- SIFT: ImageProcess::siftAlgorithm (ImageProcess.cpp:44-99) over VLFeat's vl/sift.c --------------------------------------
+ * From a gray image the reference runs vl_sift_new(w, h, 4, 2, 0), then per octave vl_sift_detect, per keypoint
+ * vl_sift_calc_keypoint_orientations and per angle vl_sift_calc_keypoint_descriptor, and inserts (descriptor, keypoint) into a
+ * std::map.  These calls give the same keypoints, angles and descriptors bit for bit, in the reference's insertion order
+ * (octave, keypoint in detection order = scan order (s, y, x), angle in bin order); the map's order stays with the caller.
+ *   - scale space: _vl_sift_smooth (sift.c:115-159) with vl_imconvcol_vf's serial float chain (imopv.c:150-186),
+ *     copy_and_downsample (:178-194), the sigma schedule of :390-406 and :465-481;
+ *   - vl_sift_detect (:497-776): DoG, 26 neighbours, the 3 x 3 refinement in double, the 12-term test;
+ *   - update_gradient (:791-876), orientations (:903-1037), descriptor (:1267-1438) with VLFeat's inline approximations;
+ *   - exp (filter taps, fast_expn's table), pow(2, sn/S), sin and cos are the specified functions of stitch_sift_elem.h, not
+ *     the host's libm.
+ * A descriptor the reference leaves unwritten (vl_sift_calc_keypoint_descriptor returns early for a keypoint on the last row,
+ * :1321-1328, and siftAlgorithm inserts its uninitialised buffer) is 128 zeros here. */
+typedef struct StitchSiftOpts { /* NULL: the reference's values */
+    int32_t octaves;      /* 4 (NOTAVES_NUM); negative: VLFeat's rule max(floor(log2(min(w, h))) - 3, 1) per frame            */
+    int32_t levels;       /* 2 (LEVEL_NUM); 1 .. 5                                                                          */
+    int32_t first_octave; /* 0; anything else is STITCH_ERR_ARG (no upsampling / pre-decimation branch)                     */
+    double peak_thresh;   /* 0                                                                                              */
+    double edge_thresh;   /* 10                                                                                             */
+    double norm_thresh;   /* 0                                                                                              */
+    double magnif;        /* 3                                                                                              */
+    double window_size;   /* 2 (NBP / 2)                                                                                    */
+} StitchSiftOpts;
+#define STITCH_SIFT_OPTS_DEFAULT {4, 2, 0, 0.0, 10.0, 0.0, 3.0, 2.0}
+typedef struct StitchSiftKeypoint { /* VlSiftKeypoint after vl_sift_detect (vl/sift.h:19-31) */
+    int32_t o, ix, iy, is;
+    float x, y, s, sigma;
+} StitchSiftKeypoint;
+#define STITCH_SIFT_OK 0
+#define STITCH_SIFT_OVERFLOW 1
+#define STITCH_SIFT_STATUS 4
+/* One frame of a batched extraction; every pointer is a device pointer. */
+typedef struct stitch_sift_desc {
+    const void *image;             /* gray, uint8 or float32 (values as the reference's (float) of the gray byte)            */
+    int32_t width, height, pitch;  /* pitch in bytes                                                                         */
+    int32_t is_f32;
+    StitchSiftKeypoint *keypoints; /* out: kp_cap records                                                                    */
+    int32_t kp_cap;
+    int32_t feat_cap;
+    int32_t *feat_kp;              /* out, feat_cap each: index into keypoints, the angle, 128 floats                        */
+    double *feat_angle;
+    float *feat_desc;
+    int32_t *counts;               /* out: {keypoints written, feature rows written}                                         */
+    int32_t *status;               /* out, STITCH_SIFT_STATUS: {STITCH_SIFT_OK / _OVERFLOW, keypoints found, feature rows
+                                    * found, octaves run}.  On overflow the first kp_cap keypoints and feat_cap rows are written,
+                                    * nothing is truncated silently, and the other frames of the call are complete.  Feature rows
+                                    * are counted over the keypoints that were written: when the keypoints overflow, call again
+                                    * with kp_cap >= status[1] to learn the number of rows.                                   */
+} stitch_sift_desc;
+/* Many frames, which may differ in size, in one launch sequence per 16 frames and octave; enqueued on `stream` with
+ * stream-ordered scratch, no host synchronisation.  A frame too small for the octaves asked for runs down to 1 x 1 octaves
+ * and finds nothing there, as the reference does. */
+int stitch_dev_sift_many(const stitch_sift_desc *frames, int n, const StitchSiftOpts *opts, void *stream);
+/* One frame on HOST buffers (uint8 gray, rows of `width` bytes); waits for the result. */
+int stitch_sift(const uint8_t *gray, int width, int height, const StitchSiftOpts *opts, StitchSiftKeypoint *keypoints, int kp_cap,
+                int32_t *feat_kp, double *feat_angle, float *feat_desc, int feat_cap, int32_t counts[2],
+                int32_t status[STITCH_SIFT_STATUS]);
+/* Verification hooks, host only: the filter of _vl_sift_smooth for `sigma` (returns its half-width W; taps holds 2 W + 1,
+ * at most 129; -1 when wider), fast_expn's 257-entry table, and the three elementary functions. */
+int stitch_sift_filter(double sigma, float *taps);
+void stitch_sift_expn_table(double *tab257);
+void stitch_sift_elem(double x, double out[4]); /* {exp(x), 2^x, sin x, cos x} */
+
 #ifdef __cplusplus
 }
 #endif
