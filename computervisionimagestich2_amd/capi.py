@@ -8,6 +8,7 @@ There is no fallback: a missing library or a missing GPU raises.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -59,6 +60,65 @@ class PairDesc(C.Structure):
                 ("out", C.c_void_p), ("out_u8", C.c_void_p)]
 
 
+def _signatures(*rows):
+    """Rows of (names, restype, *argtypes) -> {name: (restype, argtypes)}; `stem_*` stands for the twins stem_u8 and stem_f32."""
+    return {n: (res, list(args)) for names, res, *args in rows for n in re.sub(r"(\S+)\*", r"\1u8 \1f32", names).split()}
+
+
+# The signature of every function include/stitch.h declares; tests/test_capi_abi.py holds this table to the header.  Every pointer,
+# array and stream parameter is a c_void_p: it takes None, a plain int, byref(...), a ctypes array or structure array, or a c_void_p.
+vp, i32, f32, f64, sz, u32 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32
+SIGNATURES = _signatures(
+    ("stitch_abi_version stitch_init stitch_device_count", i32), ("stitch_last_error", C.c_char_p), ("stitch_trim", None),
+    ("stitch_set_device", i32, i32), ("stitch_blend_opts_default", None, vp),
+    ("stitch_plan_cache_query", i32, i32, i32, vp, vp), ("stitch_pyramid_levels", i32, i32, i32, i32, vp, vp),
+    # the per-pixel path: on host buffers, and the device twin with its stream behind
+    ("stitch_project_*", i32, vp, i32, i32, f32, vp), ("stitch_dev_project_*", i32, vp, i32, i32, f32, vp, vp),
+    ("stitch_warp_*", i32, vp, i32, i32, vp, f32, f32, vp, i32, i32), ("stitch_dev_warp_*", i32, vp, i32, i32, vp, f32, f32, vp, i32, i32, vp),
+    ("stitch_move_*", i32, vp, i32, i32, i32, i32, vp, i32, i32), ("stitch_dev_move_*", i32, vp, i32, i32, i32, i32, vp, i32, i32, vp),
+    ("stitch_blend_*", i32, vp, vp, i32, i32, vp, vp, vp), ("stitch_dev_blend_*", i32, vp, vp, vp, vp, vp),
+    ("stitch_pair_*", i32, vp, i32, i32, vp, f32, f32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
+    ("stitch_dev_pair_*", i32, vp, vp, i32, i32, vp, f32, f32, vp, i32, i32, i32, i32, vp, vp), ("stitch_dev_pairs_*", i32, vp, vp, i32, vp),
+    ("stitch_equalize_u8", i32, vp, i32, i32, vp), ("stitch_dev_equalize_u8", i32, vp, i32, i32, vp, vp),
+    ("stitch_lummix_u8", i32, vp, vp, i32, i32, f64, f64), ("stitch_dev_lummix_u8", i32, vp, vp, i32, i32, f64, f64, vp),
+    ("stitch_finish_u8", i32, vp, i32, i32, f64, f64, vp), ("stitch_dev_finish_u8", i32, vp, i32, i32, f64, f64, vp, vp),
+    # plans
+    ("stitch_plan_create", i32, i32, i32, vp, vp), ("stitch_plan_create_batched", i32, i32, i32, vp, i32, vp),
+    ("stitch_plan_destroy", None, vp), ("stitch_plan_workspace_bytes", sz, vp), ("stitch_plan_workspace_base", vp, vp),
+    ("stitch_plan_capacity stitch_plan_fused_sweep_levels stitch_plan_fast_paths stitch_plan_coarse_from stitch_plan_clear_fault", i32, vp),
+    ("stitch_plan_call_forms stitch_plan_set_profiling stitch_plan_set_profiling_kernel", i32, vp, i32),
+    ("stitch_plan_levels", i32, vp, vp, vp), ("stitch_plan_collapse_range", i32, vp, i32, vp, vp, vp), ("stitch_plan_status", i32, vp, vp),
+    ("stitch_plan_status_at", i32, vp, i32, vp), ("stitch_plan_set_handoff_spin_limit", i32, vp, C.c_uint),
+    ("stitch_plan_read_profile", i32, vp, vp, vp, vp),
+    # the callers either side of the path
+    ("stitch_gray_u8", i32, vp, i32, i32, vp, vp), ("stitch_dev_gray_u8", i32, vp, i32, i32, vp, vp, vp),
+    ("stitch_bmp_parse", i32, vp, sz, vp), ("stitch_bmp_file_bytes", sz, i32, i32),
+    ("stitch_bmp_decode_u8", i32, vp, sz, vp), ("stitch_dev_bmp_decode_u8", i32, vp, sz, vp, vp, vp),
+    ("stitch_bmp_encode_u8", i32, vp, i32, i32, vp, sz), ("stitch_dev_bmp_encode_u8", i32, vp, i32, i32, vp, sz, vp),
+    ("stitch_transfer_u8", i32, vp, i32, i32, vp, i32, i32, vp, vp), ("stitch_dev_transfer_u8", i32, vp, i32, i32, vp, i32, i32, vp, vp, vp),
+    ("stitch_project_gray_u8", i32, vp, i32, i32, f32, vp, vp, vp), ("stitch_dev_project_gray_u8", i32, vp, i32, i32, f32, vp, vp, vp, vp),
+    ("stitch_canvas_bbox", i32, i32, i32, vp, i32, i32, vp, vp, vp, vp), ("stitch_step_geometry", i32, i32, i32, vp, i32, i32, vp),
+    ("stitch_dev_step_*", i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, vp),
+    ("stitch_map_points", i32, vp, vp, vp, vp, i32, vp, f32, f32), ("stitch_shift_points", i32, vp, vp, vp, vp, i32, i32, i32),
+    # one pair split into row bands
+    ("stitch_band_create", i32, i32, i32, i32, i32, i32, vp, vp), ("stitch_band_destroy", None, vp),
+    ("stitch_band_geometry", i32, vp, i32, vp), ("stitch_band_set_level0", i32, vp, i32), ("stitch_band_levels stitch_band_status", i32, vp, vp),
+    ("stitch_band_compose_*", i32, vp, vp, i32, i32, vp, f32, f32, vp, i32, i32, i32, i32, vp), ("stitch_band_reduce_x", i32, vp, i32, vp),
+    ("stitch_band_reduce_xy_fwd", i32, vp, i32, vp, vp, vp), ("stitch_band_reduce_y_fwd", i32, vp, i32, i32, vp, vp, vp),
+    ("stitch_band_reduce_y_bwd", i32, vp, i32, i32, vp, vp, vp, vp), ("stitch_band_reduce_y_fwd_cols", i32, vp, i32, i32, i32, vp, vp, vp),
+    ("stitch_band_reduce_y_bwd_cols", i32, vp, i32, i32, i32, vp, vp, vp, vp), ("stitch_band_rows", i32, vp, i32, i32, i32, i32, vp, i32, vp),
+    ("stitch_band_top", i32, vp, vp, vp), ("stitch_band_collapse_*", i32, vp, i32, vp, vp),
+    # benchmark frames, quantisation, verification hooks
+    ("stitch_dev_synth_*", i32, vp, i32, i32, i32, vp), ("stitch_dev_quantize_u8", i32, vp, vp, sz, vp),
+    ("stitch_dev_check_fastdiv", i32, f32, vp, vp), ("stitch_dev_check_collapse_taps", i32, i32, i32, i32, vp, vp),
+    # features: matching, RANSAC, SIFT
+    ("stitch_match_l1_ratio", i32, vp, i32, vp, i32, f64, vp, vp, vp, vp), ("stitch_dev_match_l1_ratio_many", i32, vp, i32, f64, vp),
+    ("stitch_dev_match_l1_ratio", i32, vp, i32, vp, i32, f64, vp, vp, vp, vp, vp), ("stitch_ransac_rand", None, u32, vp, i32),
+    ("stitch_ransac", i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp), ("stitch_dev_ransac_many stitch_dev_sift_many", i32, vp, i32, vp, vp),
+    ("stitch_sift", i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp), ("stitch_sift_filter", i32, f64, vp),
+    ("stitch_sift_expn_table", None, vp), ("stitch_sift_elem", None, f64, vp),
+)
+
 _lib = None
 
 
@@ -77,35 +137,12 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        L.stitch_last_error.restype = C.c_char_p
-        L.stitch_plan_workspace_bytes.restype = C.c_size_t
-        L.stitch_plan_workspace_bytes.argtypes = [C.c_void_p]
-        L.stitch_plan_collapse_range.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.stitch_plan_workspace_base.restype = C.c_void_p
-        L.stitch_plan_workspace_base.argtypes = [C.c_void_p]
-        L.stitch_plan_fast_paths.argtypes = [C.c_void_p]
-        L.stitch_plan_call_forms.argtypes = [C.c_void_p, C.c_int]
-        L.stitch_plan_coarse_from.argtypes = [C.c_void_p]
-        L.stitch_plan_destroy.restype = None
-        L.stitch_plan_destroy.argtypes = [C.c_void_p]
-        L.stitch_blend_opts_default.restype = None
-        L.stitch_bmp_file_bytes.restype = C.c_size_t
-        vp, i32 = C.c_void_p, C.c_int
-        L.stitch_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
-        L.stitch_dev_match_l1_ratio.argtypes = [vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp]
-        L.stitch_dev_match_l1_ratio_many.argtypes = [vp, i32, C.c_double, vp]
-        L.stitch_dev_ransac_many.argtypes = [vp, i32, vp, vp]
-        L.stitch_ransac.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-        L.stitch_ransac_rand.restype = None
-        L.stitch_ransac_rand.argtypes = [C.c_uint32, vp, i32]
-        L.stitch_dev_sift_many.argtypes = [vp, i32, vp, vp]
-        L.stitch_sift.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp]
-        L.stitch_sift_filter.argtypes = [C.c_double, vp]
-        L.stitch_sift_expn_table.restype = None
-        L.stitch_sift_expn_table.argtypes = [vp]
-        L.stitch_sift_elem.restype = None
-        L.stitch_sift_elem.argtypes = [C.c_double, vp]
-        L.stitch_dev_project_gray_u8.argtypes = [vp, i32, i32, C.c_float, vp, vp, vp, vp]
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                f = getattr(L, name)
+            except AttributeError:
+                raise ImportError(f"{LIB_PATH} does not export {name}: it was built from another include/stitch.h") from None
+            f.restype, f.argtypes = res, args
         _lib = L
     return _lib
 
@@ -120,12 +157,12 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _sfx(dtype):
-    if dtype == np.uint8:
-        return "u8"
-    if dtype == np.float32:
-        return "f32"
-    raise TypeError(f"unsupported pixel type {dtype}")
+def _fn(stem, a):
+    """The _u8 / _f32 twin of the entry points `stem` for the pixel type of `a`, a numpy array or a torch tensor."""
+    sfx = {"uint8": "u8", "float32": "f32"}.get(str(a.dtype).rpartition(".")[2])  # "uint8" / "torch.uint8"
+    if sfx is None:
+        raise TypeError(f"unsupported pixel type {a.dtype}")
+    return getattr(lib(), stem + sfx)
 
 
 def _img(a):
@@ -178,7 +215,7 @@ def project(src, fov_deg=15.0):
     src = _img(src)
     dst = np.empty_like(src)
     _, h, w = src.shape
-    _chk(getattr(lib(), "stitch_project_" + _sfx(src.dtype))(_p(src), w, h, C.c_float(fov_deg), _p(dst)))
+    _chk(_fn("stitch_project_", src)(_p(src), w, h, fov_deg, _p(dst)))
     return dst
 
 
@@ -186,8 +223,7 @@ def warp(src, p, offx, offy, canvas):
     """ImageProcess::warpingImageByHomography (ImageProcess.cpp:596-606); writes into `canvas` in place."""
     src = _img(src)
     assert canvas.flags.c_contiguous and canvas.dtype == src.dtype and canvas.shape[0] == 3
-    _chk(getattr(lib(), "stitch_warp_" + _sfx(src.dtype))(_p(src), src.shape[2], src.shape[1], _map8(p), C.c_float(offx),
-                                                          C.c_float(offy), _p(canvas), canvas.shape[2], canvas.shape[1]))
+    _chk(_fn("stitch_warp_", src)(_p(src), src.shape[2], src.shape[1], _map8(p), offx, offy, _p(canvas), canvas.shape[2], canvas.shape[1]))
     return canvas
 
 
@@ -195,8 +231,7 @@ def move(src, ox, oy, canvas):
     """ImageProcess::movingImageByOffset (ImageProcess.cpp:608-620); writes into `canvas` in place."""
     src = _img(src)
     assert canvas.flags.c_contiguous and canvas.dtype == src.dtype and canvas.shape[0] == 3
-    _chk(getattr(lib(), "stitch_move_" + _sfx(src.dtype))(_p(src), src.shape[2], src.shape[1], int(ox), int(oy), _p(canvas),
-                                                          canvas.shape[2], canvas.shape[1]))
+    _chk(_fn("stitch_move_", src)(_p(src), src.shape[2], src.shape[1], int(ox), int(oy), _p(canvas), canvas.shape[2], canvas.shape[1]))
     return canvas
 
 
@@ -204,10 +239,8 @@ def blend(a, b, opts=None):
     """ImageProcess::blendTwoImages (ImageProcess.cpp:648-773) -> (out, Seam)."""
     a, b = _img(a), _img(b)
     assert a.shape == b.shape and a.dtype == b.dtype
-    out = np.empty_like(a)
-    s = Seam()
-    o = _opts(opts)
-    _chk(getattr(lib(), "stitch_blend_" + _sfx(a.dtype))(_p(a), _p(b), a.shape[2], a.shape[1], C.byref(o), _p(out), C.byref(s)))
+    out, s = np.empty_like(a), Seam()
+    _chk(_fn("stitch_blend_", a)(_p(a), _p(b), a.shape[2], a.shape[1], C.byref(_opts(opts)), _p(out), C.byref(s)))
     return out, s
 
 
@@ -215,12 +248,9 @@ def pair(frame, p, offx, offy, mosaic, ox, oy, cw, ch, opts=None):
     """One stitch step (ImageProcess.cpp:218-230): warp `frame`, move `mosaic`, blend -> (out, Seam)."""
     frame, mosaic = _img(frame), _img(mosaic)
     assert frame.dtype == mosaic.dtype
-    out = np.empty((3, ch, cw), frame.dtype)
-    s = Seam()
-    o = _opts(opts)
-    _chk(getattr(lib(), "stitch_pair_" + _sfx(frame.dtype))(
-        _p(frame), frame.shape[2], frame.shape[1], _map8(p), C.c_float(offx), C.c_float(offy), _p(mosaic), mosaic.shape[2],
-        mosaic.shape[1], int(ox), int(oy), int(cw), int(ch), C.byref(o), _p(out), C.byref(s)))
+    out, s = np.empty((3, ch, cw), frame.dtype), Seam()
+    _chk(_fn("stitch_pair_", frame)(_p(frame), frame.shape[2], frame.shape[1], _map8(p), offx, offy, _p(mosaic), mosaic.shape[2],
+                                    mosaic.shape[1], int(ox), int(oy), int(cw), int(ch), C.byref(_opts(opts)), _p(out), C.byref(s)))
     return out, s
 
 
@@ -236,7 +266,7 @@ def lummix(result, equalized, num=19.0, den=20.0):
     """Luminance mix of ImageProcess::matching (ImageProcess.cpp:240-268) -> new array."""
     result = np.array(_img(result), dtype=np.uint8, copy=True)
     equalized = np.ascontiguousarray(equalized, np.uint8)
-    _chk(lib().stitch_lummix_u8(_p(result), _p(equalized), result.shape[2], result.shape[1], C.c_double(num), C.c_double(den)))
+    _chk(lib().stitch_lummix_u8(_p(result), _p(equalized), result.shape[2], result.shape[1], num, den))
     return result
 
 
@@ -244,7 +274,7 @@ def finish(result, num=19.0, den=20.0):
     """Tail of matching() in one call (ImageProcess.cpp:237-268): equalise a copy, mix -> (new array, Y bins)."""
     result = np.array(_img(result), dtype=np.uint8, copy=True)
     hist = np.zeros(256, np.int32)
-    _chk(lib().stitch_finish_u8(_p(result), result.shape[2], result.shape[1], C.c_double(num), C.c_double(den), _p(hist)))
+    _chk(lib().stitch_finish_u8(_p(result), result.shape[2], result.shape[1], num, den, _p(hist)))
     return result, hist
 
 
@@ -262,7 +292,7 @@ def project_gray(src, fov_deg=15.0):
     src = np.ascontiguousarray(_img(src), np.uint8)
     _, h, w = src.shape
     dst, g, f = np.empty_like(src), np.empty((h, w), np.uint8), np.empty((h, w), np.float32)
-    _chk(lib().stitch_project_gray_u8(_p(src), w, h, C.c_float(fov_deg), _p(dst), _p(g), _p(f)))
+    _chk(lib().stitch_project_gray_u8(_p(src), w, h, fov_deg, _p(dst), _p(g), _p(f)))
     return dst, g, f
 
 
@@ -281,8 +311,8 @@ def dev_transfer(d_src, d_tem, out=None, stats=None):
     for t in (d_src, d_tem):
         assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape[0] == 3
     out = torch.empty_like(d_src) if out is None else out
-    _chk(lib().stitch_dev_transfer_u8(_dp(d_src), int(d_src.shape[2]), int(d_src.shape[1]), _dp(d_tem), int(d_tem.shape[2]),
-                                      int(d_tem.shape[1]), _dp(out), _dp(stats) if stats is not None else None, _stream()))
+    _chk(lib().stitch_dev_transfer_u8(_dp(d_src), d_src.shape[2], d_src.shape[1], _dp(d_tem), d_tem.shape[2], d_tem.shape[1], _dp(out),
+                                      _dp(stats), _stream()))
     return out
 
 
@@ -296,7 +326,7 @@ def bmp_parse(header, file_bytes):
     """Header arithmetic of CImg's load_bmp on the first 54 bytes of a file of `file_bytes` bytes.  Host only."""
     h = np.frombuffer(bytes(header[:54]), np.uint8)
     bi = BmpInfo()
-    _chk(lib().stitch_bmp_parse(_p(h), C.c_size_t(int(file_bytes) if h.size >= 54 else h.size), C.byref(bi)))
+    _chk(lib().stitch_bmp_parse(_p(h), int(file_bytes) if h.size >= 54 else h.size, C.byref(bi)))
     return bi
 
 
@@ -305,7 +335,7 @@ def bmp_decode(data):
     buf = np.frombuffer(bytes(data), np.uint8)
     bi = bmp_parse(buf[:54].tobytes(), buf.size)
     out = np.empty((3, bi.height, bi.width), np.uint8)
-    _chk(lib().stitch_bmp_decode_u8(_p(buf), C.c_size_t(buf.size), _p(out)))
+    _chk(lib().stitch_bmp_decode_u8(_p(buf), buf.size, _p(out)))
     return out
 
 
@@ -315,7 +345,7 @@ def bmp_encode(img):
     _, h, w = img.shape
     n = lib().stitch_bmp_file_bytes(w, h)
     out = np.empty(n, np.uint8)
-    _chk(lib().stitch_bmp_encode_u8(_p(img), w, h, _p(out), C.c_size_t(n)))
+    _chk(lib().stitch_bmp_encode_u8(_p(img), w, h, _p(out), n))
     return out.tobytes()
 
 
@@ -324,7 +354,7 @@ def dev_bmp_decode(d_file, info, out=None):
     import torch
     assert d_file.is_cuda and d_file.dtype == torch.uint8 and d_file.is_contiguous()
     out = torch.empty((3, info.height, info.width), dtype=torch.uint8, device=d_file.device) if out is None else out
-    _chk(lib().stitch_dev_bmp_decode_u8(_dp(d_file), C.c_size_t(d_file.numel()), C.byref(info), _dp(out), _stream()))
+    _chk(lib().stitch_dev_bmp_decode_u8(_dp(d_file), d_file.numel(), C.byref(info), _dp(out), _stream()))
     return out
 
 
@@ -335,7 +365,7 @@ def dev_bmp_encode(d_img, out=None):
     _, h, w = d_img.shape
     n = lib().stitch_bmp_file_bytes(int(w), int(h))
     out = torch.empty(n, dtype=torch.uint8, device=d_img.device) if out is None else out
-    _chk(lib().stitch_dev_bmp_encode_u8(_dp(d_img), int(w), int(h), _dp(out), C.c_size_t(out.numel()), _stream()))
+    _chk(lib().stitch_dev_bmp_encode_u8(_dp(d_img), int(w), int(h), _dp(out), out.numel(), _stream()))
     return out
 
 
@@ -365,10 +395,9 @@ def dev_step(frame, p_fwd, p_bwd, mosaic, opts=None):
     frame, mosaic = _timg(frame), _timg(mosaic)
     g = step_geometry(frame.shape[2], frame.shape[1], p_fwd, mosaic.shape[2], mosaic.shape[1])
     out = torch.empty((3, g.ch, g.cw), dtype=frame.dtype, device=frame.device)
-    g2, s, o = StepGeom(), Seam(), _opts(opts)
-    _chk(getattr(lib(), "stitch_dev_step_" + _tsfx(frame))(
-        _dp(frame), frame.shape[2], frame.shape[1], _map8(p_fwd), _map8(p_bwd), _dp(mosaic), mosaic.shape[2], mosaic.shape[1], C.byref(o),
-        _dp(out), C.c_size_t(out.numel()), C.byref(g2), C.byref(s), _stream()))
+    g2, s = StepGeom(), Seam()
+    _chk(_fn("stitch_dev_step_", frame)(_dp(frame), frame.shape[2], frame.shape[1], _map8(p_fwd), _map8(p_bwd), _dp(mosaic), mosaic.shape[2],
+                                        mosaic.shape[1], C.byref(_opts(opts)), _dp(out), out.numel(), C.byref(g2), C.byref(s), _stream()))
     return out, g2, s
 
 
@@ -376,7 +405,7 @@ def map_points(x, y, p_fwd, offx, offy):
     """updateFeaturesByHomography (ImageProcess.cpp:622-631) -> (x, y, ix, iy)."""
     x, y = np.array(x, np.float32), np.array(y, np.float32)
     ix, iy = np.empty(x.size, np.int32), np.empty(x.size, np.int32)
-    _chk(lib().stitch_map_points(_p(x), _p(y), _p(ix), _p(iy), x.size, _map8(p_fwd), C.c_float(offx), C.c_float(offy)))
+    _chk(lib().stitch_map_points(_p(x), _p(y), _p(ix), _p(iy), x.size, _map8(p_fwd), offx, offy))
     return x, y, ix, iy
 
 
@@ -416,8 +445,7 @@ def match(db, query, ratio=RATIO_THRESHOLD):
     dist2 = np.empty((nq, 2), np.float32)
     pairs = np.empty((max(nq, 1), 2), np.int32)
     count = C.c_int32(0)
-    _chk(lib().stitch_match_l1_ratio(_p(db), db.shape[0], _p(query), nq, C.c_double(ratio), _p(nn), _p(dist2), _p(pairs),
-                                     C.byref(count)))
+    _chk(lib().stitch_match_l1_ratio(_p(db), db.shape[0], _p(query), nq, ratio, _p(nn), _p(dist2), _p(pairs), C.byref(count)))
     return pairs[:count.value].copy(), nn, dist2[:, 0].copy(), dist2[:, 1].copy()
 
 
@@ -437,8 +465,7 @@ def _match_outputs(db, query, want_dist=True):
 
 
 def _mdesc(db, query, o):
-    return MatchDesc(_dp(db), _dp(query), db.shape[0], query.shape[0], _dp(o["nn"]),
-                     _dp(o["dist2"]) if o["dist2"] is not None else None, _dp(o["pairs"]), _dp(o["count"]))
+    return MatchDesc(_dp(db), _dp(query), db.shape[0], query.shape[0], _dp(o["nn"]), _dp(o["dist2"]), _dp(o["pairs"]), _dp(o["count"]))
 
 
 def dev_match(db, query, ratio=RATIO_THRESHOLD, want_dist=True):
@@ -447,8 +474,7 @@ def dev_match(db, query, ratio=RATIO_THRESHOLD, want_dist=True):
     db, query = _tdesc(db), _tdesc(query)
     o = _match_outputs(db, query, want_dist)
     d = _mdesc(db, query, o)
-    _chk(lib().stitch_dev_match_l1_ratio(d.db, d.n_db, d.query, d.n_query, C.c_double(ratio), d.nn, d.dist2, d.pairs, d.count,
-                                         _stream()))
+    _chk(lib().stitch_dev_match_l1_ratio(d.db, d.n_db, d.query, d.n_query, ratio, d.nn, d.dist2, d.pairs, d.count, _stream()))
     return o
 
 
@@ -457,7 +483,7 @@ def dev_match_many(sets, ratio=RATIO_THRESHOLD, want_dist=True):
     sets = [(_tdesc(a), _tdesc(b)) for a, b in sets]
     outs = [_match_outputs(a, b, want_dist) for a, b in sets]
     arr = (MatchDesc * max(len(sets), 1))(*[_mdesc(a, b, o) for (a, b), o in zip(sets, outs)])
-    _chk(lib().stitch_dev_match_l1_ratio_many(arr, len(sets), C.c_double(ratio), _stream()))
+    _chk(lib().stitch_dev_match_l1_ratio_many(arr, len(sets), ratio, _stream()))
     return outs
 
 # ---- map estimation: ImageProcess::RANSAC (ImageProcess.cpp:395-529) -----------------------------------------------------
@@ -483,7 +509,7 @@ class RansacDesc(C.Structure):
 def ransac_rand(n, seed=RANSAC_SEED):
     """The first n values of rand() after srand(seed) as the library generates them (host hook) -> int32 array."""
     out = np.empty(int(n), np.int32)
-    lib().stitch_ransac_rand(C.c_uint32(int(seed)), _p(out), int(n))
+    lib().stitch_ransac_rand(int(seed), _p(out), int(n))
     return out
 
 
@@ -529,10 +555,8 @@ def dev_ransac_many(lists, opts=None, want_inliers=True):
         if count is not None:
             _tvec(count, torch.int32, "count")
         inl.append(torch.empty(n_max, dtype=torch.int32, device=dev) if want_inliers else None)
-        descs.append(RansacDesc(_dp(xy[0]), _dp(xy[1]), _dp(xy[2]), _dp(xy[3]), _dp(pairs) if pairs is not None else None,
-                                _dp(count) if count is not None else None, n_max, int(bool(e.get("mirror", False))),
-                                C.c_void_p(p.data_ptr() + 64 * i), _dp(inl[-1]) if want_inliers else None,
-                                C.c_void_p(info.data_ptr() + 4 * RANSAC_INFO * i)))
+        descs.append(RansacDesc(_dp(xy[0]), _dp(xy[1]), _dp(xy[2]), _dp(xy[3]), _dp(pairs), _dp(count), n_max, int(bool(e.get("mirror", False))),
+                                p.data_ptr() + 64 * i, _dp(inl[-1]), info.data_ptr() + 4 * RANSAC_INFO * i))
     arr = (RansacDesc * max(n, 1))(*descs)
     o = opts if opts is not None else RansacOpts()
     _chk(lib().stitch_dev_ransac_many(arr, n, C.byref(o), _stream()))
@@ -577,8 +601,8 @@ def sift(gray, opts=None, kp_cap=8192, feat_cap=None):
     desc = np.zeros((max(feat_cap, 1), DESCRIPTOR_DIM), np.float32)
     counts, status = np.zeros(2, np.int32), np.zeros(SIFT_STATUS, np.int32)
     o = opts if opts is not None else SiftOpts()
-    _chk(lib().stitch_sift(_p(g), g.shape[1], g.shape[0], C.byref(o), _p(kp), int(kp_cap), _p(fkp), _p(ang), _p(desc), int(feat_cap),
-                           _p(counts), _p(status)))
+    _chk(lib().stitch_sift(_p(g), g.shape[1], g.shape[0], C.byref(o), _p(kp), int(kp_cap), _p(fkp), _p(ang), _p(desc), int(feat_cap), _p(counts),
+                           _p(status)))
     nk, nf = int(counts[0]), int(counts[1])
     return dict(kp=kp[:nk].copy(), fkp=fkp[:nf].copy(), angle=ang[:nf].copy(), desc=desc[:nf].copy(), status=status)
 
@@ -605,7 +629,7 @@ def dev_sift_many(images, opts=None, kp_cap=8192, feat_cap=None):
         outs.append(o)
         descs.append(SiftDesc(_dp(t), t.shape[1], t.shape[0], t.stride(0) * t.element_size(), int(t.dtype == torch.float32),
                               _dp(o["kp"]), int(kp_cap), int(feat_cap), _dp(o["fkp"]), _dp(o["angle"]), _dp(o["desc"]),
-                              _dp(o["head"]), C.c_void_p(o["head"].data_ptr() + 8)))
+                              _dp(o["head"]), o["head"].data_ptr() + 8))
     arr = (SiftDesc * max(n, 1))(*descs)
     op = opts if opts is not None else SiftOpts()
     _chk(lib().stitch_dev_sift_many(arr, n, C.byref(op), _stream()))
@@ -622,15 +646,6 @@ def sift_unpack(out):
 
 
 # ---- device-resident entry points (torch tensors on the HIP device) --------------------------------------------
-def _tsfx(t):
-    import torch
-    if t.dtype == torch.uint8:
-        return "u8"
-    if t.dtype == torch.float32:
-        return "f32"
-    raise TypeError(f"unsupported tensor dtype {t.dtype}")
-
-
 def _timg(t):
     if not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[0] != 3:
         raise ValueError("expected a contiguous (3,H,W) tensor on the HIP device")
@@ -643,7 +658,7 @@ def _stream():
 
 
 def _dp(t):
-    return C.c_void_p(t.data_ptr())
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def dev_project(src, fov_deg=15.0, out=None):
@@ -651,7 +666,7 @@ def dev_project(src, fov_deg=15.0, out=None):
     src = _timg(src)
     out = torch.empty_like(src) if out is None else out
     _, h, w = src.shape
-    _chk(getattr(lib(), "stitch_dev_project_" + _tsfx(src))(_dp(src), w, h, C.c_float(fov_deg), _dp(out), _stream()))
+    _chk(_fn("stitch_dev_project_", src)(_dp(src), w, h, fov_deg, _dp(out), _stream()))
     return out
 
 
@@ -665,42 +680,40 @@ def dev_project_gray(src, fov_deg=15.0):
     out = torch.empty_like(src)
     g = torch.empty((h, w), dtype=torch.uint8, device=src.device)
     f = torch.empty((h, w), dtype=torch.float32, device=src.device)
-    _chk(lib().stitch_dev_project_gray_u8(_dp(src), w, h, C.c_float(fov_deg), _dp(out), _dp(g), _dp(f), _stream()))
+    _chk(lib().stitch_dev_project_gray_u8(_dp(src), w, h, fov_deg, _dp(out), _dp(g), _dp(f), _stream()))
     return out, g, f
 
 
 def dev_warp(src, p, offx, offy, canvas):
     src, canvas = _timg(src), _timg(canvas)
-    _chk(getattr(lib(), "stitch_dev_warp_" + _tsfx(src))(_dp(src), src.shape[2], src.shape[1], _map8(p), C.c_float(offx),
-                                                         C.c_float(offy), _dp(canvas), canvas.shape[2], canvas.shape[1], _stream()))
+    _chk(_fn("stitch_dev_warp_", src)(_dp(src), src.shape[2], src.shape[1], _map8(p), offx, offy, _dp(canvas), canvas.shape[2], canvas.shape[1],
+                                      _stream()))
     return canvas
 
 
 def dev_move(src, ox, oy, canvas):
     src, canvas = _timg(src), _timg(canvas)
-    _chk(getattr(lib(), "stitch_dev_move_" + _tsfx(src))(_dp(src), src.shape[2], src.shape[1], int(ox), int(oy), _dp(canvas),
-                                                         canvas.shape[2], canvas.shape[1], _stream()))
+    _chk(_fn("stitch_dev_move_", src)(_dp(src), src.shape[2], src.shape[1], int(ox), int(oy), _dp(canvas), canvas.shape[2], canvas.shape[1],
+                                      _stream()))
     return canvas
 
 
 def dev_equalize(img, hist=None):
     """In place on a uint8 device tensor; `hist` (int32[256] device tensor, optional) receives the Y bins."""
     img = _timg(img)
-    _chk(lib().stitch_dev_equalize_u8(_dp(img), img.shape[2], img.shape[1], _dp(hist) if hist is not None else None, _stream()))
+    _chk(lib().stitch_dev_equalize_u8(_dp(img), img.shape[2], img.shape[1], _dp(hist), _stream()))
     return img
 
 
 def dev_lummix(result, equalized, num=19.0, den=20.0):
     result, equalized = _timg(result), _timg(equalized)
-    _chk(lib().stitch_dev_lummix_u8(_dp(result), _dp(equalized), result.shape[2], result.shape[1], C.c_double(num),
-                                    C.c_double(den), _stream()))
+    _chk(lib().stitch_dev_lummix_u8(_dp(result), _dp(equalized), result.shape[2], result.shape[1], num, den, _stream()))
     return result
 
 
 def dev_finish(result, num=19.0, den=20.0, hist=None):
     result = _timg(result)
-    _chk(lib().stitch_dev_finish_u8(_dp(result), result.shape[2], result.shape[1], C.c_double(num), C.c_double(den),
-                                    _dp(hist) if hist is not None else None, _stream()))
+    _chk(lib().stitch_dev_finish_u8(_dp(result), result.shape[2], result.shape[1], num, den, _dp(hist), _stream()))
     return result
 
 
@@ -708,21 +721,19 @@ def dev_synth(w, h, frame_id, dtype, device=None):
     """Synthetic benchmark frame generated on the device -> (3,h,w) tensor."""
     import torch
     out = torch.empty((3, h, w), dtype=dtype, device=device or torch.device("cuda", torch.cuda.current_device()))
-    _chk(getattr(lib(), "stitch_dev_synth_" + _tsfx(out))(_dp(out), int(w), int(h), int(frame_id), _stream()))
+    _chk(_fn("stitch_dev_synth_", out)(_dp(out), int(w), int(h), int(frame_id), _stream()))
     return out
 
 
 def dev_check_fastdiv(w):
     """stitch_dev_check_fastdiv: (numerators tested, quotients that differ from the IEEE divide) for denominator w."""
-    lib().stitch_dev_check_fastdiv.argtypes = [C.c_float, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     t, m = C.c_ulonglong(), C.c_ulonglong()
-    _chk(lib().stitch_dev_check_fastdiv(C.c_float(w), C.byref(t), C.byref(m)))
+    _chk(lib().stitch_dev_check_fastdiv(w, C.byref(t), C.byref(m)))
     return t.value, m.value
 
 
 def dev_check_collapse_taps(w, h, probe):
     """stitch_dev_check_collapse_taps: (samples compared, samples that differ between k_collapse4's per-lane taps and k_collapse)."""
-    lib().stitch_dev_check_collapse_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     t, m = C.c_ulonglong(), C.c_ulonglong()
     _chk(lib().stitch_dev_check_collapse_taps(int(w), int(h), int(probe), C.byref(t), C.byref(m)))
     return t.value, m.value
@@ -733,18 +744,33 @@ def dev_quantize(src, out=None):
     import torch
     assert src.is_cuda and src.is_contiguous() and src.dtype == torch.float32
     out = torch.empty(src.shape, dtype=torch.uint8, device=src.device) if out is None else out
-    _chk(lib().stitch_dev_quantize_u8(_dp(src), _dp(out), C.c_size_t(src.numel()), _stream()))
+    _chk(lib().stitch_dev_quantize_u8(_dp(src), _dp(out), src.numel(), _stream()))
     return out
 
 
-class Plan:
+class _Handle:
+    """An object of the library behind an opaque pointer; `_destroy` names the function that releases it."""
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Plan(_Handle):
     """stitch_plan: the device workspace of one canvas size (pyramids, scratch, tables, seam record)."""
+    _destroy = "stitch_plan_destroy"
 
     def __init__(self, cw, ch, opts=None, max_pairs=1):
         self._h = C.c_void_p()
         self.cw, self.ch, self.max_pairs = int(cw), int(ch), int(max_pairs)
-        o = _opts(opts)
-        _chk(lib().stitch_plan_create_batched(self.cw, self.ch, C.byref(o), self.max_pairs, C.byref(self._h)))
+        _chk(lib().stitch_plan_create_batched(self.cw, self.ch, C.byref(_opts(opts)), self.max_pairs, C.byref(self._h)))
         lw, lh = (C.c_int * 32)(), (C.c_int * 32)()
         n = _chk(lib().stitch_plan_levels(self._h, lw, lh))
         self.level_w, self.level_h = list(lw[:n]), list(lh[:n])
@@ -784,23 +810,12 @@ class Plan:
     def workspace_base(self):
         return lib().stitch_plan_workspace_base(self._h) or 0
 
-    def close(self):
-        if self._h:
-            lib().stitch_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def blend(self, a, b, out=None):
         import torch
         a, b = _timg(a), _timg(b)
         assert a.shape == b.shape == (3, self.ch, self.cw)
         out = torch.empty_like(a) if out is None else out
-        _chk(getattr(lib(), "stitch_dev_blend_" + _tsfx(a))(self._h, _dp(a), _dp(b), _dp(out), _stream()))
+        _chk(_fn("stitch_dev_blend_", a)(self._h, _dp(a), _dp(b), _dp(out), _stream()))
         return out
 
     def pair(self, frame, p, offx, offy, mosaic, ox, oy, out=None):
@@ -809,9 +824,8 @@ class Plan:
         frame, mosaic = _timg(frame), _timg(mosaic)
         if out is None:
             out = torch.empty((3, self.ch, self.cw), dtype=frame.dtype, device=frame.device)
-        _chk(getattr(lib(), "stitch_dev_pair_" + _tsfx(frame))(
-            self._h, _dp(frame), frame.shape[2], frame.shape[1], _map8(p), C.c_float(offx), C.c_float(offy), _dp(mosaic),
-            mosaic.shape[2], mosaic.shape[1], int(ox), int(oy), _dp(out), _stream()))
+        _chk(_fn("stitch_dev_pair_", frame)(self._h, _dp(frame), frame.shape[2], frame.shape[1], _map8(p), offx, offy, _dp(mosaic),
+                                            mosaic.shape[2], mosaic.shape[1], int(ox), int(oy), _dp(out), _stream()))
         return out
 
     def pairs(self, items):
@@ -820,14 +834,14 @@ class Plan:
         mosaic as unsigned char as well.  Returns the list of `out` tensors."""
         items = list(items)
         arr = (PairDesc * len(items))()
-        sfx = None
+        fn = None
         for d, it in zip(arr, items):
             frame, p, offx, offy, mosaic, ox, oy, out = it[:8]
             out8 = it[8] if len(it) > 8 else None
             frame, mosaic, out = _timg(frame), _timg(mosaic), _timg(out)
             assert tuple(out.shape) == (3, self.ch, self.cw) and out.dtype == frame.dtype == mosaic.dtype
-            sfx = _tsfx(frame) if sfx is None else sfx
-            assert sfx == _tsfx(frame), "one pixel type per batch"
+            assert frame.dtype == items[0][0].dtype, "one pixel type per batch"
+            fn = fn or _fn("stitch_dev_pairs_", frame)
             d.frame, d.fw, d.fh = frame.data_ptr(), frame.shape[2], frame.shape[1]
             d.p = _map8(p)
             d.offx, d.offy = float(offx), float(offy)
@@ -837,7 +851,7 @@ class Plan:
                 import torch
                 assert out8.is_cuda and out8.is_contiguous() and out8.dtype == torch.uint8 and tuple(out8.shape) == (3, self.ch, self.cw)
                 d.out_u8 = out8.data_ptr()
-        _chk(getattr(lib(), "stitch_dev_pairs_" + sfx)(self._h, arr, len(items), _stream()))
+        _chk(fn(self._h, arr, len(items), _stream()))
         return [it[7] for it in items]
 
     def status(self, index=0):
@@ -852,7 +866,7 @@ class Plan:
         _chk(lib().stitch_plan_clear_fault(self._h))
 
     def set_handoff_spin_limit(self, polls):
-        _chk(lib().stitch_plan_set_handoff_spin_limit(self._h, C.c_uint(int(polls))))
+        _chk(lib().stitch_plan_set_handoff_spin_limit(self._h, int(polls)))
 
     def set_profiling_kernel(self, name):
         _chk(lib().stitch_plan_set_profiling_kernel(self._h, KERNELS.index(name)))
@@ -862,21 +876,19 @@ class Plan:
 
     def read_profile(self):
         """-> {kernel: (total_ms, launches, level0_ms)} since profiling was enabled / last read."""
-        ms = (C.c_double * len(KERNELS))()
-        n = (C.c_int * len(KERNELS))()
-        l0 = (C.c_double * len(KERNELS))()
+        ms, n, l0 = (C.c_double * len(KERNELS))(), (C.c_int * len(KERNELS))(), (C.c_double * len(KERNELS))()
         _chk(lib().stitch_plan_read_profile(self._h, ms, n, l0))
         return {KERNELS[i]: (ms[i], n[i], l0[i]) for i in range(len(KERNELS))}
 
 
-class Band:
+class Band(_Handle):
     """stitch_band: this rank's row band of ONE pair split over several GPUs (include/stitch.h, "one pair split into row
     bands").  Computation only; what crosses ranks is moved by pipeline.BandStitcher."""
+    _destroy = "stitch_band_destroy"
 
     def __init__(self, cw, ch, rank, nranks, split_levels, opts=None):
         self._h = C.c_void_p()
-        o = _opts(opts)
-        _chk(lib().stitch_band_create(int(cw), int(ch), int(rank), int(nranks), int(split_levels), C.byref(o), C.byref(self._h)))
+        _chk(lib().stitch_band_create(int(cw), int(ch), int(rank), int(nranks), int(split_levels), C.byref(_opts(opts)), C.byref(self._h)))
         self.cw, self.ch, self.rank, self.nranks, self.split_levels = int(cw), int(ch), int(rank), int(nranks), int(split_levels)
         tot = C.c_int()
         lib().stitch_band_levels(self._h, C.byref(tot))
@@ -887,22 +899,10 @@ class Band:
             _chk(lib().stitch_band_geometry(self._h, l, g))
             self.geom.append(dict(w=g[0], rows=g[1], row0=g[2], pitch=g[3], h=g[4], halo=g[5]))
 
-    def close(self):
-        if self._h:
-            lib().stitch_band_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def compose(self, frame, p, offx, offy, mosaic, ox, oy):
         frame, mosaic = _timg(frame), _timg(mosaic)
-        _chk(getattr(lib(), "stitch_band_compose_" + _tsfx(frame))(
-            self._h, _dp(frame), frame.shape[2], frame.shape[1], _map8(p), C.c_float(offx), C.c_float(offy), _dp(mosaic), mosaic.shape[2],
-            mosaic.shape[1], int(ox), int(oy), _stream()))
+        _chk(_fn("stitch_band_compose_", frame)(self._h, _dp(frame), frame.shape[2], frame.shape[1], _map8(p), offx, offy, _dp(mosaic),
+                                                mosaic.shape[2], mosaic.shape[1], int(ox), int(oy), _stream()))
 
     def set_level0(self, source_fused):
         """Level 0 source-fused (default) or materialised (what the one-plane-at-a-time sweeps need); before the next compose."""
@@ -913,21 +913,19 @@ class Band:
 
     def reduce_xy_fwd(self, level, resume, state_out):
         """reduce_x + reduce_y_fwd(plane -1) with the anticausal x and causal y sweeps fused (one pass over the level)."""
-        _chk(lib().stitch_band_reduce_xy_fwd(self._h, int(level), _dp(resume) if resume is not None else None, _dp(state_out), _stream()))
+        _chk(lib().stitch_band_reduce_xy_fwd(self._h, int(level), _dp(resume), _dp(state_out), _stream()))
 
     def reduce_y_fwd(self, level, plane, resume, state_out):
-        _chk(lib().stitch_band_reduce_y_fwd(self._h, int(level), int(plane), _dp(resume) if resume is not None else None, _dp(state_out), _stream()))
+        _chk(lib().stitch_band_reduce_y_fwd(self._h, int(level), int(plane), _dp(resume), _dp(state_out), _stream()))
 
     def reduce_y_bwd(self, level, plane, fwd_state, resume, state_out):
-        _chk(lib().stitch_band_reduce_y_bwd(self._h, int(level), int(plane), _dp(fwd_state), _dp(resume) if resume is not None else None,
-                                            _dp(state_out), _stream()))
+        _chk(lib().stitch_band_reduce_y_bwd(self._h, int(level), int(plane), _dp(fwd_state), _dp(resume), _dp(state_out), _stream()))
 
     def reduce_y_fwd_cols(self, level, x0, x1, resume, state_out):
-        _chk(lib().stitch_band_reduce_y_fwd_cols(self._h, int(level), int(x0), int(x1), _dp(resume) if resume is not None else None, _dp(state_out), _stream()))
+        _chk(lib().stitch_band_reduce_y_fwd_cols(self._h, int(level), int(x0), int(x1), _dp(resume), _dp(state_out), _stream()))
 
     def reduce_y_bwd_cols(self, level, x0, x1, fwd_state, resume, state_out):
-        _chk(lib().stitch_band_reduce_y_bwd_cols(self._h, int(level), int(x0), int(x1), _dp(fwd_state), _dp(resume) if resume is not None else None,
-                                                 _dp(state_out), _stream()))
+        _chk(lib().stitch_band_reduce_y_bwd_cols(self._h, int(level), int(x0), int(x1), _dp(fwd_state), _dp(resume), _dp(state_out), _stream()))
 
     def rows(self, level, kind, first_row, nrows, buf, to_buffer):
         assert buf.is_cuda and buf.is_contiguous() and buf.dtype.is_floating_point and buf.element_size() == 4
@@ -939,7 +937,7 @@ class Band:
 
     def collapse(self, level, out=None):
         if level == 0:
-            _chk(getattr(lib(), "stitch_band_collapse_" + _tsfx(out))(self._h, 0, _dp(out), _stream()))
+            _chk(_fn("stitch_band_collapse_", out)(self._h, 0, _dp(out), _stream()))
         else:
             _chk(lib().stitch_band_collapse_f32(self._h, int(level), None, _stream()))
 

@@ -63,7 +63,7 @@ def calls(L, buf):
         "project_gray_null": lambda: L.stitch_project_gray_u8(N, 8, 8, f(26), N, N, N),
         "bbox_null": lambda: L.stitch_canvas_bbox(8, 8, N, 8, 8, N, N, N, N),
         "step_geom_null": lambda: L.stitch_step_geometry(8, 8, N, 8, 8, N),
-        "dev_step_null": lambda: L.stitch_dev_step_u8(N, 8, 8, N, N, N, 8, 8, N, N, N, N, N, N),
+        "dev_step_null": lambda: L.stitch_dev_step_u8(N, 8, 8, N, N, N, 8, 8, N, N, 0, N, N, N),
         "map_points_null": lambda: L.stitch_map_points(N, N, N, N, 4, N, f(0), f(0)),
         "shift_points_null": lambda: L.stitch_shift_points(N, N, N, N, 4, 0, 0),
         "synth_null": lambda: L.stitch_dev_synth_u8(N, 8, 8, 0, N),

@@ -948,6 +948,23 @@ def test_bad_arguments_are_refused(st, gpu):
     assert not any(buf), "a refused call wrote into a buffer"
 
 
+def test_plain_int_pointers_reach_the_library_whole(st, gpu):
+    """Device pointers, the element count and the stream as plain Python ints: without declared argument types ctypes passes
+    such an int as a 32-bit C int, and device allocations lie above 4 GiB, so a truncated pointer cannot give these bytes.
+    The declaration is asserted first: a regression fails there and never makes the call."""
+    import ctypes as C
+    import torch
+    fn = st.capi.lib().stitch_dev_quantize_u8
+    assert fn.argtypes == [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    src = torch.from_numpy(np.random.RandomState(7).uniform(0.0, 255.9, (3, 5, 7)).astype(np.float32)).to(gpu)
+    assert src.dtype == torch.float32 and float(src.min()) >= 0.0 and float(src.max()) <= 255.9
+    out = torch.zeros(src.shape, dtype=torch.uint8, device=gpu)
+    rc = fn(src.data_ptr(), out.data_ptr(), src.numel(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert torch.equal(out, src.to(torch.uint8))
+
+
 def test_host_entry_points_reuse_workspaces_and_trim(st, gpu, oracle, monkeypatch):
     """The host-pointer entry points keep idle workspaces (LRU by canvas and options), device staging and pinned buffers
     between calls; results must not depend on whether a call found a cached plan, a new one, or ran after stitch_trim(), and
