@@ -143,6 +143,7 @@ def lib():
             except AttributeError:
                 raise ImportError(f"{LIB_PATH} does not export {name}: it was built from another include/stitch.h") from None
             f.restype, f.argtypes = res, args
+        L.stitch_plan_handoff_counts.restype, L.stitch_plan_handoff_counts.argtypes = i32, [vp, vp]  # include/stitch_handoff.h
         _lib = L
     return _lib
 
@@ -864,6 +865,13 @@ class Plan(_Handle):
     def clear_fault(self):
         """Acknowledge the fused sweep's sticky time-out report (stitch_plan_clear_fault)."""
         _chk(lib().stitch_plan_clear_fault(self._h))
+
+    def handoff_counts(self):
+        """-> (full, zero_marker, mask_tiles_recorded): hand-offs of the fused sweeps since the plan was created, published in full
+        and as the one-word zero marker, and level-0 mask tiles recorded instead of stored (stitch_plan_handoff_counts)."""
+        out = (C.c_uint64 * 3)()
+        _chk(lib().stitch_plan_handoff_counts(self._h, out))
+        return tuple(int(v) for v in out)
 
     def set_handoff_spin_limit(self, polls):
         _chk(lib().stitch_plan_set_handoff_spin_limit(self._h, int(polls)))

@@ -10,10 +10,12 @@
 //
 // Workgroups are persistent and claim bands in increasing R from one atomic counter, so the band a claimed band
 // depends on has always been claimed earlier by a workgroup that is running (no residency assumption, no deadlock).
-// The y state travels as 8-byte {tag, word} granules (the data is the flag; relaxed agent-scope atomics = sc1
-// write-through stores / L1-bypassing loads; guide 6, Guideline 16, form R2): six granules per lane for three
-// doubles.  tag = (epoch << 12) | (producer band + 1), so the slot of a column block is reused band after band
-// within a launch.  Between launches the host clears the slots with k_clear_words and passes a constant epoch: a
+// The y state travels as 8-byte granules, a 16-bit tag above 48 bits of payload (the data is the flag; relaxed
+// agent-scope atomics = sc1 write-through stores / L1-bypassing loads; guide 6, Guideline 16, form R2): four
+// granules per lane for three doubles, a fifth on the planes that pass the level-0 mask row down.  tag = (epoch << 12)
+// | (producer band + 1), so the slot of a column block is reused band after band within a launch; tag bit 15 marks a
+// state that is +0 in every live column, which travels as the polled word alone (a third of the image planes at
+// config 2: the canvas left of the warped frame, right of the mosaic).  Between launches the host clears the slots with k_clear_words and passes a constant epoch: a
 // per-launch epoch would be frozen by a HIP-graph capture and stale tags of the previous replay would match at
 // once.  Every spin is bounded; a timeout raises `abort` for all workgroups.
 typedef unsigned long long u64;
@@ -21,12 +23,16 @@ typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 
 struct Wavefront {
-    u64* yg;            // [planes][NC][7][64] granules: y state leaving band R towards band R+1 (+ one spare word)
-    int mask_l0;        // level-0 implicit mask (see MaskL0): planes p%7==6 carry their x-blurred row in the 7th granule
+    u64* yg;            // [planes][NC][WF_GRAN][64] granules: y state leaving band R towards band R+1
+    int mask_l0;        // level-0 implicit mask (see MaskL0): planes p%7==6 carry their x-blurred row in the 5th granule.
+                        // 2: the tiles of such a plane below its first band are recorded, not stored, where they repeat the
+                        // plane's row 0 (the reader is k_vv_y_bwd_dec with fill_l0 set: a plan's batch launch only)
     unsigned* counter;  // band queue head (zeroed by the host before the launch)
     unsigned* abort;    // set when a spin timed out (cleared in front of every launch sequence)
     unsigned* sticky;   // count of timed-out waits since the plan was created: NEVER cleared by the launch sequence, so
-                        // a bail-out in any earlier queued call is still visible to stitch_plan_status_at
+                        // a bail-out in any earlier queued call is still visible to stitch_plan_status_at.  Behind it, as
+                        // 64-bit words that only grow too: hand-offs published in full (sticky + 2) and as the zero marker
+                        // (sticky + 4), added once per band by one lane (stitch_plan_handoff_counts)
     int NR, NC, NP;
     unsigned epoch;
     unsigned spin_limit;      // polls before a wait gives up (STITCH_XBYF_SPIN_LIMIT; tests force the bail-out path with 0)
@@ -41,67 +47,80 @@ struct Wavefront {
 #ifndef STITCH_XBYF_SLEEP
 #define STITCH_XBYF_SLEEP 32  // s_sleep between the polls of a hand-off wait (A/B builds: 8 and 2 measured, scripts/experiments/r4_run28.sh)
 #endif
-constexpr int WF_GRAN = 7;  // granules per lane and slot: 3 doubles = 6 words, + 1 spare word
-__device__ __forceinline__ void granules_publish(u64* base, int lane, unsigned tag, double a, double b, double c, unsigned extra) {
-    const u64 w[3] = {(u64)__double_as_longlong(a), (u64)__double_as_longlong(b), (u64)__double_as_longlong(c)};
-    __hip_atomic_store((gu64*)(base + 6 * WAVE + lane), ((u64)tag << 32) | extra, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        __hip_atomic_store((gu64*)(base + (2 * i) * WAVE + lane), ((u64)tag << 32) | (w[i] & 0xffffffffu), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store((gu64*)(base + (2 * i + 1) * WAVE + lane), ((u64)tag << 32) | (w[i] >> 32), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+constexpr int WF_GRAN = 5;  // slot stride in granules per lane: 3 doubles = 4 payloads of 48 bits, + the mask row's word (pass_row planes only)
+constexpr int WF_POLL = 3;  // the polled word: granule WF_POLL of the last lane
+constexpr unsigned WF_ZERO = 0x8000u;  // tag bit: every live column's state is +0 (and the row word 0); ONLY the polled word was stored
+constexpr u64 WF_PAYLOAD = (1ull << 48) - 1;
+// Publishes the y state of `live` columns under `tag`; returns true when it went out as the zero marker (one word instead of four
+// or five per lane).  The test is on the bit pattern, as in y_idle and the zero-tile flags: a -0.0 is not zero here.
+__device__ __forceinline__ bool granules_publish(u64* base, int lane, int live, unsigned tag, double a, double b, double c, unsigned extra, bool row) {
+    const u64 wa = (u64)__double_as_longlong(a), wb = (u64)__double_as_longlong(b), wc = (u64)__double_as_longlong(c), t = (u64)tag << 48;
+    if (__ballot(lane < live && ((wa | wb | wc) != 0 || (row && extra != 0))) == 0) {
+        if (lane == WAVE - 1)
+            __hip_atomic_store((gu64*)(base + WF_POLL * WAVE + lane), (u64)(tag | WF_ZERO) << 48, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return true;
     }
+    if (row) __hip_atomic_store((gu64*)(base + 4 * WAVE + lane), t | extra, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((gu64*)(base + lane), t | (wa & WF_PAYLOAD), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((gu64*)(base + WAVE + lane), t | (wa >> 48) | ((wb & 0xffffffffull) << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((gu64*)(base + 2 * WAVE + lane), t | (wb >> 32) | ((wc & 0xffffull) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((gu64*)(base + 3 * WAVE + lane), t | (wc >> 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return false;
 }
 // Wait for a state.  Pollers cost the streaming wavefronts bandwidth (guide, "polling-cost"), and most bands wait
 // long for their first tile (band R starts R hand-offs after band 0), so the wait is two-phase: ONE lane re-reads
-// ONE granule with a long sleep between polls; once its tag matches, the whole wavefront reads its six granules,
-// repeating that (rarely) until every tag matches -- the stores of one publish may become visible in any order.
+// ONE granule with a long sleep between polls; once its tag matches, the whole wavefront reads its four (five) granules,
+// repeating that (rarely) until every tag matches -- the stores of one publish may become visible in any order.  A polled
+// word that carries the zero marker IS the whole state: nothing else is read.
 // Wave-uniform exit; false on timeout / abort.
-// The same read, split in two so that it can be issued early: the seven loads go out BEFORE the next tile's prefetch
+// The same read, split in two so that it can be issued early: the loads go out BEFORE the next tile's prefetch
 // (loads return in order, so a poll issued behind 16 tile loads would wait for all of them), the check happens after the
-// x sweep.  In the steady state of the pipeline the band above is ahead and the early read already holds the state.
+// x sweep.  In the steady state of the pipeline the band above is ahead and the early read already holds the state.  The
+// polled word is the last lane's granule WF_POLL, so the early read holds the zero marker too: no second round trip.
 // (A second tile of prefetch was tried and is slower: more bytes in flight lengthen every queue the hand-off sits in.)
-__device__ __forceinline__ void granules_issue(const u64* base, int lane, u64 g[WF_GRAN]) {
+// `row` (wave-uniform, constant over a band): the plane passes the mask row down, i.e. the fifth granule exists.
+__device__ __forceinline__ void granules_issue(const u64* base, int lane, u64 g[WF_GRAN], bool row) {
 #pragma unroll
-    for (int i = 0; i < WF_GRAN; ++i) g[i] = __hip_atomic_load((gu64*)(base + i * WAVE + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int i = 0; i < 4; ++i) g[i] = __hip_atomic_load((gu64*)(base + i * WAVE + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    g[4] = 0;
+    if (row) g[4] = __hip_atomic_load((gu64*)(base + 4 * WAVE + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ bool granules_accept(const u64 g[WF_GRAN], unsigned tag, double& a, double& b, double& c, unsigned& extra) {
-    bool ok = true;
+__device__ __forceinline__ bool granules_accept(const u64 g[WF_GRAN], unsigned tag, double& a, double& b, double& c, unsigned& extra, bool row) {
+    const unsigned polled = (unsigned)__builtin_amdgcn_readlane((int)(g[WF_POLL] >> 48), WAVE - 1);
+    if (polled == (tag | WF_ZERO)) {
+        a = b = c = 0.0;
+        extra = 0;
+        return true;
+    }
+    bool ok = !row || (unsigned)(g[4] >> 48) == tag;
 #pragma unroll
-    for (int i = 0; i < WF_GRAN; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+    for (int i = 0; i < 4; ++i) ok &= (unsigned)(g[i] >> 48) == tag;
     if (!__all(ok)) return false;
-    extra = (unsigned)g[6];
-    a = __longlong_as_double((long long)((g[0] & 0xffffffffu) | (g[1] << 32)));
-    b = __longlong_as_double((long long)((g[2] & 0xffffffffu) | (g[3] << 32)));
-    c = __longlong_as_double((long long)((g[4] & 0xffffffffu) | (g[5] << 32)));
+    extra = (unsigned)g[4];
+    a = __longlong_as_double((long long)((g[0] & WF_PAYLOAD) | (g[1] << 48)));
+    b = __longlong_as_double((long long)(((g[1] & WF_PAYLOAD) >> 16) | (g[2] << 32)));
+    c = __longlong_as_double((long long)(((g[2] & WF_PAYLOAD) >> 32) | (g[3] << 16)));
     return true;
 }
 __device__ __forceinline__ bool granules_consume(const u64* base, int lane, unsigned tag, unsigned* abort, unsigned* sticky,
-                                                 unsigned spin_limit, double& a, double& b, double& c, unsigned& extra, bool brisk = false) {
+                                                 unsigned spin_limit, double& a, double& b, double& c, unsigned& extra, bool row, bool brisk = false) {
     // brisk (k_vv_xby_m's courier: a wavefront that does nothing else, few of them on the chip): short naps between polls
     for (unsigned spins = 0;; ++spins) {
-        // two-phase poll: one lane watches the tag of one granule, the whole wavefront reads the seven only once it has
-        // appeared (polling all seven, or sleeping less, measured within +-3 %)
+        // two-phase poll: one lane watches the tag of one granule, the whole wavefront reads its granules only once it has
+        // appeared (polling all of them, or sleeping less, measured within +-3 %)
         unsigned seen = 0;
         if (lane == 0)
-            seen = (unsigned)(__hip_atomic_load((gu64*)(base + 5 * WAVE + (WAVE - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32);
+            seen = (unsigned)(__hip_atomic_load((gu64*)(base + WF_POLL * WAVE + (WAVE - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 48);
         seen = __shfl(seen, 0, 64);
+        if (seen == (tag | WF_ZERO)) {  // the marker: nothing else was stored
+            a = b = c = 0.0;
+            extra = 0;
+            return true;
+        }
         if (seen == tag) {
             u64 g[WF_GRAN];
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < WF_GRAN; ++i) {
-                g[i] = __hip_atomic_load((gu64*)(base + i * WAVE + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok &= (unsigned)(g[i] >> 32) == tag;
-            }
-            if (__all(ok)) {
-                extra = (unsigned)g[6];
-                a = __longlong_as_double((long long)((g[0] & 0xffffffffu) | (g[1] << 32)));
-                b = __longlong_as_double((long long)((g[2] & 0xffffffffu) | (g[3] << 32)));
-                c = __longlong_as_double((long long)((g[4] & 0xffffffffu) | (g[5] << 32)));
-                return true;
-            }
+            granules_issue(base, lane, g, row);
+            if (granules_accept(g, tag, a, b, c, extra, row)) return true;
         }
         {
             if ((spins & 31) == 31) {
@@ -140,8 +159,10 @@ struct Recompute {
 // memory, starting from the y state `resume` when the band is not the first.  A template parameter, not a run-time test: the
 // extra scalars alone (11 more SGPR spills in a kernel that already spills) cost the batch sweep 9 % when they were arguments
 // of the one instance.
+// Three wavefronts per SIMD (168 VGPRs) are asked for where the instance fits them: left to itself the scheduler gives up that tier for a
+// register or two at the tile store and then spreads to 190 (the re-run forms and the diagnostic build need two tiers anyway).
 template <bool STAMP, typename PX = float, int MODE = 0, bool BANDED = false>
-__global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w, int h, int pitch, VVK k,
+__global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(float* __restrict__ data, int w, int h, int pitch, VVK k,
                                                  const double* __restrict__ state_x, long lines, double* __restrict__ state_y,
                                                  Wavefront wf, Recompute rc, typename CollapseSrc<PX, MODE == 2>::type pa) {
     __shared__ __attribute__((aligned(16))) float tile[TS * TP];
@@ -249,6 +270,14 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
             }
         };
         bool next_zero = false, spec = true;
+        unsigned sent = 0;  // hand-offs of this band: full ones in the low half, zero markers in the high half (NC < 65536)
+        // Level-0 mask blur, recorded instead of stored.  Below the first band every input of a column is the one constant rowv, and
+        // the causal sweep started at that constant's fixed point (u = rowv / sumsq): in float the outputs repeat the first one (row
+        // 0 of the plane, which band 0 always stores) although the double state may cycle in its last bit -- so the equality is
+        // tested, tile by tile, on the outputs themselves.  The flag of such a tile then means "every sample equals row 0 of its
+        // column"; +0 everywhere is the case rowv = +0.  k_vv_y_bwd_dec substitutes the row-0 value.
+        const bool fill_rows = !BANDED && const_rows && wf.mask_l0 == 2;
+        unsigned recorded = 0;
         if (!const_rows) {
             next_zero = fetch_tile(wf.NC - 1);
             gather_tile(wf.NC - 1, next_zero);
@@ -258,10 +287,10 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
             const bool tile_zero = next_zero;  // the tile now going to LDS holds +0 only
             u64* slot = wf.yg + ((size_t)p * wf.NC + C) * WF_GRAN * WAVE;
             u64 early[WF_GRAN];
-            // speculation is dropped while it fails (the band above is not ahead: the seven loads would only be repeated
+            // speculation is dropped while it fails (the band above is not ahead: the loads would only be repeated
             // by the poll) and probed again every fourth tile
             const bool early_on = R > 0 && wf.early_read && (spec || (C & 3) == 0);
-            if (early_on) granules_issue(slot, lane, early);  // ahead of the prefetch below (in-order return)
+            if (early_on) granules_issue(slot, lane, early, pass_row);  // ahead of the prefetch below (in-order return)
             double f1 = n1, f2 = n2, f3 = n3;  // this tile's checkpoint (MODE 1/2)
             if (!const_rows) {
                 if constexpr (MODE == 2)
@@ -364,19 +393,28 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
                 u1 = u2 = u3 = (double)colp[0] / k.sumsq;  // CImg.h:34909
                 rowbits = __float_as_uint(colp[0]);     // the x-blurred row (mask plane: identical for every y)
             } else {
-                const bool hit = early_on && granules_accept(early, (wf.epoch << 12) | (unsigned)R, u1, u2, u3, rowbits);
+                const bool hit = early_on && granules_accept(early, (wf.epoch << 12) | (unsigned)R, u1, u2, u3, rowbits, pass_row);
                 if (early_on) spec = hit;
-                if (!hit && !granules_consume(slot, lane, (wf.epoch << 12) | (unsigned)R, wf.abort, wf.sticky, wf.spin_limit, u1, u2, u3, rowbits)) {
+                if (!hit && !granules_consume(slot, lane, (wf.epoch << 12) | (unsigned)R, wf.abort, wf.sticky, wf.spin_limit, u1, u2, u3, rowbits, pass_row)) {
                     dead = true;
                     break;
                 }
             }
             stamp(3);  // y state wait
             const float rowv = __uint_as_float(rowbits);
+            unsigned fillbits = 0;  // what the outputs are compared with: +0, or (fill_rows) the first causal output for rowv
+            if (fill_rows) {  // the operations band 0 performs for its row 0
+                const double u = (double)rowv / k.sumsq;
+                double v0 = (double)rowv;
+                v0 += u * k.f1;
+                v0 += u * k.f2;
+                v0 += u * k.f3;
+                fillbits = __float_as_uint((float)v0);
+            }
             // rows that are all the passed-down row: below the first band of an implicit mask plane -- and, in a BANDED launch, in
             // the first band too: it starts y0 rows into the plane, so its last rows lie beyond the 64 rows the x sweeps generate
             const bool y_const = const_rows || (BANDED && pass_row);
-            unsigned ynz = 0;  // OR of the bit patterns of this lane's column after the sweep
+            unsigned ynz = 0;  // OR of the bit patterns of this lane's column after the sweep, each XOR fillbits
             const double iplus_y = y_const ? (double)rowv : (double)colp[(nrows - 1) * TP];  // last band only (CImg.h:34906)
             // the same for the y sweep: a tile of +0 under a +0 state stays +0 (only the columns that exist are asked)
             const bool y_idle = x_idle && __ballot(lane < ncols && (__double_as_longlong(u1) | __double_as_longlong(u2) |
@@ -401,7 +439,7 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
                         v0 += u2 * k.f2;
                         v0 += u3 * k.f3;
                         ys[u] = (float)v0;
-                        ynz |= __float_as_uint(ys[u]);
+                        ynz |= __float_as_uint(ys[u]) ^ fillbits;
                         u3 = u2;
                         u2 = u1;
                         u1 = v0;
@@ -415,7 +453,7 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
                         v0 += u2 * k.f2;
                         v0 += u3 * k.f3;
                         colp[j * TP] = (float)v0;
-                        ynz |= __float_as_uint(colp[j * TP]);
+                        ynz |= __float_as_uint(colp[j * TP]) ^ fillbits;
                         u3 = u2;
                         u2 = u1;
                         u1 = v0;
@@ -423,7 +461,7 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
                 }
             }
             if (R < wf.NR - 1)
-                granules_publish(slot, lane, (wf.epoch << 12) | (unsigned)(R + 1), u1, u2, u3, pass_row ? rowbits : 0u);
+                sent += granules_publish(slot, lane, ncols, (wf.epoch << 12) | (unsigned)(R + 1), u1, u2, u3, rowbits, pass_row) ? 0x10000u : 1u;
             else {  // last band: the state the anticausal y sweep starts from ([4][planes][pitch], as k_vv_y_fwd leaves it)
                 const size_t n = (size_t)wf.NP * pitch, i = (size_t)p * pitch + c0 + lane;
                 state_y[i] = u1;
@@ -436,12 +474,20 @@ __global__ __launch_bounds__(64) void k_vv_xbyf(float* __restrict__ data, int w,
             bool out_zero = false;
             if (wf.zt.flags) {  // the y sweep ran over every column of the tile; columns >= w hold whatever the fetch left: not counted
                 out_zero = __ballot(lane < ncols && ynz != 0) == 0;
+                // band 0 of a plane whose flags mean "repeats row 0" is always stored: it holds that row
+                if (!BANDED && pass_row && R == 0 && wf.mask_l0 == 2) out_zero = false;
                 if (lane == 0) wf.zt.flags[wf.zt.index(p, R, C)] = out_zero ? 1 : 0;
+                if (fill_rows && out_zero) ++recorded;
             }
             if (!out_zero) tile_store_rows(base, pitch, c0, lane, tile, nrows);  // a partial last band must not touch the next plane's rows
             __syncthreads();  // the tile buffer is refilled next
             stamp(5);  // store
         }
+        if (lane == 0 && sent != 0) {
+            atomicAdd((u64*)(wf.sticky + 2), (u64)(sent & 0xffffu));
+            atomicAdd((u64*)(wf.sticky + 4), (u64)(sent >> 16));
+        }
+        if (lane == 0 && recorded != 0) atomicAdd((u64*)(wf.sticky + 6), (u64)recorded);
     }
     if (STAMP && lane == 0)
         for (int i = 0; i < 8; ++i) wf.dbg[(size_t)blockIdx.x * 8 + i] = seg[i];

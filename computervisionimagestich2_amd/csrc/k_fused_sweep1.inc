@@ -207,13 +207,14 @@ __global__ __launch_bounds__(XY_THREADS, 3) void k_vv_xby_m(float* __restrict__ 
         } else if (wave == 3) {
             // ---- the storer ------------------------------------------------------------------------------------------------
             int ydone = 0;
+            unsigned sent = 0;  // hand-offs of this band: full ones in the low half, zero markers in the high half (as k_vv_xbyf)
             const bool last_band = R == wf.NR - 1;
             for (int j = 0; j < NC; ++j) {
                 wait_ge(&c_y, ydone, j + 1);
                 const XYState& so = st_out[j & 1];
                 const int c0 = (NC - 1 - j) * TS;
                 if (!last_band)
-                    granules_publish(slot_of(j), lane, tag_out, so.u[0][lane], so.u[1][lane], so.u[2][lane], so.extra[lane]);
+                    sent += granules_publish(slot_of(j), lane, min(TS, w - c0), tag_out, so.u[0][lane], so.u[1][lane], so.u[2][lane], so.extra[lane], pass_row) ? 0x10000u : 1u;
                 else {  // the state the anticausal y sweep starts from ([4][planes][pitch], as k_vv_y_fwd leaves it)
                     const size_t n = (size_t)wf.NP * pitch, i = (size_t)p * pitch + c0 + lane;
                     state_y[i] = so.u[0][lane];
@@ -243,33 +244,45 @@ __global__ __launch_bounds__(XY_THREADS, 3) void k_vv_xby_m(float* __restrict__ 
                 wr(&c_stored, j + 1);
                 stamp(j);
             }
+            if (lane == 0 && sent != 0) {
+                atomicAdd((u64*)(wf.sticky + 2), (u64)(sent & 0xffffu));
+                atomicAdd((u64*)(wf.sticky + 4), (u64)(sent >> 16));
+            }
         } else if (R > 0) {
             // ---- the courier: the y state of the band above, one tile ahead of the poll it is needed by ------------------------------
-            int ydone = 0;
-            u64 g[2][WF_GRAN];
-            granules_issue(slot_of(0), lane, g[0]);
-            bool alive = true;
-            for (int j0 = 0; j0 < NC; j0 += 2) {
+            // (a plane that passes the mask row down runs its own copy of the loop: the fifth granule's load is not conditional in either)
+            auto courier = [&](auto ROW) {
+                constexpr bool row = decltype(ROW)::value;
+                int ydone = 0;
+                u64 g[2][WF_GRAN];
+                granules_issue(slot_of(0), lane, g[0], row);
+                bool alive = true;
+                for (int j0 = 0; j0 < NC; j0 += 2) {
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int j = j0 + b;
-                    granules_issue(slot_of(min(j + 1, NC - 1)), lane, g[1 - b]);  // unconditional (past the end: read again, never used)
-                    if (j < NC) {
-                        double a = 0, bb = 0, c = 0;
-                        unsigned extra = 0;
-                        if (alive && !granules_accept(g[b], tag_in, a, bb, c, extra)) {
-                            alive = granules_consume(slot_of(j), lane, tag_in, wf.abort, wf.sticky, wf.spin_limit, a, bb, c, extra, true);
-                            if (!alive) wr(&s_dead, 1);  // the band runs out on zeros, the workgroup ends after it
+                    for (int b = 0; b < 2; ++b) {
+                        const int j = j0 + b;
+                        granules_issue(slot_of(min(j + 1, NC - 1)), lane, g[1 - b], row);  // unconditional (past the end: read again, never used)
+                        if (j < NC) {
+                            double a = 0, bb = 0, c = 0;
+                            unsigned extra = 0;
+                            if (alive && !granules_accept(g[b], tag_in, a, bb, c, extra, row)) {
+                                alive = granules_consume(slot_of(j), lane, tag_in, wf.abort, wf.sticky, wf.spin_limit, a, bb, c, extra, row, true);
+                                if (!alive) wr(&s_dead, 1);  // the band runs out on zeros, the workgroup ends after it
+                            }
+                            wait_ge(&c_y, ydone, j - XY_IN + 1);  // the y chain has left tile j - XY_IN: its slot is free
+                            XYState& si = st_in[j % XY_IN];
+                            si.u[0][lane] = a, si.u[1][lane] = bb, si.u[2][lane] = c;
+                            si.extra[lane] = extra;
+                            wr(&c_in, j + 1);
+                            stamp(j);
                         }
-                        wait_ge(&c_y, ydone, j - XY_IN + 1);  // the y chain has left tile j - XY_IN: its slot is free
-                        XYState& si = st_in[j % XY_IN];
-                        si.u[0][lane] = a, si.u[1][lane] = bb, si.u[2][lane] = c;
-                        si.extra[lane] = extra;
-                        wr(&c_in, j + 1);
-                        stamp(j);
                     }
                 }
-            }
+            };
+            if (pass_row)
+                courier(std::true_type{});
+            else
+                courier(std::false_type{});
         }
         __syncthreads();  // the band is done: counters and s_q are written again
     }

@@ -689,12 +689,15 @@ __global__ __launch_bounds__(64) void k_vv_y_bwd(float* __restrict__ data, int h
 // its neighbour; its 128 columns then lie in up to three tiles of the zero-tile flags.
 // XCH (even widths; stitch_band_reduce_y_bwd_cols): the launch covers source columns x_base .. x_base + 128 * gridDim.x - 1 and
 // `state` / `resume` / `state_out` are the chunk's own arrays, [k][planes][128 * gridDim.x] (as k_vv_y_fwd<true>).
+// fill_l0 (a plan's fused level 0 with the implicit mask; k_vv_xbyf, Wavefront::mask_l0 == 2): on the planes y % 7 == 6 a flagged tile was
+// not all +0 but a repetition of the plane's row 0, which is always stored: the row a flagged lane re-reads IS that row, and the lane keeps
+// what it read instead of taking zeros (no register holds the fill values: the ROWZ instances sit at 127 of 128 VGPRs for four wavefronts).
 template <bool ROWZ = false, int NST = YST, bool ZT = true, bool ODD = false, bool XCH = false>
 __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ data, int w, int h, int pitch, size_t ps,
                                                       VVK k, const double* __restrict__ state, float* __restrict__ dst,
                                                       int w2, int h2, int dpitch, size_t dps, ZeroTiles zt,
                                                       const double* __restrict__ resume, double* __restrict__ state_out, int wh, int wh2,
-                                                      int x_base = 0) {
+                                                      int x_base = 0, int fill_l0 = 0) {
     static_assert(!(XCH && ODD), "column chunks: even widths");
     // wh, wh2: the heights the decimation's overlap weights are taken from (CImg.h:29557-29575 weights by the LEVEL's
     // heights): h, h2 for a whole level; for a row band of a split pair the level's, not the band's (the quotient is the same
@@ -751,6 +754,8 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
     };
     auto chunk_zero = [&](int chunk) { return ROWZ ? false : zero_at(chunk * YCH); };
     // ZT = false: rows h-1, h-2, ... 0 are loaded strictly in this order (rc counts them); past row 0 the offset stays there
+    const bool fill_on = ZT && zt_on && fill_l0 != 0 && blockIdx.y % 7 == 6;  // workgroup-uniform
+    const int dummy = fill_on ? 0 : h - 1;  // the row a flagged lane re-reads: on a fill plane the very row it stands for
     const __amdgpu_buffer_rsrc_t rsp = plane_rsrc(data + blockIdx.y * ps, ps);
     const unsigned xo = (col_live ? (unsigned)x : 0u) * 4u, pitch_b = (unsigned)pitch * 4u;
     unsigned next = (unsigned)(h - 1) * pitch_b;  // byte offset of the next row to load
@@ -763,8 +768,10 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
         } else {
             if (ROWZ) zero = zero_at(rc);
             const int r = rc < h ? rc : h - 1, y = h - 1 - r;
-            const f2 v = *reinterpret_cast<const f2*>(p + (size_t)(zero ? h - 1 : y) * pitch);
-            return zero ? f2{0.f, 0.f} : v;
+            const f2 v = *reinterpret_cast<const f2*>(p + (size_t)(zero ? dummy : y) * pitch);
+            // (as a mask on the bits, not a select between two values: 131 -> 124 VGPRs, ROWZ 127 -> 118)
+            const unsigned keep = (zero && !fill_on) ? 0u : ~0u;
+            return f2{__uint_as_float(__float_as_uint(v.x) & keep), __uint_as_float(__float_as_uint(v.y) & keep)};
         }
     };
     if (wave == 0) {
@@ -795,7 +802,7 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
                                           (unsigned long long)__double_as_longlong(s.a3) | (unsigned long long)__double_as_longlong(s.b1) |
                                           (unsigned long long)__double_as_longlong(s.b2) | (unsigned long long)__double_as_longlong(s.b3) |
                                           (unsigned long long)(__float_as_uint(first.x) | __float_as_uint(first.y));
-            const bool allz0 = __all(mine_all && sb == 0ull);
+            const bool allz0 = __all(mine_all && sb == 0ull) && !fill_on;  // (on a fill plane a flag stands for row 0, not for zeros)
             if (lane == 0) s_allz = allz0 ? 1 : 0;
         }
         __syncthreads();

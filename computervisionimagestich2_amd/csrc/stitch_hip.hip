@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "stitch.h"
+#include "stitch_handoff.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -272,7 +273,8 @@ struct Level {
 
 constexpr int CO_LDS_BYTES = 144 * 1024;  // dynamic LDS k_coarse_lds may take (160 KB per CU, 15 KB of tables beside it)
 constexpr int WF_CTRL_WORDS = 4 * 16 + 16;  // band-queue heads of up to 4 levels (64 bytes apart) + the abort word
-constexpr int WF_STICKY_WORDS = 16;         // behind them, outside what a launch sequence clears: the plan's count of timed-out waits
+constexpr int WF_STICKY_WORDS = 16;         // behind them, outside what a launch sequence clears: the plan's count of timed-out waits and,
+                                            // from word 2, its three 64-bit hand-off counts (stitch_plan_handoff_counts)
 
 struct ProfRec {
     int stage, level;
@@ -477,7 +479,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             const size_t gran_words = (size_t)wf.NP * wf.NC * WF_GRAN * WAVE;
             k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(p->wf_yg, gran_words);
             wf.epoch = 1;
-            wf.mask_l0 = mk.enabled;
+            wf.mask_l0 = mk.enabled ? (zt.flags ? 2 : 1) : 0;  // 2: the mask blur below the first band is recorded in the flags, not stored
             wf.zt = zt;
             wf.early_read = p->wf_early_read;
             const long ntiles = (long)wf.NP * wf.NR;  // one persistent wavefront per row band
@@ -505,18 +507,19 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             }
             StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
             dim3 g((a.pitch + YCOLS - 1) / YCOLS, np);
+            const int fill_l0 = wf.mask_l0 == 2;  // flagged tiles of the mask planes repeat the plane's row 0 (k_vv_xbyf)
             if ((a.w & 1) == 0 && !p->no_fuse) {
                 if (rowz)
-                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
+                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
                 else
-                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
+                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
                 decimated = true;
             } else if (odd_dec) {  // odd width: three-tap x decimation, workgroups overlap by two columns
                 const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
                 if (rowz)
-                    k_vv_y_bwd_dec<true, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
+                    k_vv_y_bwd_dec<true, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
                 else
-                    k_vv_y_bwd_dec<false, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
+                    k_vv_y_bwd_dec<false, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
                 decimated = true;
             } else
                 k_vv_y_bwd<<<g, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, state_y, nullptr, nullptr);
@@ -2014,6 +2017,18 @@ int stitch_plan_status(stitch_plan* p, stitch_seam* seam_out) { return stitch_pl
 int stitch_plan_set_handoff_spin_limit(stitch_plan* p, unsigned polls) {
     if (!p) return fail(STITCH_ERR_ARG, "null plan");
     p->wf_spin_limit = polls;
+    return STITCH_OK;
+}
+
+int stitch_plan_handoff_counts(stitch_plan* p, uint64_t out[3]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    out[0] = out[1] = out[2] = 0;
+    // the 64-bit words behind the sticky count (Wavefront::sticky): like it, no launch sequence clears them
+    if (p->wf_ctrl) HIPCHK(hipMemcpy(out, p->wf_ctrl + WF_CTRL_WORDS + 2, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return STITCH_OK;
 }
 
