@@ -608,28 +608,36 @@ def sift(gray, opts=None, kp_cap=8192, feat_cap=None):
     return dict(kp=kp[:nk].copy(), fkp=fkp[:nf].copy(), angle=ang[:nf].copy(), desc=desc[:nf].copy(), status=status)
 
 
-def dev_sift_many(images, opts=None, kp_cap=8192, feat_cap=None):
+def dev_sift_many(images, opts=None, kp_cap=8192, feat_cap=None, slack=0, fill=None):
     """Many gray frames -- (H, W) uint8 or float32 device tensors with contiguous rows, sizes may differ -- in one launch sequence
-    per 16 frames and octave on torch's current stream (no synchronisation).  Returns a list of dicts of device tensors: kp
-    ((kp_cap, 8) int32: the StitchSiftKeypoint records, columns 4..7 are float32 bits), fkp, angle, desc, counts ((2,) int32) and
-    status ((4,) int32); sift_unpack turns one into host arrays."""
+    per 16 frames and octave on torch's current stream (no synchronisation).  kp_cap and feat_cap (default 2 * kp_cap) are one
+    number for every frame or a sequence with one per frame.  Returns a list of dicts of device tensors: kp ((kp_cap, 8) int32:
+    the StitchSiftKeypoint records, columns 4..7 are float32 bits), fkp, angle, desc, counts ((2,) int32) and status ((4,)
+    int32); sift_unpack turns one into host arrays.  The buffers are `slack` records longer than the capacities and, with `fill`,
+    hold that byte everywhere before the call (for tests: nothing may be written at or beyond a capacity)."""
     import torch
     n = len(images)
-    feat_cap = 2 * kp_cap if feat_cap is None else feat_cap
+    kcaps = [int(k) for k in kp_cap] if hasattr(kp_cap, "__len__") else [int(kp_cap)] * n
+    fcaps = [2 * k for k in kcaps] if feat_cap is None else [int(k) for k in feat_cap] if hasattr(feat_cap, "__len__") else [int(feat_cap)] * n
+    if len(kcaps) != n or len(fcaps) != n:
+        raise ValueError("one capacity per frame")
     outs, descs = [], []
-    for t in images:
+    for t, kc, fc in zip(images, kcaps, fcaps):
         if not (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.dtype in (torch.uint8, torch.float32)):
             raise ValueError("expected (H, W) uint8 or float32 device tensors with contiguous rows")
         dev = t.device
-        o = dict(kp=torch.empty((max(kp_cap, 1), 8), dtype=torch.int32, device=dev),
-                 fkp=torch.empty(max(feat_cap, 1), dtype=torch.int32, device=dev),
-                 angle=torch.empty(max(feat_cap, 1), dtype=torch.float64, device=dev),
-                 desc=torch.empty((max(feat_cap, 1), DESCRIPTOR_DIM), dtype=torch.float32, device=dev),
+        o = dict(kp=torch.empty((max(kc, 1) + slack, 8), dtype=torch.int32, device=dev),
+                 fkp=torch.empty(max(fc, 1) + slack, dtype=torch.int32, device=dev),
+                 angle=torch.empty(max(fc, 1) + slack, dtype=torch.float64, device=dev),
+                 desc=torch.empty((max(fc, 1) + slack, DESCRIPTOR_DIM), dtype=torch.float32, device=dev),
                  head=torch.empty(2 + SIFT_STATUS, dtype=torch.int32, device=dev))
+        if fill is not None:
+            for k in ("kp", "fkp", "angle", "desc"):
+                o[k].view(torch.uint8).fill_(int(fill))
         o["counts"], o["status"] = o["head"][:2], o["head"][2:]
         outs.append(o)
         descs.append(SiftDesc(_dp(t), t.shape[1], t.shape[0], t.stride(0) * t.element_size(), int(t.dtype == torch.float32),
-                              _dp(o["kp"]), int(kp_cap), int(feat_cap), _dp(o["fkp"]), _dp(o["angle"]), _dp(o["desc"]),
+                              _dp(o["kp"]), kc, fc, _dp(o["fkp"]), _dp(o["angle"]), _dp(o["desc"]),
                               _dp(o["head"]), o["head"].data_ptr() + 8))
     arr = (SiftDesc * max(n, 1))(*descs)
     op = opts if opts is not None else SiftOpts()

@@ -627,7 +627,11 @@ typedef struct stitch_sift_desc {
                                     * found, octaves run}.  On overflow the first kp_cap keypoints and feat_cap rows are written,
                                     * nothing is truncated silently, and the other frames of the call are complete.  Feature rows
                                     * are counted over the keypoints that were written: when the keypoints overflow, call again
-                                    * with kp_cap >= status[1] to learn the number of rows.                                   */
+                                    * with kp_cap >= status[1] to learn the number of rows.  Nothing is written at or beyond
+                                    * record kp_cap of keypoints or row feat_cap of feat_kp / feat_angle / feat_desc.  "Octaves
+                                    * run" counts the octaves of this frame that had at least one pixel: min(octaves asked for
+                                    * or given by the automatic rule, floor(log2(min(width, height))) + 1).  The reference goes
+                                    * on through the remaining, empty octaves and finds nothing in them.                      */
 } stitch_sift_desc;
 /* Many frames, which may differ in size, in one launch sequence per 16 frames and octave; enqueued on `stream` with
  * stream-ordered scratch, no host synchronisation.  A frame too small for the octaves asked for runs down to 1 x 1 octaves

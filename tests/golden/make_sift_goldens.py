@@ -16,7 +16,17 @@ Runs only where oracle/_ref/libref_hotpath.so has been built; it uses nothing bu
     sift_synth.npz   a 300 x 401 noise image under (auto octaves, 3 levels), (3, 5), (2, 1) and a non-zero peak threshold, a
                      constant image, and crops of 23 x 37, 17 x 9 and 64 x 65: kp, fkp, angle, desc in full per case
 
-    python tests/golden/make_sift_goldens.py
+    sift_edges.npz   `dense` (760 x 600: anisotropic Gaussian bumps of both signs on a jittered 6 px grid over mid-grey) under the
+                     defaults and automatic octaves, and its crops of sift_ref.EDGE_CROPS (380 x 300 down to 1 x 1) under both, the
+                     two shallow ones and 200 x 160 under octaves = 6 as well
+    sift_edges2.npz  `strip` (the same construction at 4096 x 20) and its transpose, `squares` (80 x 80, axis-aligned squares)
+                     under the defaults and (auto octaves, 3 levels), and `f32` (a crop of dense scaled and jittered to negative,
+                     fractional and > 255 float32 samples)
+                     per case of sift_ref.EDGE_CASES: kp, fkp, angle, oct (the octaves the reference ran), desc_crc, desc_sha,
+                     and desc in full up to sift_ref.EDGE_FULL_ROWS rows; the images are stored (their generator uses exp)
+
+    python tests/golden/make_sift_goldens.py          everything
+    python tests/golden/make_sift_goldens.py edges    sift_edges*.npz only
 """
 import ctypes as C
 import os
@@ -43,6 +53,67 @@ def synth_images():
                 c64x65=noise[100:165, 100:164].copy())
 
 
+EDGE_SEED = 20261018
+
+
+def bumps(rng, w, h, spacing=6, jitter=2.0):
+    """Mid-grey plus one anisotropic, rotated Gaussian bump of either sign per cell of a jittered grid."""
+    img = np.full((h, w), 128.0)
+    for gy in range(spacing // 2, h + spacing // 2, spacing):
+        for gx in range(spacing // 2, w + spacing // 2, spacing):
+            cx, cy = gx + rng.uniform(-jitter, jitter), gy + rng.uniform(-jitter, jitter)
+            su, sv, th = rng.uniform(1.2, 3.0), rng.uniform(1.2, 3.0), rng.uniform(0, np.pi)
+            amp = rng.uniform(60, 120) * (1 if rng.random() < 0.5 else -1)
+            r = 12
+            x0, x1, y0, y1 = max(int(cx) - r, 0), min(int(cx) + r + 1, w), max(int(cy) - r, 0), min(int(cy) + r + 1, h)
+            if x0 >= x1 or y0 >= y1:
+                continue
+            yy, xx = np.mgrid[y0:y1, x0:x1]
+            u = (xx - cx) * np.cos(th) + (yy - cy) * np.sin(th)
+            v = -(xx - cx) * np.sin(th) + (yy - cy) * np.cos(th)
+            img[y0:y1, x0:x1] += amp * np.exp(-0.5 * ((u / su) ** 2 + (v / sv) ** 2))
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def edge_images():
+    rng = np.random.default_rng(EDGE_SEED)
+    dense = bumps(rng, 760, 600)
+    strip = bumps(rng, 4096, 20)
+    squares = np.full((80, 80), 110, np.uint8)
+    for k, (cx, cy) in enumerate((x, y) for y in (13, 40, 66) for x in (14, 39, 66)):  # apart, so that each keeps its symmetry
+        r = int(rng.integers(2, 9))
+        squares[cy - r:cy + r + 1, cx - r:cx + r + 1] = 215 if k % 2 else 30
+    x0, y0, w, h = R.EDGE_CROPS["c200x160"]
+    f32 = ((dense[y0:y0 + h, x0:x0 + w].astype(np.float64) - 128) * 3.7 + rng.random((h, w))).astype(np.float32)
+    return dict(dense=dense, strip=strip, squares=squares, f32=f32)
+
+
+def edges(L):
+    imgs = edge_images()
+    Z = [{"img_dense": imgs["dense"]}, {f"img_{k}": imgs[k] for k in ("strip", "squares", "f32")}]
+    for name, image, o in R.EDGE_CASES:
+        z = Z[R.EDGE_FILES.index(R.edge_file(image))]
+        img = R.edge_image(z, image)
+        r = R.reference_sift(L, img, **o)
+        z[f"{name}_kp"], z[f"{name}_fkp"], z[f"{name}_angle"], z[f"{name}_oct"] = r["kp"], r["fkp"], r["angle"], np.int32(r["octaves"])
+        z[f"{name}_desc_crc"], z[f"{name}_desc_sha"] = R.row_crcs(r["desc"]), np.array(R.sha(r["desc"]))
+        if len(r["desc"]) <= R.EDGE_FULL_ROWS:
+            z[f"{name}_desc"] = r["desc"]
+        per = np.bincount(r["kp"]["o"], minlength=1) if len(r["kp"]) else []
+        print(f"{name}: {img.shape[1]} x {img.shape[0]} {img.dtype} {o}: {r['octaves']} octaves, keypoints {list(per)}, "
+              f"{len(r['desc'])} features, most angles {np.bincount(r['fkp']).max() if len(r['fkp']) else 0}")
+    for z, f in zip(Z, R.EDGE_FILES):
+        np.savez_compressed(os.path.join(HERE, f), **z)
+
+
+def sizes():
+    for f in sorted(os.listdir(HERE)):
+        if f.startswith("sift_") and f.endswith(".npz"):
+            size = os.path.getsize(os.path.join(HERE, f))
+            assert size < 1 << 20, (f, size)
+            print(f, size)
+
+
 def projected_gray(Ref, path):
     rgb = Ref.load_bmp(path)
     proj = np.empty_like(rgb)
@@ -55,6 +126,9 @@ def projected_gray(Ref, path):
 def main():
     from oracle_lib import Reference
     L = R.load_reference()
+    if sys.argv[1:] == ["edges"]:
+        edges(L)
+        return sizes()
     Ref = Reference()
     Z = {"expn": R.reference_expn(L)}
     for S in (1, 2, 3, 5):
@@ -90,11 +164,8 @@ def main():
         S[f"{name}_kp"], S[f"{name}_fkp"], S[f"{name}_angle"], S[f"{name}_desc"] = r["kp"], r["fkp"], r["angle"], r["desc"]
         print(f"{name}: {imgs[img].shape[1]} x {imgs[img].shape[0]} {o}: {len(r['kp'])} keypoints, {len(r['desc'])} features")
     np.savez_compressed(os.path.join(HERE, "sift_synth.npz"), **S)
-    for f in sorted(os.listdir(HERE)):
-        if f.startswith("sift_") and f.endswith(".npz"):
-            size = os.path.getsize(os.path.join(HERE, f))
-            assert size < 1 << 20, (f, size)
-            print(f, size)
+    edges(L)
+    sizes()
 
 
 if __name__ == "__main__":

@@ -3,7 +3,8 @@
 // order, so that they can be compared with the recorded fixtures on a machine without a GPU.  What the kernels add on top
 // (which lane takes which sample, the ballot / scan compaction, the ordered histogram walk) is pinned by tests/test_gpu_sift.py.
 //   sift_emulate <in> <out>
-//   in : int32 w, h, octaves, levels, dump; double peak, edge, norm, magnif, window; w * h bytes (gray)
+//   in : int32 w, h, octaves, levels, flags (1: dump, 2: the image is float32); double peak, edge, norm, magnif, window; w * h
+//        bytes (gray) or floats
 //   out: records {int32 tag, int32 octave, int64 bytes, payload}: 1 Gaussian levels, 2 DoG levels, 3 gradient planes (only
 //        with dump), 4 candidates (x, y, s int32), 5 keypoints (8 x 4 bytes), 6 feature keypoint index (int32, per frame),
 //        7 angles (double), 8 descriptors (128 float); 9 = filter taps (double sigma, int32 W, pad, 2W+1 floats) per new
@@ -63,11 +64,12 @@ int main(int argc, char** argv) {
     int32_t hd[5];
     double th[5];
     if (fread(hd, 4, 5, f) != 5 || fread(th, 8, 5, f) != 5) return 2;
-    const int W0 = hd[0], H0 = hd[1], S = hd[3], dump = hd[4];
+    const int W0 = hd[0], H0 = hd[1], S = hd[3], dump = hd[4] & 1, is_f32 = hd[4] & 2;
     const int noct = hd[2] < 0 ? sift_auto_octaves(W0, H0) : hd[2];
     const size_t ls = (size_t)W0 * H0;
-    std::vector<unsigned char> gray(ls);
-    if (fread(gray.data(), 1, ls, f) != ls) return 2;
+    std::vector<unsigned char> gray(is_f32 ? 0 : ls);
+    std::vector<float> grayf(is_f32 ? ls : 0);
+    if (is_f32 ? fread(grayf.data(), 4, ls, f) != ls : fread(gray.data(), 1, ls, f) != ls) return 2;
     fclose(f);
     g_out = fopen(argv[2], "wb");
     if (!g_out) return 2;
@@ -80,7 +82,7 @@ int main(int argc, char** argv) {
     tab[257] = 0;  // as k_sift_table
     record(10, 0, tab, 257 * sizeof(double));
     std::vector<float> oct((S + 3) * ls), tmp(ls), grad(2 * (size_t)S * ls), dog;
-    for (size_t i = 0; i < ls; ++i) oct[i] = (float)gray[i];
+    for (size_t i = 0; i < ls; ++i) oct[i] = is_f32 ? grayf[i] : (float)gray[i];  // k_sift_load
     std::vector<SiftKeypoint> all_kp;
     std::vector<int32_t> f_kp;
     std::vector<double> f_ang;

@@ -30,6 +30,55 @@ SYNTH_CASES = [  # name, image, options
     ("s64x65", "c64x65", dict()),
 ]
 
+# tests/golden/sift_edges*.npz.  Every crop is a rectangle of the stored image `dense`, so no test has to regenerate an image.
+EDGE_CROPS = {  # name: (x0, y0, w, h) in `dense`
+    "c380x300": (190, 150, 380, 300), "c200x160": (300, 200, 200, 160), "c64x63": (411, 277, 64, 63), "c200x24": (96, 333, 200, 24),
+    "c150x9": (505, 41, 150, 9), "c15x65": (77, 419, 15, 65), "c3x2": (250, 250, 3, 2), "c1x1": (33, 77, 1, 1),
+}
+EDGE_CASES = (  # name, image, options
+    [("dense", "dense", dict()), ("dense_auto", "dense", dict(octaves=-1))]
+    + [(c, c, dict()) for c in EDGE_CROPS] + [(c + "_auto", c, dict(octaves=-1)) for c in EDGE_CROPS]
+    + [("c200x24_o6", "c200x24", dict(octaves=6)), ("c150x9_o6", "c150x9", dict(octaves=6)),
+       ("c200x160_o6", "c200x160", dict(octaves=6)),
+       ("strip", "strip", dict()), ("stripT", "stripT", dict()),
+       ("squares", "squares", dict()), ("squares_l3", "squares", dict(levels=3, octaves=-1)), ("f32", "f32", dict())])
+EDGE_FILES = ("sift_edges.npz", "sift_edges2.npz")  # `dense` and its crops; strips, squares, f32
+EDGE_FULL_ROWS = 64  # descriptors are stored in full up to this many rows; every case has the row CRCs and the SHA-256
+
+MIXED_CALL = ["c380x300", "c64x63", "dense", "c200x24", "c1x1", "c3x2", "c200x160"]  # one call of test_gpu_sift_edges.py, octaves = -1
+GRID_LIMIT = 2048  # kSiftWaveGrid of stitch_sift.inc: workgroups of the per-keypoint kernels
+
+
+def split_keypoint(z, prefix):
+    """(keypoint, its first row) of the first keypoint with two or more angles that is not the frame's first: a feat_cap of
+    first row + 1 cuts between two of its angles."""
+    fkp = z[prefix + "fkp"]
+    n = np.bincount(fkp)
+    k = int(np.nonzero(n[1:] >= 2)[0][0]) + 1
+    return k, int(np.searchsorted(fkp, k))
+
+
+def edge_file(image):
+    return EDGE_FILES[0] if image == "dense" or image in EDGE_CROPS else EDGE_FILES[1]
+
+
+def edge_image(z, image):
+    """The image of an edge case from its fixture file z (np.load of edge_file(image))."""
+    if image in EDGE_CROPS:
+        x0, y0, w, h = EDGE_CROPS[image]
+        return np.ascontiguousarray(z["img_dense"][y0:y0 + h, x0:x0 + w])
+    if image == "stripT":
+        return np.ascontiguousarray(z["img_strip"].T)
+    return z["img_" + image]
+
+
+def pixel_octaves(w, h, octaves):
+    """How many of `octaves` octaves (negative: VLFeat's rule) of a w x h frame have at least one pixel: status[3] of stitch.h."""
+    m = min(w, h)
+    if octaves < 0:
+        octaves = max(m.bit_length() - 1 - 3, 1)
+    return min(octaves, m.bit_length())
+
 
 def opts_of(**kw):
     o = dict(DEFAULTS)
@@ -69,14 +118,17 @@ def build_emulator(directory):
 
 
 def emulate(exe, gray, directory, dump=False, **kw):
-    """Runs the emulation on a (h, w) uint8 image.  Returns a dict: kp (KP_DTYPE, all octaves), fkp, angle, desc, cand {o: (m, 3)},
+    """Runs the emulation on a (h, w) uint8 image, or a float32 one (passed as floats, the is_f32 form of stitch_sift_desc).
+    Returns a dict: kp (KP_DTYPE, all octaves), fkp, angle, desc, cand {o: (m, 3)},
     taps [(sigma, float32 array)], expn, and with dump gauss / dog / grad {o: flat float32}."""
     o = opts_of(**kw)
-    gray = np.ascontiguousarray(gray, np.uint8)
+    f32 = np.asarray(gray).dtype == np.float32
+    gray = np.ascontiguousarray(gray, np.float32 if f32 else np.uint8)
     h, w = gray.shape
     src, dst = os.path.join(str(directory), "sift_in.bin"), os.path.join(str(directory), "sift_out.bin")
     with open(src, "wb") as f:
-        f.write(struct.pack("<5i5d", w, h, o["octaves"], o["levels"], int(dump), o["peak"], o["edge"], o["norm"], o["magnif"], o["window"]))
+        f.write(struct.pack("<5i5d", w, h, o["octaves"], o["levels"], int(dump) | (2 if f32 else 0), o["peak"], o["edge"], o["norm"],
+                            o["magnif"], o["window"]))
         f.write(gray.tobytes())
     subprocess.run([exe, src, dst], check=True, timeout=1800)
     out = dict(cand={}, gauss={}, dog={}, grad={}, taps=[], kps=[])
@@ -185,12 +237,13 @@ def reference_sift(L, gray, dump=False, want_desc=True, want_cand=False, **kw):
     f = L.vl_sift_new(w, h, o["octaves"], S, 0)
     F = f.contents
     F.peak_thresh, F.edge_thresh, F.norm_thresh, F.magnif, F.windowSize = o["peak"], o["edge"], o["norm"], o["magnif"], o["window"]
-    out = dict(cand={}, gauss={}, dog={}, grad={}, taps=[])
+    out = dict(cand={}, gauss={}, dog={}, grad={}, taps=[], octaves=0)
     kps, fkp, angs, descs = [], [], [], []
     VL_ERR_EOF = 5
     if L.vl_sift_process_first_octave(f, img.ctypes.data) != VL_ERR_EOF:
         while True:
             L.vl_sift_detect(f)
+            out["octaves"] += 1
             ow, oh, oc = F.octave_width, F.octave_height, F.o_cur
             if dump:
                 out["gauss"][oc] = _plane(F.octave, (S + 3) * ow * oh)

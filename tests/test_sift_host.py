@@ -103,3 +103,92 @@ def test_fixture_coverage():
     assert n["const"] == n["s23x37"] == n["s17x9"] == 0 and n["s64x65"] > 0
     assert min(n["auto3"], n["o3l5"], n["o2l1"], n["peak"], n["norm"]) >= 30
     assert (z["norm_desc"] == 0).all(axis=1).any() and (z["norm_desc"] != 0).any()  # the norm threshold cuts some, not all
+
+
+# ---- the edge fixtures (sift_edges*.npz): what only the GPU's launch logic can get wrong needs inputs that reach it ------------
+@pytest.fixture(scope="module")
+def edges():
+    return {f: np.load(os.path.join(GOLD, f)) for f in R.EDGE_FILES}
+
+
+def check_edge(got, z, name):
+    """Every bit of a result (emulate()'s or sift_unpack()'s dict) against the case `name` of its fixture file z."""
+    check_features(got, z, name + "_", name)
+    assert got["desc"].shape == (len(z[name + "_fkp"]), R.DIM)
+    bad = np.nonzero(R.row_crcs(got["desc"]) != z[name + "_desc_crc"])[0]
+    assert len(bad) == 0, f"{name}: descriptor rows {bad[:8]} differ"
+    assert R.sha(got["desc"]) == str(z[name + "_desc_sha"]), f"{name}: descriptors"
+    if name + "_desc" in z:
+        assert R.same_bits(got["desc"], z[name + "_desc"]), f"{name}: descriptors"
+
+
+@pytest.mark.parametrize("name,img,opts", R.EDGE_CASES, ids=[c[0] for c in R.EDGE_CASES])
+def test_edge_case_equals_reference(emulator, edges, name, img, opts):
+    exe, d = emulator
+    z = edges[R.edge_file(img)]
+    image = R.edge_image(z, img)
+    assert image.dtype == (np.float32 if img == "f32" else np.uint8)
+    check_edge(R.emulate(exe, image, d, **opts), z, name)
+
+
+def keypoints_per_octave(z, name, octaves=8):
+    return np.bincount(z[name + "_kp"]["o"], minlength=octaves)
+
+
+def test_edge_fixture_coverage(edges):
+    """The edge fixtures reach what they were made for; conditions on the reference's own results, not measurements."""
+    z, z2 = (edges[f] for f in R.EDGE_FILES)
+    per = keypoints_per_octave(z, "dense")
+    assert per[0] >= 2200 > R.GRID_LIMIT and per[2] > 0 and per[3] > 0, per  # a cap of 2 048 cuts inside octave 0
+    assert len(z["dense_kp"]) <= 4096  # the capacity the GPU test gives it
+    octs = [int(z[c + "_auto_oct"]) for c in R.MIXED_CALL]
+    assert len(set(octs)) >= 3, octs
+    later = [(a, b) for a in range(len(octs)) for b in range(a + 1, len(octs))
+             if octs[b] > octs[a] and keypoints_per_octave(z, R.MIXED_CALL[b] + "_auto")[octs[a]:].any()]
+    assert later, octs  # a frame listed after one with fewer octaves has a keypoint in an octave that one lacks
+    for c, (x0, y0, w, h) in R.EDGE_CROPS.items():  # the reference runs every octave asked for, pixels or not
+        assert int(z[c + "_oct"]) == 4 and int(z[c + "_auto_oct"]) == max(min(w, h).bit_length() - 4, 1)
+    for c in ("c200x24", "c150x9", "c200x160"):
+        w, h = R.EDGE_CROPS[c][2:]
+        assert int(z[c + "_o6_oct"]) == 6 and (R.pixel_octaves(w, h, 6) < 6) == (c != "c200x160")  # h >> o reaches 0 first
+    for c in ("squares", "squares_l3"):
+        assert np.bincount(z2[c + "_fkp"]).max() == 4, c
+    for c in ("strip", "stripT"):
+        per = keypoints_per_octave(z2, c)
+        assert per[0] > 0 and per[1] > 0, (c, per)
+    assert z2["img_strip"].shape == (20, 4096)
+    f = z2["img_f32"]
+    assert f.dtype == np.float32 and f.min() < 0 and f.max() > 255 and (f != np.rint(f)).any() and len(z2["f32_kp"]) > 0
+    for c in ("c3x2", "c1x1"):
+        assert len(z[c + "_kp"]) == len(z[c + "_auto_kp"]) == 0
+    zi = np.load(os.path.join(GOLD, "sift_input.npz"))  # the capacities of the per-frame GPU test come from these
+    k, row = R.split_keypoint(zi, "f4_")  # a feat_cap of row + 1 falls between two angles of keypoint k
+    assert zi["f4_fkp"][row] == zi["f4_fkp"][row + 1] == k and zi["f4_fkp"][row - 1] == k - 1 and row + 1 < len(zi["f4_fkp"])
+    per = keypoints_per_octave(zi, "f1")
+    assert per[0] > 100 and per[1:].sum() > 0  # a kp_cap of per[0] ends octave 0, one of 100 lies inside it
+
+
+def sweep_crops():
+    """48 crops of `dense`: each side drawn from 1..40 or 41..200, every combination of narrow / short / ordinary occurring."""
+    rng = np.random.default_rng(4096)
+    out = []
+    for k in range(48):
+        w, h = (int(rng.integers(1, 41)) if small else int(rng.integers(41, 201)) for small in ((k & 1) == 0, (k & 2) == 0))
+        out.append((int(rng.integers(0, 760 - w + 1)), int(rng.integers(0, 600 - h + 1)), w, h))
+    return out
+
+
+@pytest.mark.skipif(not os.path.exists(R.REF_SO), reason="the reference library is built only where its sources are")
+@pytest.mark.parametrize("opts", [dict(), dict(octaves=-1)], ids=["defaults", "auto"])
+def test_crop_sweep_against_live_reference(emulator, edges, opts):
+    exe, d = emulator
+    L = R.load_reference()
+    dense = edges[R.EDGE_FILES[0]]["img_dense"]
+    found = 0
+    for x0, y0, w, h in sweep_crops():
+        img = np.ascontiguousarray(dense[y0:y0 + h, x0:x0 + w])
+        got, ref = R.emulate(exe, img, d, **opts), R.reference_sift(L, img, **opts)
+        for k in ("kp", "fkp", "angle", "desc"):
+            assert R.same_bits(got[k], ref[k]), f"{w} x {h} at ({x0}, {y0}) {opts}: {k}"
+        found += len(ref["desc"])
+    assert found > 0
