@@ -31,6 +31,7 @@ class StitchError(RuntimeError):
 
 
 OK, ERR_ARG, ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP, ERR_PYRAMID, ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6
+ERR_NO_MAP, ERR_CAPACITY = -7, -8  # the whole-panorama calls (include/stitch_panorama.h)
 
 
 class BlendOpts(C.Structure):
@@ -119,6 +120,19 @@ SIGNATURES = _signatures(
     ("stitch_sift_expn_table", None, vp), ("stitch_sift_elem", None, f64, vp),
 )
 
+# The same for include/stitch_panorama.h, the whole panorama (a header of its own, so a table of its own: SIGNATURES states
+# stitch.h and nothing else); tests/test_panorama_host.py holds it to that header.
+PANORAMA_SIGNATURES = _signatures(
+    ("stitch_panorama_opts_default stitch_panorama_destroy", None, vp),
+    ("stitch_feature_order", i32, vp, i32, vp, vp), ("stitch_stitch_order", i32, vp, i32, i32, vp, vp, vp),
+    ("stitch_dev_map_points", i32, vp, vp, vp, vp, i32, vp, f32, f32, vp), ("stitch_dev_shift_points", i32, vp, vp, vp, vp, i32, i32, i32, vp),
+    ("stitch_dev_pair_maps", i32, vp, vp, f64, vp, vp, vp, vp),
+    ("stitch_dev_panorama_from_features_u8", i32, vp, vp, i32, vp, vp, vp), ("stitch_dev_panorama_u8", i32, vp, i32, vp, vp, vp),
+    ("stitch_panorama_u8", i32, vp, i32, vp, vp), ("stitch_panorama_info", i32, vp, vp, vp, vp, vp),
+    ("stitch_panorama_step_at", i32, vp, i32, vp), ("stitch_panorama_pixels", vp, vp), ("stitch_panorama_step_pixels", vp, vp, i32),
+    ("stitch_panorama_copy", i32, vp, i32, vp, sz, i32, vp),
+)
+
 _lib = None
 
 
@@ -137,7 +151,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -418,6 +432,29 @@ def shift_points(x, y, ox, oy):
     return x, y, ix, iy
 
 
+def dev_map_points(x, y, p_fwd, offx, offy, want_int=True):
+    """map_points on float32 device tensors, IN PLACE, on torch's current stream (no synchronisation) -> (x, y, ix, iy); ix / iy
+    are new int32 tensors (None without want_int)."""
+    import torch
+    x, y = _tvec(x, torch.float32, "x"), _tvec(y, torch.float32, "y")
+    if x.numel() != y.numel():
+        raise ValueError("x and y differ in length")
+    ix, iy = (torch.empty(x.numel(), dtype=torch.int32, device=x.device) for _ in range(2)) if want_int else (None, None)
+    _chk(lib().stitch_dev_map_points(_dp(x), _dp(y), _dp(ix), _dp(iy), x.numel(), _map8(p_fwd), offx, offy, _stream()))
+    return x, y, ix, iy
+
+
+def dev_shift_points(x, y, ox, oy, want_int=True):
+    """shift_points on float32 device tensors, IN PLACE, on torch's current stream -> (x, y, ix, iy)."""
+    import torch
+    x, y = _tvec(x, torch.float32, "x"), _tvec(y, torch.float32, "y")
+    if x.numel() != y.numel():
+        raise ValueError("x and y differ in length")
+    ix, iy = (torch.empty(x.numel(), dtype=torch.int32, device=x.device) for _ in range(2)) if want_int else (None, None)
+    _chk(lib().stitch_dev_shift_points(_dp(x), _dp(y), _dp(ix), _dp(iy), x.numel(), int(ox), int(oy), _stream()))
+    return x, y, ix, iy
+
+
 # ---- descriptor matching: ImageProcess::getImgPair (ImageProcess.cpp:273-351) -----------------------------------------------
 DESCRIPTOR_DIM = 128  # STITCH_DESCRIPTOR_DIM (DESCRIPTOR_SUM, ImageProcess.h:20)
 RATIO_THRESHOLD = 0.5  # ImageProcess.h:22
@@ -652,6 +689,165 @@ def sift_unpack(out):
     kp = out["kp"][:nk].cpu().numpy().view(SIFT_KP_DTYPE).reshape(-1)
     return dict(kp=kp, fkp=out["fkp"][:nf].cpu().numpy(), angle=out["angle"][:nf].cpu().numpy(), desc=out["desc"][:nf].cpu().numpy(),
                 status=head[2:].copy())
+
+
+# ---- the whole panorama: include/stitch_panorama.h ------------------------------------------------------------------------
+class FeatureSet(C.Structure):
+    """stitch_feature_set: one frame's features in map order (device pointers)."""
+    _fields_ = [("d_desc", C.c_void_p), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("n", C.c_int32)]
+
+
+class FrameU8(C.Structure):
+    """stitch_frame_u8: one planar (3, height, width) frame, not projected."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class PanoramaOpts(C.Structure):
+    """stitch_panorama_opts; the defaults are stitch_panorama_opts_default's (the reference's values)."""
+    _fields_ = [("blend", C.c_void_p), ("sift", C.c_void_p), ("ransac", C.c_void_p), ("ratio", C.c_double), ("match_threshold", C.c_int32),
+                ("fov_deg", C.c_float), ("kp_cap", C.c_int32), ("feat_cap", C.c_int32), ("finish", C.c_int32), ("num", C.c_double),
+                ("den", C.c_double), ("keep_steps", C.c_int32)]
+
+
+class PanoramaStep(C.Structure):
+    """stitch_panorama_step: what one stitch step used and produced."""
+    _fields_ = [("src", C.c_int32), ("dst", C.c_int32), ("p_fwd", C.c_double * 8), ("p_bwd", C.c_double * 8), ("geom", StepGeom), ("seam", Seam),
+                ("info", (C.c_int32 * RANSAC_INFO) * 2)]
+
+
+def feature_order_c(descriptors):
+    """stitch_feature_order: the index array of pipeline.feature_order, computed by the library's host code."""
+    d = _desc_rows(descriptors)
+    idx, kept = np.empty(max(d.shape[0], 1), np.int32), C.c_int(0)
+    _chk(lib().stitch_feature_order(_p(d), d.shape[0], _p(idx), C.byref(kept)))
+    return idx[:kept.value].copy()
+
+
+def stitch_order_c(counts, threshold=20):
+    """stitch_stitch_order: pipeline.stitch_order by the library's host code -> (start, [(src, dst), ...])."""
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    n = c.shape[0]
+    if c.ndim != 2 or c.shape[1] != n:
+        raise ValueError("expected a square matrix of counts")
+    pairs, start, steps = np.zeros((max(n * (n - 1), 1), 2), np.int32), C.c_int(0), C.c_int(0)
+    _chk(lib().stitch_stitch_order(_p(c), n, int(threshold), C.byref(start), _p(pairs), C.byref(steps)))
+    return start.value, [(int(a), int(b)) for a, b in pairs[:steps.value]]
+
+
+def _feature_set(desc, x, y):
+    import torch
+    desc, x, y = _tdesc(desc), _tvec(x, torch.float32, "x"), _tvec(y, torch.float32, "y")
+    if not x.numel() == y.numel() == desc.shape[0]:
+        raise ValueError("descriptors, x and y differ in length")
+    return FeatureSet(_dp(desc), _dp(x), _dp(y), desc.shape[0])
+
+
+def dev_pair_maps(src, dst, ratio=RATIO_THRESHOLD, opts=None):
+    """pipeline.pair_maps without its read-back: src / dst are (descriptors (n, 128), x (n,), y (n,)) float32 device tensors in map
+    order -- the frame in the mosaic and the frame to warp.  Both matcher calls, the longer-list rule and both estimations are
+    enqueued on torch's current stream.  Returns device tensors (p (2, 8) float64: forward, backward; info (2, 5) int32)."""
+    import torch
+    a, b = _feature_set(*src), _feature_set(*dst)
+    dev = src[0].device
+    p = torch.empty((2, 8), dtype=torch.float64, device=dev)
+    info = torch.empty((2, RANSAC_INFO), dtype=torch.int32, device=dev)
+    o = opts if opts is not None else RansacOpts()
+    _chk(lib().stitch_dev_pair_maps(C.byref(a), C.byref(b), float(ratio), C.byref(o), _dp(p), _dp(info), _stream()))
+    return p, info
+
+
+def _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, keep_steps, ratio, match_threshold, fov_deg, keep):
+    o = PanoramaOpts()
+    lib().stitch_panorama_opts_default(C.byref(o))
+    for obj, field in ((_opts(opts) if opts is not None else None, "blend"), (sift_opts, "sift"), (ransac_opts, "ransac")):
+        if obj is not None:
+            keep.append(obj)  # the structure must outlive the call
+            setattr(o, field, C.addressof(obj))
+    o.ratio, o.match_threshold, o.fov_deg = float(ratio), int(match_threshold), float(fov_deg)
+    o.kp_cap, o.feat_cap, o.finish, o.num, o.den = int(kp_cap), int(feat_cap or 0), int(bool(finish)), float(num), float(den)
+    o.keep_steps = int(bool(keep_steps))
+    return o
+
+
+def _panorama_result(h, device, return_steps, keep_steps):
+    """The handle's mosaic (and steps) as torch tensors / dicts shaped like pipeline.panorama_from_features's; destroys the handle."""
+    import torch
+    L = lib()
+    try:
+        w, ht, start, ns = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _chk(L.stitch_panorama_info(h, C.byref(w), C.byref(ht), C.byref(start), C.byref(ns)))
+        final = torch.empty((3, ht.value, w.value), dtype=torch.uint8, device=device)
+        _chk(L.stitch_panorama_copy(h, -1, _dp(final), final.numel(), 1, _stream()))
+        steps = []
+        for k in range(ns.value if return_steps else 0):
+            s = PanoramaStep()
+            _chk(L.stitch_panorama_step_at(h, k, C.byref(s)))
+            g = s.geom
+            out = None
+            if keep_steps:
+                out = torch.empty((3, g.ch, g.cw), dtype=torch.uint8, device=device)
+                _chk(L.stitch_panorama_copy(h, k, _dp(out), out.numel(), 1, _stream()))
+            steps.append(dict(start=start.value, src=s.dst, mosaic_src=s.src, p=np.array(s.p_bwd[:]), p_fwd=np.array(s.p_fwd[:]), offx=g.min_x, offy=g.min_y,
+                              ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch, out=out, seam=s.seam.as_tuple(),
+                              info=np.array([list(s.info[0]), list(s.info[1])], np.int64)))
+        torch.cuda.current_stream().synchronize()  # the copies have left the handle's buffers
+    finally:
+        L.stitch_panorama_destroy(h)
+    return (final, steps) if return_steps else final
+
+
+def _frames_u8(frames):
+    import torch
+    frames = [_timg(f) for f in frames]
+    if any(f.dtype != torch.uint8 for f in frames):
+        raise TypeError("expected uint8 frames")
+    return frames, (FrameU8 * max(len(frames), 1))(*[FrameU8(_dp(f), f.shape[2], f.shape[1]) for f in frames])
+
+
+def dev_panorama(frames, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, keep_steps=False, sift_opts=None, ransac_opts=None,
+                 kp_cap=4096, feat_cap=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+    """The whole of ImageProcess::ImageProcess plus matching() in ONE library call (stitch_dev_panorama_u8): frames is a list of
+    (3, H, W) uint8 device tensors (unprojected).  Returns the mosaic as a tensor; with return_steps also a list of dicts with the
+    keys of pipeline.panorama_from_features's steps ("src" is the warped frame; "out" the step's mosaic with keep_steps, else
+    None).  Runs on torch's current stream and waits for it."""
+    frames, arr = _frames_u8(frames)
+    keep, h = [], C.c_void_p()
+    o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, keep_steps, ratio, match_threshold, fov_deg, keep)
+    _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
+    return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+
+
+def dev_panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, keep_steps=False,
+                               ransac_opts=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+    """stitch_dev_panorama_from_features_u8: as dev_panorama, from the frames and per frame (descriptors (n, 128), x, y) float32
+    device tensors in map order, which are left unchanged."""
+    frames, arr = _frames_u8(frames)
+    if len(features) != len(frames):
+        raise ValueError("one feature set per frame")
+    sets = (FeatureSet * max(len(frames), 1))(*[_feature_set(*f) for f in features])
+    keep, h = [], C.c_void_p()
+    o = _panorama_opts(opts, finish, num, den, None, ransac_opts, 4096, None, keep_steps, ratio, match_threshold, fov_deg, keep)
+    _chk(lib().stitch_dev_panorama_from_features_u8(arr, sets, len(frames), C.byref(o), _stream(), C.byref(h)))
+    return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+
+
+def panorama(frames, opts=None, finish=True, num=19.0, den=20.0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None,
+             ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+    """stitch_panorama_u8: the whole panorama from (3, H, W) uint8 HOST arrays -> the mosaic as a numpy array."""
+    frames = [np.ascontiguousarray(_img(f), np.uint8) for f in frames]
+    arr = (FrameU8 * max(len(frames), 1))(*[FrameU8(f.ctypes.data, f.shape[2], f.shape[1]) for f in frames])
+    keep, h = [], C.c_void_p()
+    o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, False, ratio, match_threshold, fov_deg, keep)
+    L = lib()
+    _chk(L.stitch_panorama_u8(arr, len(frames), C.byref(o), C.byref(h)))
+    try:
+        w, ht = C.c_int(), C.c_int()
+        _chk(L.stitch_panorama_info(h, C.byref(w), C.byref(ht), None, None))
+        out = np.empty((3, ht.value, w.value), np.uint8)
+        _chk(L.stitch_panorama_copy(h, -1, _p(out), out.nbytes, 0, None))
+    finally:
+        L.stitch_panorama_destroy(h)
+    return out
 
 
 # ---- device-resident entry points (torch tensors on the HIP device) --------------------------------------------

@@ -20,6 +20,7 @@
 
 #include "stitch.h"
 #include "stitch_handoff.h"
+#include "stitch_panorama.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2547,3 +2548,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_match.inc"
 #include "stitch_ransac.inc"
 #include "stitch_sift.inc"
+#include "stitch_panorama.inc"

@@ -865,3 +865,7 @@ def panorama_from_frames(frames, opts=None, finish=True, num=19.0, den=20.0, ret
     """The whole of ImageProcess::ImageProcess plus matching() from decoded frames alone: sift_features (kp_cap / feat_cap are
     its per-frame capacities; a frame that needs more raises StitchError with the counts found), then panorama_from_features."""
     return panorama_from_features(frames, sift_features(frames, sift_opts, kp_cap, feat_cap), opts, finish, num, den, return_steps)
+
+
+# ---- the same chain as ONE call of the C ABI (include/stitch_panorama.h): what a C++ caller gets ----------------------------------
+panorama_c = capi.dev_panorama

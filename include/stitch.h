@@ -40,7 +40,9 @@ typedef enum stitch_status {
                                      (ImageProcess.cpp:687)                                                      */
     STITCH_ERR_PYRAMID = -4,      /* a pyramid level would have a zero dimension (min side < 2^(levels-1))       */
     STITCH_ERR_HIP = -5,          /* a HIP runtime call failed; text in stitch_last_error()                      */
-    STITCH_ERR_NO_DEVICE = -6     /* no HIP device visible                                                       */
+    STITCH_ERR_NO_DEVICE = -6,    /* no HIP device visible                                                       */
+    STITCH_ERR_NO_MAP = -7,       /* whole panorama: a stitched pair's RANSAC did not return STITCH_RANSAC_OK twice      */
+    STITCH_ERR_CAPACITY = -8      /* whole panorama: a frame's SIFT reported STITCH_SIFT_OVERFLOW                        */
 } stitch_status;
 
 /* Parameters of the multi-band blend.  stitch_blend_opts_default() = the root variant the oracle follows. */
@@ -646,6 +648,13 @@ int stitch_sift(const uint8_t *gray, int width, int height, const StitchSiftOpts
 int stitch_sift_filter(double sigma, float *taps);
 void stitch_sift_expn_table(double *tab257);
 void stitch_sift_elem(double x, double out[4]); /* {exp(x), 2^x, sin x, cos x} */
+
+/* ---- whole panorama: frames in, mosaic out ---------------------------------------------------------------------------------
+ * The chain that joins the stages above -- projection + gray, SIFT, the map order, all-pairs matching, the stitch order, per
+ * step both maps, the stitch step and the feature updates, the finish pass -- as one call, with its building blocks, is
+ * declared in include/stitch_panorama.h (same library, same ABI version; a header of its own like stitch_handoff.h, so that
+ * the table of entry points above stays as it is).  Its two status codes, STITCH_ERR_NO_MAP and STITCH_ERR_CAPACITY, are in
+ * stitch_status above. */
 
 #ifdef __cplusplus
 }
