@@ -794,6 +794,28 @@ def stitch_order(counts, threshold=MATCH_THRESHOLD):
     return start, order
 
 
+class KeyPointTrack:
+    """Every frame's key points through the steps of matching() (ImageProcess.cpp:226-227, :232), on the host: the warped frame's
+    key points go through the forward map, then those of imgs[preStichingIndex] -- the frame warped by the step BEFORE (the start
+    frame at the first step), whichever frame the step's srcIndex is -- move by the canvas offsets.  `kps` is a list of (n, 2)
+    x/y arrays; `pre` is preStichingIndex."""
+
+    def __init__(self, kps, start):
+        import numpy as np
+        self.kps = [np.array(k, dtype=np.float32).reshape(-1, 2) for k in kps]
+        self.pre = start
+
+    def stitched(self, src, dst, p_fwd, geom):
+        """Step (srcIndex, dstIndex): frame `dst` has been warped onto the mosaic with the forward map p_fwd and the step geometry
+        `geom` (capi.StepGeom).  `src` names the step; the reference moves imgs[preStichingIndex], not imgs[srcIndex]."""
+        import numpy as np
+        x, y, _, _ = capi.map_points(self.kps[dst][:, 0], self.kps[dst][:, 1], p_fwd, geom.min_x, geom.min_y)
+        self.kps[dst] = np.stack([x, y], 1)
+        x, y, _, _ = capi.shift_points(self.kps[self.pre][:, 0], self.kps[self.pre][:, 1], geom.ox, geom.oy)
+        self.kps[self.pre] = np.stack([x, y], 1)
+        self.pre = dst
+
+
 def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False):
     """ImageProcess::matching (ImageProcess.cpp:101-268) from the frames and their SIFT features alone: frames is a list of
     (3, H, W) uint8 device tensors (unprojected), features a list of (descriptors (n, 128), keypoints (n, 2) x/y) in the
@@ -801,8 +823,9 @@ def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, d
     feature updates of :226-227.  Returns the final mosaic (and, with return_steps, what every step used and produced)."""
     import numpy as np
     desc = [np.ascontiguousarray(d, dtype=np.float32) for d, _ in features]
-    kps = [np.array(k, dtype=np.float32).reshape(-1, 2) for _, k in features]
     start, order = stitch_order(match_counts(desc))
+    track = KeyPointTrack([k for _, k in features], start)
+    kps = track.kps  # updated in place by track.stitched
     proj = {}
 
     def projected(i):
@@ -811,20 +834,14 @@ def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, d
         return proj[i]
 
     result = projected(start)
-    pre = start
     steps = []
     for src, dst in order:
         p_fwd, p_bwd, info = pair_maps(desc[src], kps[src], desc[dst], kps[dst])
         if info[0][0] != capi.RANSAC_OK or info[1][0] != capi.RANSAC_OK:
             raise capi.StitchError(-1, f"frames {src} -> {dst}: no map (RANSAC status {int(info[0][0])} / {int(info[1][0])}, {int(info[0][1])} pairs)")
         result, g, _seam = capi.dev_step(projected(dst), p_fwd, p_bwd, result, opts)
-        # :226-227: the warped frame's keypoints go through the forward map, those of the frame stitched before move by the offsets
-        x, y, _, _ = capi.map_points(kps[dst][:, 0], kps[dst][:, 1], p_fwd, g.min_x, g.min_y)
-        kps[dst] = np.stack([x, y], 1)
-        x, y, _, _ = capi.shift_points(kps[pre][:, 0], kps[pre][:, 1], g.ox, g.oy)
-        kps[pre] = np.stack([x, y], 1)
-        pre = dst
-        steps.append(dict(start=start, src=dst, p=p_bwd, p_fwd=p_fwd, offx=g.min_x, offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch,
+        track.stitched(src, dst, p_fwd, g)  # :226-227
+        steps.append(dict(start=start, src=dst, mosaic_src=src, p=p_bwd, p_fwd=p_fwd, offx=g.min_x, offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch,
                           out=result, info=info))
     if finish:
         result = result.clone() if return_steps and steps else result

@@ -99,7 +99,7 @@ def main():
                        "cw": int(kv["cw"]), "ch": int(kv["ch"]), "fw": int(kv["sw"]), "fh": int(kv["sh"])}
             elif ln.startswith("move"):
                 cur.update({"ox": int(kv["ox"]), "oy": int(kv["oy"]), "mw": int(kv["sw"]), "mh": int(kv["sh"])})
-            else:
+            elif ln.startswith("blend"):  # the recorder's other lines (fwd, shift, pairs) are for add_forward_maps.py / make_chain_goldens.py
                 k = len(steps)
                 cw, ch = cur["cw"], cur["ch"]
                 ld = lambda tag, w_, h_: np.fromfile(os.path.join(dump, f"step{k}_{tag}_{w_}x{h_}.raw"), np.uint8).reshape(3, h_, w_)
