@@ -372,10 +372,18 @@ int stitch_bmp_encode_u8(const uint8_t *planar, int w, int h, uint8_t *file, siz
 int stitch_dev_bmp_decode_u8(const uint8_t *d_file, size_t n, const stitch_bmp_info *info, uint8_t *d_planar, void *stream);
 int stitch_dev_bmp_encode_u8(const uint8_t *d_planar, int w, int h, uint8_t *d_file, size_t cap, void *stream);
 /* transfer::transfer (transfer.cpp:3-13, :125-225): Reinhard's l-alpha-beta colour transfer of
- * `tem`'s statistics onto `src`.  Dead code in the reference (ImageProcess.cpp:180-182) and not buildable outside
- * Windows, so parity is against the CPU restatement only ("parity unpinned").  The float running sums of
+ * `tem`'s statistics onto `src`.  Dead code in the reference (ImageProcess.cpp:180-182).  The float running sums of
  * transfer.cpp:128-164 are kept in the reference's serial order; std::log(float) / std::pow(10, float) are the
- * specified functions of include/stitch_elem.h.  stats (optional, 12 floats): mean[3], sd[3] of the source, then of the
+ * specified functions of include/stitch_elem.h.
+ * Parity is pinned to the reference's own transfer.cpp, compiled unchanged (oracle/ref_transfer.cpp, its Win32 thread calls
+ * supplied by oracle/win32_shim.h): the CPU restatement equals it bit for bit -- every output byte, every bit of the twelve
+ * statistics -- when both call the platform's libm (tests/test_oracle_vs_reference.py, all 2^24 colours included).  The
+ * kernels and the restatement's default mode evaluate the specified functions of include/stitch_elem.h instead, whose
+ * logarithm is the correctly rounded one at all 50 331 648 inputs the transfer can make; glibc's logf is not at 17 757 of
+ * them, so a glibc build of the reference differs from the kernels by one grey level in a recorded handful of bytes: 18 of
+ * 1.06e8 over the 27 recorded cases (tests/golden/transfer.npz: 15 where every colour is transferred onto every colour,
+ * 2 for every colour onto a 97x61 template, 1 of 589 824 on the committed frames 3 -> 4), none anywhere else.
+ * stats (optional, 12 floats): mean[3], sd[3] of the source, then of the
  * template, in l-alpha-beta.  out may alias src. */
 int stitch_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, uint8_t *out, float stats[12]);
 int stitch_dev_transfer_u8(const uint8_t *d_src, int sw, int sh, const uint8_t *d_tem, int tw, int th, uint8_t *d_out,

@@ -4,9 +4,16 @@
  * :212-214; the authors linked the MSVC runtime).  No two libms agree bit for bit, so the result of the reference on
  * this path is platform-defined in its last bit.  To make the CPU restatement (oracle/) and the HIP kernels agree
  * exactly, both evaluate the two functions below: plain IEEE-754 double +,-,*,/ in a fixed order, no FMA contraction
- * (both sides are compiled with -ffp-contract=off), accurate to a few 1e-16 relative, so that the float the reference
- * rounds to is reproduced except within ~1e-8 ulp of a rounding boundary.  tests/test_oracle_golden.py bounds the
- * distance to glibc's logf / pow.
+ * (both sides are compiled with -ffp-contract=off), accurate to about 2e-16 relative.
+ *
+ * Measured over the inputs the transfer really makes (tests/test_oracle_golden.py, tests/elem_check.c):
+ *   stitch_elem_logf  equals the correctly rounded logarithm, (float)logl(x), at every l, m, s of all 2^24 colours
+ *                     (50 331 648 inputs, 0 departures).  glibc's logf departs from it at 17 757 of them.
+ *   stitch_elem_pow10 rounds to the same float as powl(10, y) at every exponent LabToRGB receives when every colour is
+ *                     transferred onto every colour (50 331 648 inputs in -1.7 .. 2.5, 0 departures, at most 1.98e-16
+ *                     relative in double), and over a sweep of [-6, 6].  glibc's pow agrees at all of them.
+ * Hence a glibc build of the reference differs from this path only through logf: by one grey level in 18 recorded bytes of
+ * 1.06e8 (tests/golden/transfer.npz), and in the last bits of some statistics.
  */
 #ifndef STITCH_ELEM_H
 #define STITCH_ELEM_H

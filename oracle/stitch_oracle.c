@@ -896,7 +896,10 @@ int oracle_bmp_encode_u8(const uint8_t *planar, int w, int h, uint8_t *file, siz
 /* ---- transfer.cpp:3-13,125-225, the l-alpha-beta colour transfer (dead code in the reference:
  * ImageProcess.cpp:180-182 are commented out).  Restatement of the per-pixel arithmetic, which is the same in the
  * serial branch (transfer.cpp:71-78,113-121) and in the Win32-threaded one (:15-41, rows are independent).
- * PARITY UNPINNED: transfer.cpp does not compile here (windows.h threads) and the reference holds no output of it.
+ * PINNED: with use_libm set this equals the reference's transfer.cpp (compiled unchanged through ref_transfer.cpp and
+ * win32_shim.h) in every output byte and every bit of the twelve statistics (tests/test_oracle_vs_reference.py); without
+ * it, it differs from that glibc build by one grey level in 18 recorded bytes of 1.06e8 (tests/golden/transfer.npz), because
+ * stitch_elem_logf is correctly rounded at all 50 331 648 inputs of this path and glibc's logf is not at 17 757 of them.
  * The two libm calls (std::log(float), std::pow(10, float) -> pow(double,double)) are the specified functions of
  * include/stitch_elem.h unless use_libm is set (then logf / pow of this platform's libm, for measuring the distance). */
 #include "../include/stitch_elem.h"
@@ -919,11 +922,16 @@ static void tr_rgb_to_lab(float R, float G, float B, float *L, float *a, float *
     *a = (float)((double)(paraB * l + paraB * m) - (2.0 * (double)paraB) * (double)s);
     *b = paraC * l - paraC * m;
 }
-static void tr_lab_to_rgb(float L, float a, float b, float *R, float *G, float *B, int use_libm) { /* transfer.cpp:201-225 */
+/* the three exponents of transfer.cpp:208-210, the arguments of its pow(10, .) calls */
+static void tr_lab_to_exponents(float L, float a, float b, float *l, float *m, float *s) {
     const float paraA = (float)(sqrt(3.0) / 3.0), paraB = (float)(sqrt(6.0) / 6.0), paraC = (float)(sqrt(2.0) / 2.0);
-    float l = (paraA * L + paraB * a) + paraC * b;
-    float m = (paraA * L + paraB * a) - paraC * b;
-    float s = (float)((double)(paraA * L) - (2.0 * (double)paraB) * (double)a);
+    *l = (paraA * L + paraB * a) + paraC * b;
+    *m = (paraA * L + paraB * a) - paraC * b;
+    *s = (float)((double)(paraA * L) - (2.0 * (double)paraB) * (double)a);
+}
+static void tr_lab_to_rgb(float L, float a, float b, float *R, float *G, float *B, int use_libm) { /* transfer.cpp:201-225 */
+    float l, m, s;
+    tr_lab_to_exponents(L, a, b, &l, &m, &s);
     l = (float)tr_pow10((double)l, use_libm);
     m = (float)tr_pow10((double)m, use_libm);
     s = (float)tr_pow10((double)s, use_libm);
@@ -933,6 +941,15 @@ static void tr_lab_to_rgb(float L, float a, float b, float *R, float *G, float *
     *R = r > 0.0f ? (r < 255.0f ? r : 255.0f) : 0.0f;
     *G = g > 0.0f ? (g < 255.0f ? g : 255.0f) : 0.0f;
     *B = bb > 0.0f ? (bb < 255.0f ? bb : 255.0f) : 0.0f;
+}
+/* the two per-pixel functions on their own (the reference's public statics): n pixels, 3 floats each, interleaved */
+void oracle_transfer_rgb_to_lab(const float *rgb, float *lab, long long n, int use_libm) {
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < n; ++i) tr_rgb_to_lab(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], &lab[3 * i], &lab[3 * i + 1], &lab[3 * i + 2], use_libm);
+}
+void oracle_transfer_lab_to_rgb(const float *lab, float *rgb, long long n, int use_libm) {
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < n; ++i) tr_lab_to_rgb(lab[3 * i], lab[3 * i + 1], lab[3 * i + 2], &rgb[3 * i], &rgb[3 * i + 1], &rgb[3 * i + 2], use_libm);
 }
 static float *tr_lab_image(const uint8_t *rgb, int w, int h, int use_libm) { /* transfer.cpp:4-9, :83-123 */
     const size_t n = (size_t)w * h;
@@ -955,9 +972,9 @@ static void tr_stats(const float *lab, size_t n, int w, int h, float mean[3], fl
         sd[c] = sqrtf(var / (float)(w * h));
     }
 }
-int oracle_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, uint8_t *out, float stats[12],
-                       int use_libm) {
-    if (!src || !tem || !out || sw <= 0 || sh <= 0 || tw <= 0 || th <= 0) return ORACLE_ERR_ARG;
+static int tr_transfer(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, uint8_t *out, float stats[12],
+                       float *exponents, int use_libm) {
+    if (!src || !tem || (!out && !exponents) || sw <= 0 || sh <= 0 || tw <= 0 || th <= 0) return ORACLE_ERR_ARG;
     const size_t n = (size_t)sw * sh, nt = (size_t)tw * th;
     float *ls = tr_lab_image(src, sw, sh, use_libm), *lt = tr_lab_image(tem, tw, th, use_libm);
     if (!ls || !lt) {
@@ -979,6 +996,8 @@ int oracle_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, i
     for (long long i = 0; i < (long long)n; ++i) { /* transfer.cpp:165-171, then :43-81, then the cast of :12 */
         float v[3], R, G, B;
         for (int c = 0; c < 3; ++c) v[c] = (ls[(size_t)c * n + i] - ms[c]) * st[c] / ss[c] + mt[c];
+        if (exponents) tr_lab_to_exponents(v[0], v[1], v[2], &exponents[i], &exponents[n + i], &exponents[2 * n + i]);
+        if (!out) continue;
         tr_lab_to_rgb(v[0], v[1], v[2], &R, &G, &B, use_libm);
         out[i] = (uint8_t)R;
         out[n + i] = (uint8_t)G;
@@ -987,4 +1006,15 @@ int oracle_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, i
     free(ls);
     free(lt);
     return ORACLE_OK;
+}
+int oracle_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, uint8_t *out, float stats[12],
+                       int use_libm) {
+    if (!out) return ORACLE_ERR_ARG;
+    return tr_transfer(src, sw, sh, tem, tw, th, out, stats, NULL, use_libm);
+}
+/* the arguments of the pow(10, .) calls that this transfer makes (transfer.cpp:212-214), planar 3 x sh x sw: the domain
+ * over which tests/test_oracle_golden.py holds stitch_elem_pow10 against the correctly rounded power */
+int oracle_transfer_exponents_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, float *exponents, int use_libm) {
+    if (!exponents) return ORACLE_ERR_ARG;
+    return tr_transfer(src, sw, sh, tem, tw, th, NULL, NULL, exponents, use_libm);
 }

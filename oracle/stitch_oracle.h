@@ -107,11 +107,19 @@ int oracle_bmp_decode_u8(const uint8_t *file, size_t n, uint8_t *planar);
 size_t oracle_bmp_file_bytes(int w, int h);
 int oracle_bmp_encode_u8(const uint8_t *planar, int w, int h, uint8_t *file, size_t cap);
 /* transfer.cpp:3-13,125-225 (l-alpha-beta colour transfer; dead code in the reference).
- * PARITY UNPINNED (transfer.cpp needs windows.h; no output of it exists in the reference).  stats (optional) receives
+ * PINNED to transfer.cpp itself (oracle/ref_transfer.cpp): bit for bit with use_libm = 1, where both sides call the same
+ * libm; with use_libm = 0 one grey level apart from a glibc build of the reference in 18 recorded bytes of 1.06e8
+ * (tests/golden/transfer.npz), where glibc's logf is not the correctly rounded value.  stats (optional) receives
  * mean[3], sd[3] of the source and mean[3], sd[3] of the template in l-alpha-beta.  use_libm = 0: the specified
  * log / pow10 of include/stitch_elem.h (what the product computes); 1: this platform's logf / pow. */
 int oracle_transfer_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, uint8_t *out, float stats[12],
                        int use_libm);
+/* the two per-pixel functions of the transfer on their own (transfer::RGBtoLab / LabToRGB, transfer.cpp:175-226): n pixels,
+ * three floats each, interleaved */
+void oracle_transfer_rgb_to_lab(const float *rgb, float *lab, long long n, int use_libm);
+void oracle_transfer_lab_to_rgb(const float *lab, float *rgb, long long n, int use_libm);
+/* the arguments of the transfer's pow(10, .) calls (transfer.cpp:212-214) for these images, planar 3 x sh x sw */
+int oracle_transfer_exponents_u8(const uint8_t *src, int sw, int sh, const uint8_t *tem, int tw, int th, float *exponents, int use_libm);
 /* synthetic frame generator of SURVEY.md 8(d) */
 void oracle_synth_u8(uint8_t *dst, int w, int h, int frame_id);
 void oracle_synth_f32(float *dst, int w, int h, int frame_id);

@@ -13,6 +13,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "libstitch_oracle.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_hotpath.so")
+REF_TRANSFER_SO = os.path.join(ROOT, "oracle", "_ref", "libref_transfer.so")  # the reference's transfer.cpp (oracle/ref_transfer.cpp)
 REF6_SO = os.path.join(ROOT, "oracle", "_ref", "libref6_hotpath.so")  # the src/ex6 variant (oracle/ref6_harness.cpp)
 
 
@@ -276,6 +277,31 @@ class Oracle:
         assert rc == 0, rc
         return out, st
 
+    def transfer_exponents(self, src, tem, use_libm=False):
+        """the arguments of the pow(10, .) calls this transfer makes (transfer.cpp:212-214), planar (3, H, W) float32"""
+        src, tem = _img(src, np.uint8), _img(tem, np.uint8)
+        ex = np.empty(src.shape, np.float32)
+        self.lib.oracle_transfer_exponents_u8.restype = C.c_int
+        rc = self.lib.oracle_transfer_exponents_u8(_p(src), src.shape[2], src.shape[1], _p(tem), tem.shape[2], tem.shape[1], _p(ex), int(use_libm))
+        assert rc == 0, rc
+        return ex
+
+    def _per_pixel(self, fn, px, use_libm):
+        px = np.ascontiguousarray(px, np.float32)
+        assert px.ndim == 2 and px.shape[1] == 3, px.shape
+        out = np.empty_like(px)
+        fn.restype = None
+        fn(_p(px), _p(out), C.c_longlong(px.shape[0]), int(use_libm))
+        return out
+
+    def rgb_to_lab(self, rgb, use_libm=False):
+        """transfer::RGBtoLab (transfer.cpp:175-198) of n pixels: (n, 3) float32 R G B -> (n, 3) float32 l alpha beta"""
+        return self._per_pixel(self.lib.oracle_transfer_rgb_to_lab, rgb, use_libm)
+
+    def lab_to_rgb(self, lab, use_libm=False):
+        """transfer::LabToRGB (transfer.cpp:200-226) of n pixels, clamped to [0, 255] and not yet truncated"""
+        return self._per_pixel(self.lib.oracle_transfer_lab_to_rgb, lab, use_libm)
+
     def bmp_decode(self, data):
         """bytes of a BMP file -> (rc, planar (3,H,W) uint8 or None)"""
         buf = np.frombuffer(bytes(data), np.uint8)
@@ -305,6 +331,10 @@ def have_reference():
     return os.path.exists(REF_SO)
 
 
+def have_reference_transfer():
+    return os.path.exists(REF_TRANSFER_SO)
+
+
 class ReferenceEx6:
     """The `src/ex6` variant's own blend (src/ex6/ImageProcess.cpp:638-742, oracle/ref6_harness.cpp)."""
 
@@ -322,8 +352,43 @@ class Reference:
     """The reference's own functions (oracle/ref_harness.cpp).  Only for pinning the oracle and for
     generating tests/golden; exists only where /root/reference was available to oracle/Makefile."""
 
-    def __init__(self):
-        self.lib = C.CDLL(REF_SO)
+    @property
+    def lib(self):
+        """libref_hotpath.so, loaded on first use"""
+        if not hasattr(self, "_lib"):
+            self._lib = C.CDLL(REF_SO)
+        return self._lib
+
+    @property
+    def tlib(self):
+        """libref_transfer.so, loaded on first use (have_reference_transfer() says whether it is there)"""
+        if not hasattr(self, "_tlib"):
+            self._tlib = C.CDLL(REF_TRANSFER_SO)
+        return self._tlib
+
+    def transfer(self, src, tem):
+        """transfer::transfer (transfer.cpp:4-13) -> (out, stats[12] = mean_src, sd_src, mean_tem, sd_tem)"""
+        src, tem = _img(src, np.uint8), _img(tem, np.uint8)
+        out, st = np.empty_like(src), np.zeros(12, np.float32)
+        rc = self.tlib.ref_transfer_u8(_p(src), src.shape[2], src.shape[1], _p(tem), tem.shape[2], tem.shape[1], _p(out), _p(st))
+        assert rc == 0, rc
+        return out, st
+
+    def _per_pixel(self, fn, px):
+        px = np.ascontiguousarray(px, np.float32)
+        assert px.ndim == 2 and px.shape[1] == 3, px.shape
+        out = np.empty_like(px)
+        fn.restype = None
+        fn(_p(px), _p(out), C.c_longlong(px.shape[0]))
+        return out
+
+    def rgb_to_lab(self, rgb):
+        """the static transfer::RGBtoLab of n pixels: (n, 3) float32 -> (n, 3) float32"""
+        return self._per_pixel(self.tlib.ref_transfer_rgb_to_lab, rgb)
+
+    def lab_to_rgb(self, lab):
+        """the static transfer::LabToRGB of n pixels: (n, 3) float32 -> (n, 3) float32"""
+        return self._per_pixel(self.tlib.ref_transfer_lab_to_rgb, lab)
 
     def project(self, src):
         src = _img(src, np.uint8)

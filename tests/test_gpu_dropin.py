@@ -77,7 +77,7 @@ print("RESULT " + json.dumps({"rc": rc, "equal": bool(np.array_equal(got, want))
 
 
 def test_transfer_class_binding():
-    """The reference's `transfer` class (transfer.h; its own transfer.cpp needs the Win32 thread API) constructed exactly
+    """The reference's `transfer` class (transfer.h, as the adaptor defines it) constructed exactly
     as ImageProcess.cpp:180 would -- output aliasing the source -- runs on the HIP path and equals the CPU restatement."""
     need(DROPIN)
     out = subprocess.run([sys.executable, "-c", TRANSFER_SCRIPT, DROPIN, HERE], capture_output=True, text=True, timeout=300)

@@ -817,7 +817,7 @@ def test_bmp_refusals(st, gpu):
 
 @pytest.mark.parametrize("sw,sh,tw,th", [(384, 512, 384, 512), (300, 200, 97, 61), (257, 129, 640, 360), (16, 16, 5, 3), (1, 1, 2, 2), (1000, 1000, 333, 77)])
 def test_colour_transfer(st, gpu, oracle, sw, sh, tw, th):
-    """SURVEY.md 8(f) row 4 (transfer.cpp; parity unpinned, see include/stitch.h): the HIP path equals the CPU
+    """SURVEY.md 8(f) row 4 (transfer.cpp; pinned to the reference in test_gpu_transfer.py, see include/stitch.h): the HIP path equals the CPU
     restatement bit for bit -- the uchar result AND the twelve float statistics, whose serial float running sums are the
     order-sensitive part (sizes that are not multiples of the 256-sample staging block included)."""
     import torch

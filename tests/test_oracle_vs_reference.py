@@ -1,7 +1,8 @@
 """CPU: the oracle against the reference's own functions on fixed seeded inputs.
 
 The reference runs where oracle/Makefile could compile it (oracle/_ref/libref_hotpath.so, libref6_hotpath.so); everywhere
-else its results for exactly these inputs are replayed from tests/golden/reference_results.json.  A result is kept as what
+else its results for exactly these inputs are replayed from tests/golden/reference_results.json (the colour transfer, whose last bit belongs to the platform's libm, has a
+recording of its own: tests/golden/transfer.npz, see the section at the end).  A result is kept as what
 the comparison needs: a digest of an array's shape and values (as float64, so -0.0 == 0.0 as in np.array_equal), numbers
 as they are; the key is the function and a digest of its inputs, so changed inputs find no recording and fail.  Where the
 reference is built, every result is also checked against its recording; STITCH_RECORD_REFERENCE=1 rewrites the recording
@@ -13,7 +14,8 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import REF6_SO, Reference, ReferenceEx6, have_reference
+import transfer_cases as T
+from oracle_lib import REF6_SO, Reference, ReferenceEx6, have_reference, have_reference_transfer
 
 RECORDING = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_results.json")
 
@@ -271,3 +273,92 @@ def test_blend_ex6_random_sizes_sweep(oracle, ref6):
             continue  # empty mid row / no overlap / degenerate pyramid: the variant hangs or divides 0/0 there
         assert digest(out) == ref6.blend(A, B), (w, h)
         done += 1
+
+
+# ---- the l-alpha-beta colour transfer against the reference's transfer.cpp (oracle/ref_transfer.cpp) ----------------------
+# Two modes.  With use_libm the restatement calls the same logf / pow as the reference built next to it, so the two must agree
+# in every bit: that pins every promotion, the order of the running sums, the == 0 -> 1 rule, the clamps, the final cast and
+# the layout of the statistics.  Live only, because the bits belong to the libm both sides share.  Without it the restatement
+# evaluates include/stitch_elem.h (what the HIP kernels evaluate), which is the same on every platform: its result is replayed
+# from tests/golden/transfer.npz, which also holds the few bytes where a glibc build of the reference differs.
+@pytest.fixture(scope="module")
+def ref_transfer():
+    if not have_reference_transfer():
+        pytest.skip("the reference's transfer is not built here (make -C oracle ref); the replay tests below run everywhere")
+    return Reference()
+
+
+@pytest.fixture(scope="module")
+def transfer_recording():
+    return T.Recording()
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("name,rs,rt", T.CASES, ids=T.CASE_NAMES)
+def test_transfer_libm_mode_is_the_reference(oracle, ref_transfer, name, rs, rt):
+    """oracle.transfer(use_libm=True) == transfer::transfer of the reference: every output byte, every bit of the twelve
+    statistics.  The cases are what transfer.cpp distinguishes (tests/transfer_cases.py says which is which)."""
+    src, tem = T.build_image(rs, oracle), T.build_image(rt, oracle)
+    want, wst = ref_transfer.transfer(src, tem)
+    got, gst = oracle.transfer(src, tem, use_libm=True)
+    assert np.array_equal(bits(gst), bits(wst)), (gst, wst)
+    assert np.array_equal(got, want), int((got != want).sum())
+
+
+def test_transfer_per_pixel_every_colour(oracle, ref_transfer):
+    """The reference's two public per-pixel functions against the restatement's (libm mode), bit for bit: RGBtoLab for all
+    2^24 colours, LabToRGB for the l-alpha-beta values those colours give, shifted and scaled so that the clamps at 0 and
+    255 are both met."""
+    rgb = np.ascontiguousarray(T.every_colour(1).reshape(3, -1).T, np.float32)
+    want = ref_transfer.rgb_to_lab(rgb)
+    assert np.array_equal(bits(oracle.rgb_to_lab(rgb, use_libm=True)), bits(want))
+    lab = want[::7] * np.float32(1.25) - np.float32(0.5)
+    back = ref_transfer.lab_to_rgb(lab)
+    assert back.min() == 0 and back.max() == 255
+    assert np.array_equal(bits(oracle.lab_to_rgb(lab, use_libm=True)), bits(back))
+
+
+def test_transfer_without_libm_dependence(oracle, ref):
+    """Where no libm rounding enters, both modes of the restatement equal the reference on any platform, so these go through
+    the recording: black images (log(1) = 0, sd = 0, 0 * 0 / 0 = NaN through pow and the clamps), and LabToRGB of values
+    whose powers are 0, 1, inf or NaN (IEEE pow fixes those)."""
+    inf, nan = np.float32(np.inf), np.float32(np.nan)
+    lab = np.array([[0, 0, 0], [inf, 0, 0], [-inf, 0, 0], [nan, 0, 0], [0, inf, 0], [0, -inf, 0], [0, 0, inf], [0, 0, -inf], [0, nan, 0], [0, 0, nan],
+                    [1e30, 0, 0], [-1e30, 0, 0], [0, 1e30, 0], [0, -1e30, 0], [0, 0, 1e30], [0, 0, -1e30], [inf, -inf, 0], [nan, inf, -inf]], np.float32)
+    want = ref.lab_to_rgb_bits(lab)
+    black, black_tem = np.zeros((3, 17, 20), np.uint8), np.zeros((3, 3, 5), np.uint8)
+    want_t = ref.transfer(black, black_tem)
+    for use_libm in (False, True):
+        assert digest(bits(oracle.lab_to_rgb(lab, use_libm=use_libm))) == want
+        out, st = oracle.transfer(black, black_tem, use_libm=use_libm)
+        assert digest([out, st]) == want_t and not out.any() and not st.any()
+
+
+def test_transfer_recording_covers_the_cases(transfer_recording):
+    assert list(transfer_recording.cases) == T.CASE_NAMES
+    m = transfer_recording.meta
+    assert m["total_differing_bytes"] == sum(c["differing_bytes"] for c in m["cases"].values()) <= 1e-5 * m["total_bytes"]
+
+
+@pytest.mark.parametrize("name", T.CASE_NAMES)
+def test_transfer_specified_mode_replay(oracle, transfer_recording, name):
+    """oracle.transfer with the specified functions of include/stitch_elem.h against the recording, no tolerance: its bytes
+    and statistic bits are the recorded specified-function ones, and with the recorded differing bytes (each one grey level,
+    18 of 1.06e8 over all cases) replaced it IS the reference's output, by SHA-256 and in full where the output is stored."""
+    c = transfer_recording.cases[name]
+    src, tem = transfer_recording.images(name, oracle)
+    assert sha(src) == c["src_sha256"] and sha(tem) == c["tem_sha256"]
+    out, st = oracle.transfer(src, tem)
+    assert list(out.shape) == c["shape"] and sha(out) == c["spec_sha256"]
+    assert [int(v) for v in bits(st)] == c["spec_stats_bits"]
+    as_ref = transfer_recording.as_reference(name, out)
+    assert sha(as_ref) == c["ref_sha256"]
+    pos, ref_b, spec_b = transfer_recording.diffs(name)
+    assert pos.size == c["differing_bytes"] and np.all(np.abs(ref_b.astype(int) - spec_b.astype(int)) == 1)
+    full = transfer_recording.ref_out(name)
+    assert (full is not None) == (out.nbytes <= T.FULL_OUTPUT_LIMIT)
+    if full is not None:
+        assert np.array_equal(as_ref, full)
