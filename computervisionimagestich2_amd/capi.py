@@ -133,6 +133,14 @@ PANORAMA_SIGNATURES = _signatures(
     ("stitch_panorama_copy", i32, vp, i32, vp, sz, i32, vp),
 )
 
+# The same for include/stitch_rig.h, a calibrated rig; tests/test_rig_host.py holds it to that header.
+RIG_SIGNATURES = _signatures(
+    ("stitch_rig_opts_default stitch_rig_destroy", None, vp), ("stitch_rig_create", i32, vp, i32, i32, vp, i32, vp, vp),
+    ("stitch_rig_from_panorama", i32, vp, vp, i32, vp, vp), ("stitch_rig_info", i32, vp, vp, vp, vp, vp, vp), ("stitch_rig_step_plan", vp, vp, i32),
+    ("stitch_dev_rig_stitch_u8", i32, vp, vp, i32, vp, vp, vp, vp), ("stitch_dev_project_many_u8", i32, vp, vp, i32, i32, i32, f32, vp),
+    ("stitch_dev_finish_many_u8", i32, vp, i32, i32, i32, f64, f64, vp),
+)
+
 _lib = None
 
 
@@ -151,7 +159,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -1157,3 +1165,162 @@ class Band(_Handle):
         s = Seam()
         _chk(lib().stitch_band_status(self._h, C.byref(s)))
         return s
+
+
+# ---- a calibrated rig: include/stitch_rig.h ---------------------------------------------------------------------------------
+class Panorama(_Handle):
+    """stitch_panorama: the result handle of a whole-panorama call, kept open (dev_panorama_handle) -- what Rig.from_panorama reads."""
+    _destroy = "stitch_panorama_destroy"
+
+    def __init__(self, h, device):
+        self._h, self.device = h, device
+        w, ht, start, ns = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().stitch_panorama_info(h, C.byref(w), C.byref(ht), C.byref(start), C.byref(ns)))
+        self.width, self.height, self.start, self.n_steps = w.value, ht.value, start.value, ns.value
+
+    def mosaic(self):
+        """A copy of the mosaic as a (3, height, width) uint8 tensor, complete when this returns."""
+        import torch
+        out = torch.empty((3, self.height, self.width), dtype=torch.uint8, device=self.device)
+        _chk(lib().stitch_panorama_copy(self._h, -1, _dp(out), out.numel(), 1, _stream()))
+        torch.cuda.current_stream().synchronize()
+        return out
+
+
+def dev_panorama_handle(frames, opts=None, finish=True, num=19.0, den=20.0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None,
+                        ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+    """dev_panorama, but the result stays behind its handle -> Panorama (close() it when done)."""
+    frames, arr = _frames_u8(frames)
+    keep, h = [], C.c_void_p()
+    o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, False, ratio, match_threshold, fov_deg, keep)
+    _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
+    return Panorama(h, frames[0].device)
+
+
+class RigOpts(C.Structure):
+    """stitch_rig_opts; the defaults are stitch_rig_opts_default's."""
+    _fields_ = [("blend", C.c_void_p), ("fov_deg", C.c_float), ("finish", C.c_int32), ("num", C.c_double), ("den", C.c_double),
+                ("max_sets", C.c_int32)]
+
+
+def _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep):
+    o = RigOpts()
+    lib().stitch_rig_opts_default(C.byref(o))
+    if opts is not None:
+        keep.append(_opts(opts))  # the library copies it during creation
+        o.blend = C.addressof(keep[-1])
+    o.fov_deg, o.finish, o.num, o.den, o.max_sets = float(fov_deg), int(bool(finish)), float(num), float(den), int(max_sets)
+    return o
+
+
+def rig_steps(steps, start=None):
+    """Step dicts -> (start, PanoramaStep array).  The dicts are those of dev_panorama(return_steps=True), pipeline.stitch_chain and
+    tests/golden/golden.json: start, src, p, p_fwd, offx, offy, ox, oy, cw, ch.  In them `src` is the frame that is WARPED -- `dst`
+    of stitch_panorama_step -- and `p` the backward map; the frame already in the mosaic ("mosaic_src", where a dict has it) goes
+    into stitch_panorama_step's src, which no step depends on."""
+    steps = list(steps)
+    arr = (PanoramaStep * max(len(steps), 1))()
+    for d, st in zip(arr, steps):
+        d.src, d.dst = int(st.get("mosaic_src", -1)), int(st["src"])
+        d.p_fwd, d.p_bwd = _map8(st["p_fwd"]), _map8(st["p"])
+        d.geom = StepGeom(float(st["offx"]), float(st["offy"]), int(st["cw"]), int(st["ch"]), int(st["ox"]), int(st["oy"]))
+    if start is None:
+        start = steps[0]["start"]
+    return int(start), arr
+
+
+class Rig(_Handle):
+    """stitch_rig: the recorded stitch order, maps and canvases of a panorama, replayed on many frame sets -- step k of all the
+    sets of a call is one batched launch sequence."""
+    _destroy = "stitch_rig_destroy"
+
+    def __init__(self, h):
+        self._h = h
+        v = [C.c_int() for _ in range(5)]
+        _chk(lib().stitch_rig_info(h, *[C.byref(x) for x in v]))
+        self.width, self.height, self.n_frames, self.n_steps, self.max_sets = (x.value for x in v)
+
+    @classmethod
+    def from_steps(cls, frame_sizes, start, steps, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0):
+        """stitch_rig_create (host only): frame_sizes = (width, height) of every decoded frame; steps = step dicts as rig_steps
+        takes them (`src` is the WARPED frame) or a ready PanoramaStep array; start may be None to take steps[0]["start"]."""
+        if isinstance(steps, C.Array):
+            arr, n_steps = steps, len(steps)
+        else:
+            steps = list(steps)
+            n_steps = len(steps)
+            start, arr = rig_steps(steps, start) if steps else (start, (PanoramaStep * 1)())
+        wh = np.ascontiguousarray(np.array(frame_sizes, np.int32).reshape(-1, 2))
+        keep, h = [], C.c_void_p()
+        o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
+        _chk(lib().stitch_rig_create(_p(wh), wh.shape[0], int(start), arr, n_steps, C.byref(o), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_panorama(cls, pano, frames, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0):
+        """stitch_rig_from_panorama: pano is a Panorama (dev_panorama_handle), frames the tensors it was made from (sizes only)."""
+        arr = (FrameU8 * max(len(frames), 1))(*[FrameU8(None, f.shape[2], f.shape[1]) for f in frames])
+        keep, h = [], C.c_void_p()
+        o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
+        _chk(lib().stitch_rig_from_panorama(pano._h, arr, len(frames), C.byref(o), C.byref(h)))
+        return cls(h)
+
+    def step_plan(self, k):
+        """stitch_rig_step_plan: the address of the batched workspace step k runs on (None before the first stitch call)."""
+        return lib().stitch_rig_step_plan(self._h, int(k))
+
+    def stitch(self, sets, out=None):
+        """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for.  sets: a list of frame sets, each a list of
+        n_frames (3, H, W) uint8 device tensors.  Returns (outputs, statuses, seams): one (3, height, width) tensor per set, each
+        set's status (OK, ERR_EMPTY_MIDROW or ERR_ZERO_OVERLAP: a failed set does not raise, the others are valid), and per set the
+        Seam tuples of its steps.  self.last_rc keeps the call's return value (the status of the first set that is not OK).
+        Anything else -- a bad argument, a failed HIP call, a hand-off time-out -- raises StitchError."""
+        import torch
+        sets = [list(fs) for fs in sets]
+        flat = [f for fs in sets for f in fs]
+        if any(len(fs) != self.n_frames for fs in sets):
+            raise ValueError(f"every set has {self.n_frames} frames")
+        flat, arr = _frames_u8(flat)
+        n_sets = len(sets)
+        if out is None:
+            out = [torch.empty((3, self.height, self.width), dtype=torch.uint8, device=flat[0].device) for _ in range(n_sets)]
+        out = [_timg(o) for o in out]
+        if len(out) != n_sets or any(tuple(o.shape) != (3, self.height, self.width) or o.dtype != torch.uint8 for o in out):
+            raise ValueError(f"one (3, {self.height}, {self.width}) uint8 output per set")
+        ptrs = (C.c_void_p * max(n_sets, 1))(*[o.data_ptr() for o in out])
+        status = (C.c_int32 * max(n_sets, 1))()
+        seams = (Seam * max(n_sets * self.n_steps, 1))()
+        rc = lib().stitch_dev_rig_stitch_u8(self._h, arr, n_sets, ptrs, status, seams, _stream())
+        statuses = list(status[:n_sets])
+        seam_rows = [[seams[i * self.n_steps + k].as_tuple() for k in range(self.n_steps)] for i in range(n_sets)]
+        self.last_rc = rc
+        if rc < 0 and rc not in (ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP):
+            raise StitchError(rc, lib().stitch_last_error().decode())
+        return out, statuses, seam_rows
+
+
+def _ptr_table(tensors):
+    return (C.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+
+
+def dev_project_many(srcs, fov_deg=15.0, out=None):
+    """stitch_dev_project_many_u8: same-size (3, H, W) uint8 device tensors through ONE projection launch -> list of tensors."""
+    import torch
+    srcs = [_timg(t) for t in srcs]
+    out = [torch.empty_like(t) for t in srcs] if out is None else list(out)
+    _, h, w = srcs[0].shape
+    if any(tuple(t.shape) != (3, h, w) or t.dtype != torch.uint8 for t in srcs + out) or len(out) != len(srcs):
+        raise ValueError("expected uint8 images of one size, and one output per image")
+    _chk(lib().stitch_dev_project_many_u8(_ptr_table(srcs), _ptr_table(out), len(srcs), w, h, fov_deg, _stream()))
+    return out
+
+
+def dev_finish_many(results, num=19.0, den=20.0):
+    """stitch_dev_finish_many_u8: the finish pass on same-size (3, H, W) uint8 device tensors, in place, in three launches."""
+    import torch
+    results = [_timg(t) for t in results]
+    _, h, w = results[0].shape
+    if any(tuple(t.shape) != (3, h, w) or t.dtype != torch.uint8 for t in results):
+        raise ValueError("expected uint8 mosaics of one size")
+    _chk(lib().stitch_dev_finish_many_u8(_ptr_table(results), len(results), w, h, num, den, _stream()))
+    return results

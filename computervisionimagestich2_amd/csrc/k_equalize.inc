@@ -94,8 +94,10 @@ __device__ __forceinline__ unsigned luma_bin(unsigned r, unsigned g, unsigned b)
 // Y histogram (equalization.cpp:104-107): each wavefront owns a private 256-bin LDS histogram (no cross-wave
 // contention), the workgroup's wavefronts are summed through LDS, and each bin is flushed with one global
 // atomic per workgroup.  Four pixels per work-item per step (uchar4 loads when the plane size allows).
+// (The bodies of these kernels are device functions so that the many-mosaic forms of k_rig.inc run them per mosaic of a batch:
+// blockIdx.x / gridDim.x address the samples.)
 constexpr int HIST_WAVES = 4;
-__global__ __launch_bounds__(HIST_WAVES * 64) void k_hist(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
+__device__ __forceinline__ void hist_bytes(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
     __shared__ int lh[HIST_WAVES][256];
     const int wid = threadIdx.x >> 6;
     for (int i = threadIdx.x; i < HIST_WAVES * 256; i += blockDim.x) (&lh[0][0])[i] = 0;
@@ -112,12 +114,15 @@ __global__ __launch_bounds__(HIST_WAVES * 64) void k_hist(const uint8_t* __restr
         if (s) atomicAdd(&hist[b], s);
     }
 }
+__global__ __launch_bounds__(HIST_WAVES * 64) void k_hist(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
+    hist_bytes(img, n, hist);
+}
 
 // CDF and LUT (equalization.cpp:110-124): p_i = hist_i / total for all bins side by side (the divisions are independent),
 // then the running sum as 256 sequential double additions on one lane -- its order is the reference's, so the sum is
 // bit-identical -- then lut_i = round(255 cdf_i) side by side again; round() is half-away-from-zero.  (All on one lane this took
 // 20 us -- a sixth of an equalisation of 25 MPix: every iteration waited for a double-precision divide.)
-__global__ __launch_bounds__(256) void k_lut(const int32_t* __restrict__ hist, int w, int h, int32_t* __restrict__ lut) {
+__device__ __forceinline__ void lut_of_hist(const int32_t* __restrict__ hist, int w, int h, int32_t* __restrict__ lut) {
     __shared__ double pc[256];
     const double total = (double)(w * h);
     const int i = threadIdx.x;
@@ -133,11 +138,14 @@ __global__ __launch_bounds__(256) void k_lut(const int32_t* __restrict__ hist, i
     __syncthreads();
     lut[i] = (int32_t)round(255.0 * pc[i]);
 }
+__global__ __launch_bounds__(256) void k_lut(const int32_t* __restrict__ hist, int w, int h, int32_t* __restrict__ lut) {
+    lut_of_hist(hist, w, h, lut);
+}
 
 // apply (equalization.cpp:127-130 + :92-99), in place; FUSE_MIX additionally performs M1 so that the equalised
 // copy never exists in memory (stitch_dev_finish_u8).
 template <bool FUSE_MIX>
-__global__ __launch_bounds__(256) void k_equalize_apply(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, MixK mk) {
+__device__ __forceinline__ void equalize_apply_bytes(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, const MixK& mk) {
     __shared__ int slut[256];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) slut[i] = lut[i];
     __syncthreads();
@@ -159,6 +167,10 @@ __global__ __launch_bounds__(256) void k_equalize_apply(uint8_t* __restrict__ im
         img[i + n] = o1;
         img[i + 2 * n] = o2;
     }
+}
+template <bool FUSE_MIX>
+__global__ __launch_bounds__(256) void k_equalize_apply(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, MixK mk) {
+    equalize_apply_bytes<FUSE_MIX>(img, n, lut, mk);
 }
 
 // M1 stand-alone, ImageProcess.cpp:240-268
@@ -188,7 +200,7 @@ typedef unsigned u4a __attribute__((ext_vector_type(4), aligned(4)));  // 16-byt
 __device__ __forceinline__ void unpack4(unsigned w, float v[4]) {
     v[0] = (float)(w & 255u), v[1] = (float)((w >> 8) & 255u), v[2] = (float)((w >> 16) & 255u), v[3] = (float)(w >> 24);
 }
-__global__ __launch_bounds__(HIST_WAVES * 64) void k_hist4(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
+__device__ __forceinline__ void hist_words(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
     __shared__ int lh[HIST_WAVES * HIST_COPIES * HIST_PITCH];
     for (int i = threadIdx.x; i < HIST_WAVES * HIST_COPIES * HIST_PITCH; i += blockDim.x) lh[i] = 0;
     __syncthreads();
@@ -224,9 +236,12 @@ __global__ __launch_bounds__(HIST_WAVES * 64) void k_hist4(const uint8_t* __rest
         if (s_) atomicAdd(&hist[bin], s_);
     }
 }
+__global__ __launch_bounds__(HIST_WAVES * 64) void k_hist4(const uint8_t* __restrict__ img, size_t n, int32_t* __restrict__ hist) {
+    hist_words(img, n, hist);
+}
 
 template <bool FUSE_MIX>
-__global__ __launch_bounds__(256) void k_equalize_apply4(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, MixK mk) {
+__device__ __forceinline__ void equalize_apply_words(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, const MixK& mk) {
     __shared__ int slut[256];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) slut[i] = lut[i];
     __syncthreads();
@@ -280,4 +295,8 @@ __global__ __launch_bounds__(256) void k_equalize_apply4(uint8_t* __restrict__ i
         pg[i] = b;
         pb[i] = c;
     }
+}
+template <bool FUSE_MIX>
+__global__ __launch_bounds__(256) void k_equalize_apply4(uint8_t* __restrict__ img, size_t n, const int32_t* __restrict__ lut, MixK mk) {
+    equalize_apply_words<FUSE_MIX>(img, n, lut, mk);
 }

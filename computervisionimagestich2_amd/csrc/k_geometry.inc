@@ -2,10 +2,10 @@
 // ---- P1: cylindrical projection, Projection.cpp:20-73 ------------------------------------------------------
 // One output pixel (three channels) per work-item; r is computed on the host (tan).  Writes 0 where the
 // source coordinate falls outside, so no memset pass is needed.
+// (The body is a device function so that k_project_many, k_rig.inc, runs it per image of a batch: blockIdx.x / .y address the pixel.)
 template <typename PX>
-__global__ __launch_bounds__(256) void k_project(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h,
-                                                 int flag, int width, int height, float r, uint8_t* __restrict__ gray,
-                                                 float* __restrict__ gray_f32) {
+__device__ __forceinline__ void project_untiled(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, int flag, int width, int height,
+                                                float r, uint8_t* __restrict__ gray, float* __restrict__ gray_f32) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= w) return;
@@ -32,6 +32,12 @@ __global__ __launch_bounds__(256) void k_project(const PX* __restrict__ src, PX*
         if (gray) gray[off] = v;
         if (gray_f32) gray_f32[off] = (float)v;
     }
+}
+template <typename PX>
+__global__ __launch_bounds__(256) void k_project(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h,
+                                                 int flag, int width, int height, float r, uint8_t* __restrict__ gray,
+                                                 float* __restrict__ gray_f32) {
+    project_untiled<PX>(src, dst, w, h, flag, width, height, r, gray, gray_f32);
 }
 
 // ---- W1: the bilinear map, ImageProcess.cpp:465-471 --------------------------------------------------------

@@ -281,9 +281,11 @@ __device__ __noinline__ void project_px_global(const PX* __restrict__ src, PX* _
         }
     }
 }
+// (The tile's work is a device function so that k_project_lds_many, k_rig.inc, runs it per image of a batch: blockIdx.x / .y
+// address the tile.)
 template <typename PX, int TW, int TH>
-__global__ __launch_bounds__(256) void k_project_lds(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
-                                                     uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+__device__ __forceinline__ void project_lds_tile(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
+                                                 uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pj_smem[];
     __shared__ ProjCol corner[4];
     constexpr int CPX = PJ_CHUNK / (int)sizeof(PX);  // pixels per staging chunk
@@ -363,14 +365,19 @@ __global__ __launch_bounds__(256) void k_project_lds(const PX* __restrict__ src,
         pj_emit2<PX>(rd, x, y0, two, w, pl, res, in0, in1, gray, gray_f32);
     }
 }
+template <typename PX, int TW, int TH>
+__global__ __launch_bounds__(256) void k_project_lds(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
+                                                     uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+    project_lds_tile<PX, TW, TH>(src, dst, w, h, r, gray, gray_f32, lds_bytes);
+}
 
 // Landscape frames (the reference's `flag == 1` branch, Projection.cpp:24-26,30-49: the roles of the axes swap): k and the
 // source ROW u depend on the output row alone, the source column v = (x - w/2)/k(y) + w/2 on both.  Same tiling; the per-row
 // terms of a tile's TH rows are evaluated by TH work-items and shared through LDS, the tile's source box is bounded by its
 // first and last row (u grows with y) and, for the columns, by its rows nearest to / farthest from the axis.
 template <typename PX, int TW, int TH>
-__global__ __launch_bounds__(256) void k_project_lds_t(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
-                                                       uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+__device__ __forceinline__ void project_lds_tile_t(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
+                                                   uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pj_smem[];
     __shared__ ProjCol corner[4];
     __shared__ __attribute__((aligned(16))) ProjRow rowc[TH];
@@ -442,4 +449,9 @@ __global__ __launch_bounds__(256) void k_project_lds_t(const PX* __restrict__ sr
         pj_bilinear2<PX>((lds_ptr<uint8_t>)pj_smem, nrow * ncol, oA0, oA1, xc0 - xf0, oB0, oB1, xc1 - xf1, w_ld, w_rd, w_rt, w_lt, res);
         pj_emit2<PX>(rd, x, y0, two, w, pl, res, in0, in1, gray, gray_f32);
     }
+}
+template <typename PX, int TW, int TH>
+__global__ __launch_bounds__(256) void k_project_lds_t(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
+                                                       uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+    project_lds_tile_t<PX, TW, TH>(src, dst, w, h, r, gray, gray_f32, lds_bytes);
 }

@@ -21,6 +21,7 @@
 #include "stitch.h"
 #include "stitch_handoff.h"
 #include "stitch_panorama.h"
+#include "stitch_rig.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -969,6 +970,49 @@ void seam_to_public(const SeamDev& d, stitch_seam* o) {
     o->start = d.start;
 }
 
+// The form a projection of w x h frames runs, decided from the size and from whether the source addresses are 4-byte aligned:
+// source rows tiled into LDS (k_project_lds; k_project_lds_t for landscape frames, where the axes swap roles) when the largest
+// source box of a tile fits the budget -> the LDS bytes of a launch; otherwise (widths that are not a multiple of 4,
+// STITCH_PROJECT1=1) 0: k_project.
+template <typename PX>
+size_t project_lds_bytes(int w, int h, const ProjParams& pp, bool src_aligned4) {
+    constexpr int TW = sizeof(PX) == 1 ? PJ_TW_U8 : PJ_TW_F32, TH = sizeof(PX) == 1 ? PJ_TH_U8 : PJ_TH_F32, CPX = PJ_CHUNK / (int)sizeof(PX);
+    size_t lds = 0;
+    // (float landscape frames stay with k_project: there a wavefront's taps of a row already share their cache lines -- the
+    // source row depends on the output row alone -- and it runs at 0.52 of the roofline, 0.073 ms at 4096 x 3072 against 0.092
+    // through LDS; unsigned char: 0.063 -> 0.050)
+    const bool tiled = (w % 4) == 0 && (unsigned long long)w * h * 3 * sizeof(PX) < 0xfffffff0ULL && src_aligned4 &&
+                       !(pp.flag && sizeof(PX) == 4) && !(Tuning::env_int("STITCH_PROJECT1") > 0);
+    if (!tiled) return 0;
+    // the box of a tile, as the kernel derives it, over the tiles that can have the largest one (those farthest from the
+    // axis and from the middle: the four corner tiles), plus a margin of two rows and two chunks.  `along` = the axis k
+    // depends on (columns for portrait frames, rows for landscape ones), `across` the other.
+    const int n_al = pp.flag ? h : w, n_ac = pp.flag ? w : h;
+    auto k_of = [&](int i) {
+        const float d = (float)(i - n_al / 2);
+        const double rd = (double)pp.r, dd = (double)d;
+        return (float)(rd / std::sqrt(rd * rd + dd * dd));
+    };
+    auto u_of = [&](int i) { return (float)(i - n_al / 2) / k_of(i) + (float)(n_al / 2); };
+    auto v_of = [&](int j, float k) { return (float)(j - n_ac / 2) / k + (float)(n_ac / 2); };
+    const int t_al = pp.flag ? TH : TW, t_ac = pp.flag ? TW : TH;  // tile extent along / across
+    const int nt_al = (n_al + t_al - 1) / t_al, nt_ac = (n_ac + t_ac - 1) / t_ac;
+    for (int bc : {0, nt_ac - 1})
+        for (int ba : {0, nt_al - 1}) {
+            const int ia = ba * t_al, ib = std::min(ia + t_al, n_al) - 1, ja = bc * t_ac, jb = std::min(ja + t_ac, n_ac) - 1;
+            const int mid = n_al / 2, inear = ia <= mid && mid <= ib ? mid : (std::abs(ia - mid) < std::abs(ib - mid) ? ia : ib),
+                      ifar = std::abs(ia - mid) > std::abs(ib - mid) ? ia : ib;
+            const float kn = k_of(inear), kf = k_of(ifar);
+            const float vs[4] = {v_of(ja, kn), v_of(ja, kf), v_of(jb, kn), v_of(jb, kf)};
+            const float vmin = std::min(std::min(vs[0], vs[1]), std::min(vs[2], vs[3])), vmax = std::max(std::max(vs[0], vs[1]), std::max(vs[2], vs[3]));
+            const long n_across = (long)std::ceil(vmax) - (long)std::floor(vmin) + 1, n_along = (long)std::ceil(u_of(ib)) - (long)std::floor(u_of(ia)) + 1;
+            const long rows = (pp.flag ? n_along : n_across) + 2;
+            const long cols = ((pp.flag ? n_across : n_along) + 2 * CPX + CPX - 1) / CPX * CPX;
+            lds = std::max(lds, pj_box_bytes<PX>((size_t)rows * cols));
+        }
+    return lds <= 60 * 1024 ? lds : 0;
+}
+
 template <typename PX>
 int dev_project(const PX* d_src, int w, int h, float fov_deg, PX* d_dst, void* stream, uint8_t* d_gray = nullptr,
                 float* d_gray_f32 = nullptr) {
@@ -976,44 +1020,9 @@ int dev_project(const PX* d_src, int w, int h, float fov_deg, PX* d_dst, void* s
     if (rc) return rc;
     if (!d_src || !d_dst || w <= 0 || h <= 0) return fail(STITCH_ERR_ARG, "project: null buffer or bad size %dx%d", w, h);
     const ProjParams pp = proj_params(w, h, fov_deg);
-    // source rows tiled into LDS (k_project_lds; k_project_lds_t for landscape frames, where the axes swap roles) when the
-    // largest source box of a tile fits the budget; otherwise (widths that are not a multiple of 4, STITCH_PROJECT1=1): k_project
-    constexpr int TW = sizeof(PX) == 1 ? PJ_TW_U8 : PJ_TW_F32, TH = sizeof(PX) == 1 ? PJ_TH_U8 : PJ_TH_F32, CPX = PJ_CHUNK / (int)sizeof(PX);
-    size_t lds = 0;
-    // (float landscape frames stay with k_project: there a wavefront's taps of a row already share their cache lines -- the
-    // source row depends on the output row alone -- and it runs at 0.52 of the roofline, 0.073 ms at 4096 x 3072 against 0.092
-    // through LDS; unsigned char: 0.063 -> 0.050)
-    bool tiled = (w % 4) == 0 && (unsigned long long)w * h * 3 * sizeof(PX) < 0xfffffff0ULL && (reinterpret_cast<uintptr_t>(d_src) % 4) == 0 &&
-                 !(pp.flag && sizeof(PX) == 4) && !(Tuning::env_int("STITCH_PROJECT1") > 0);
-    if (tiled) {
-        // the box of a tile, as the kernel derives it, over the tiles that can have the largest one (those farthest from the
-        // axis and from the middle: the four corner tiles), plus a margin of two rows and two chunks.  `along` = the axis k
-        // depends on (columns for portrait frames, rows for landscape ones), `across` the other.
-        const int n_al = pp.flag ? h : w, n_ac = pp.flag ? w : h;
-        auto k_of = [&](int i) {
-            const float d = (float)(i - n_al / 2);
-            const double rd = (double)pp.r, dd = (double)d;
-            return (float)(rd / std::sqrt(rd * rd + dd * dd));
-        };
-        auto u_of = [&](int i) { return (float)(i - n_al / 2) / k_of(i) + (float)(n_al / 2); };
-        auto v_of = [&](int j, float k) { return (float)(j - n_ac / 2) / k + (float)(n_ac / 2); };
-        const int t_al = pp.flag ? TH : TW, t_ac = pp.flag ? TW : TH;  // tile extent along / across
-        const int nt_al = (n_al + t_al - 1) / t_al, nt_ac = (n_ac + t_ac - 1) / t_ac;
-        for (int bc : {0, nt_ac - 1})
-            for (int ba : {0, nt_al - 1}) {
-                const int ia = ba * t_al, ib = std::min(ia + t_al, n_al) - 1, ja = bc * t_ac, jb = std::min(ja + t_ac, n_ac) - 1;
-                const int mid = n_al / 2, inear = ia <= mid && mid <= ib ? mid : (std::abs(ia - mid) < std::abs(ib - mid) ? ia : ib),
-                          ifar = std::abs(ia - mid) > std::abs(ib - mid) ? ia : ib;
-                const float kn = k_of(inear), kf = k_of(ifar);
-                const float vs[4] = {v_of(ja, kn), v_of(ja, kf), v_of(jb, kn), v_of(jb, kf)};
-                const float vmin = std::min(std::min(vs[0], vs[1]), std::min(vs[2], vs[3])), vmax = std::max(std::max(vs[0], vs[1]), std::max(vs[2], vs[3]));
-                const long n_across = (long)std::ceil(vmax) - (long)std::floor(vmin) + 1, n_along = (long)std::ceil(u_of(ib)) - (long)std::floor(u_of(ia)) + 1;
-                const long rows = (pp.flag ? n_along : n_across) + 2;
-                const long cols = ((pp.flag ? n_across : n_along) + 2 * CPX + CPX - 1) / CPX * CPX;
-                lds = std::max(lds, pj_box_bytes<PX>((size_t)rows * cols));
-            }
-        tiled = lds <= 60 * 1024;
-    }
+    constexpr int TW = sizeof(PX) == 1 ? PJ_TW_U8 : PJ_TW_F32, TH = sizeof(PX) == 1 ? PJ_TH_U8 : PJ_TH_F32;
+    const size_t lds = project_lds_bytes<PX>(w, h, pp, (reinterpret_cast<uintptr_t>(d_src) % 4) == 0);
+    const bool tiled = lds > 0;
     const dim3 tgrid((w + TW - 1) / TW, (h + TH - 1) / TH);
     if (tiled && !pp.flag)
         k_project_lds<PX, TW, TH><<<tgrid, 256, lds, as_stream(stream)>>>(d_src, d_dst, w, h, pp.r, d_gray, d_gray_f32, (int)lds);
@@ -2549,3 +2558,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_ransac.inc"
 #include "stitch_sift.inc"
 #include "stitch_panorama.inc"
+#include "stitch_rig.inc"

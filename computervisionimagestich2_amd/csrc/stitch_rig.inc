@@ -1,0 +1,441 @@
+// stitch_rig.inc -- a calibrated rig: the recorded steps of one panorama replayed on many frame sets (include/stitch_rig.h;
+// kernels in k_rig.inc).  Included at the end of stitch_hip.hip (one translation unit).
+//
+// The replay restates pipeline.py's stitch_chain for up to max_sets sets per launch sequence: the projections of a frame index,
+// every step (stitch_dev_pairs_u8 on a batched workspace the rig owns) and the finish pass are each ONE launch sequence over
+// the sets.  No bit can differ from the single-set chain: a pair of a batch does not depend on its neighbours, and the
+// many-image kernels run the single-image kernels' device functions per image.
+struct stitch_rig {
+    // ---- the description (host only) ----
+    int n = 0, start = 0, max_sets = 16, finish = 1;
+    float fov_deg = 15.0f;
+    double num = 19.0, den = 20.0;
+    bool has_blend = false;
+    stitch_blend_opts blend{};
+    std::vector<int32_t> fw, fh;
+    std::vector<stitch_panorama_step> steps;
+    std::vector<int> needed;  // the frames the replay projects: the start and every step's dst, each once
+    int out_w = 0, out_h = 0;
+    // ---- the workspaces, from the first stitch call on ----
+    int device = -1;
+    std::vector<stitch_plan*> plans;   // one per distinct canvas size
+    std::vector<int> plan_of_step;
+    std::vector<uint8_t*> proj;        // per frame: max_sets projected frames (NULL for a frame no step uses)
+    uint8_t* mosaic[2] = {nullptr, nullptr};  // max_sets mosaics each, `mosaic_bytes` apart
+    size_t mosaic_bytes = 0;
+    const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
+    ~stitch_rig() {
+        for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
+        for (uint8_t* p : proj)
+            if (p) (void)hipFree(p);
+        for (uint8_t* p : mosaic)
+            if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+constexpr int kRigMaxSets = 16, kRigMaxImages = 65535;
+
+bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
+// The sets of a call cut into launch sequences: pipeline.sequence_sizes(n_sets, max_sets, 1), balanced sizes in set order.
+std::vector<int> rig_sequences(int n_sets, int max_sets) {
+    const int m = (n_sets + max_sets - 1) / max_sets;
+    std::vector<int> sizes((size_t)m);
+    for (int i = 0; i < m; ++i) sizes[i] = n_sets / m + (i < n_sets % m ? 1 : 0);
+    return sizes;
+}
+
+// `count` same-size images through one projection launch.  d_tab is the device copy of h_tab (already enqueued); the form is
+// chosen once, from the size and the alignment of ALL sources, and is per image exactly dev_project's.
+int rig_project_many(const RigImage* h_tab, const RigImage* d_tab, int count, int w, int h, float fov_deg, hipStream_t s) {
+    const ProjParams pp = proj_params(w, h, fov_deg);
+    bool aligned = true;
+    for (int i = 0; i < count; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(h_tab[i].src) % 4) == 0;
+    const size_t lds = project_lds_bytes<uint8_t>(w, h, pp, aligned);
+    constexpr int TW = PJ_TW_U8, TH = PJ_TH_U8;
+    const dim3 tgrid((w + TW - 1) / TW, (h + TH - 1) / TH, (unsigned)count);
+    if (lds && !pp.flag)
+        k_project_lds_many<TW, TH><<<tgrid, 256, lds, s>>>(d_tab, w, h, pp.r, (int)lds);
+    else if (lds)
+        k_project_lds_t_many<TW, TH><<<tgrid, 256, lds, s>>>(d_tab, w, h, pp.r, (int)lds);
+    else
+        k_project_many<<<grid_xy(w, h, count), 256, 0, s>>>(d_tab, w, h, pp.flag, pp.width, pp.height, pp.r);
+    return launch_check("k_project_many");
+}
+
+// `count` same-size mosaics (the dst entries of the table) through the finish pass in three launches.  d_scratch: RIG_EQ_WORDS
+// int32 per mosaic, the bins zeroed.  The word form only when every mosaic allows it (words_ok).
+int rig_finish_many(const RigImage* h_tab, const RigImage* d_tab, int32_t* d_scratch, int count, int w, int h, double num, double den, hipStream_t s) {
+    const size_t n = (size_t)w * h;
+    bool v4 = true;
+    for (int i = 0; i < count; ++i) v4 = v4 && words_ok(h_tab[i].dst, n);
+    const MixK mk = mix_params(num, den);
+    if (v4) {
+        k_hist_many<true><<<dim3((unsigned)std::min(eq_grid(n / 4), 512), (unsigned)count), HIST_WAVES * 64, 0, s>>>(d_tab, n, d_scratch);
+        k_lut_many<<<(unsigned)count, 256, 0, s>>>(d_scratch, w, h);
+        k_finish_apply_many<true><<<dim3((unsigned)eq_grid(n / 4), (unsigned)count), 256, 0, s>>>(d_tab, n, d_scratch, mk);
+    } else {
+        k_hist_many<false><<<dim3((unsigned)eq_grid(n), (unsigned)count), HIST_WAVES * 64, 0, s>>>(d_tab, n, d_scratch);
+        k_lut_many<<<(unsigned)count, 256, 0, s>>>(d_scratch, w, h);
+        k_finish_apply_many<false><<<dim3((unsigned)eq_grid(n), (unsigned)count), 256, 0, s>>>(d_tab, n, d_scratch, mk);
+    }
+    return launch_check("finish_many");
+}
+
+int rig_cfg(const stitch_rig_opts* opts, stitch_rig* R) {
+    stitch_rig_opts o;
+    if (opts)
+        o = *opts;
+    else
+        stitch_rig_opts_default(&o);
+    if (o.max_sets < 1 || o.max_sets > kRigMaxSets) return fail(STITCH_ERR_ARG, "rig: max_sets = %d outside 1 .. %d", o.max_sets, kRigMaxSets);
+    R->max_sets = o.max_sets;
+    R->finish = o.finish != 0;
+    R->fov_deg = o.fov_deg;
+    R->num = o.num;
+    R->den = o.den;
+    R->has_blend = o.blend != nullptr;
+    if (o.blend) R->blend = *o.blend;
+    return STITCH_OK;
+}
+
+// The workspaces, on the current device.  On failure the rig keeps what it has; the destructor frees it.
+int rig_workspaces(stitch_rig* R) {
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (R->device >= 0) {
+        if (dev != R->device) return fail(STITCH_ERR_ARG, "rig: its workspaces belong to device %d, the current device is %d", R->device, dev);
+        return STITCH_OK;
+    }
+    const int ns = (int)R->steps.size();
+    if (R->plan_of_step.empty()) {
+        std::vector<stitch_plan*> plans;
+        std::vector<int> of((size_t)ns, -1);
+        int rc = STITCH_OK;
+        for (int k = 0; k < ns && !rc; ++k) {
+            const stitch_step_geom& g = R->steps[k].geom;
+            for (int j = 0; j < k && of[k] < 0; ++j)
+                if (R->steps[j].geom.cw == g.cw && R->steps[j].geom.ch == g.ch) of[k] = of[j];
+            if (of[k] >= 0) continue;
+            stitch_plan* p = nullptr;
+            if ((rc = stitch_plan_create_batched(g.cw, g.ch, R->blend_ptr(), R->max_sets, &p))) break;
+            of[k] = (int)plans.size();
+            plans.push_back(p);
+        }
+        if (rc) {
+            for (stitch_plan* p : plans) stitch_plan_destroy(p);
+            return rc;
+        }
+        R->plans = plans;
+        R->plan_of_step = of;
+    }
+    if (R->proj.empty()) R->proj.assign((size_t)R->n, nullptr);
+    for (int f : R->needed)  // (zero steps: the start frame is projected straight into the caller's buffers)
+        if (ns && !R->proj[f]) HIPCHK(hipMalloc((void**)&R->proj[f], (size_t)R->max_sets * 3 * R->fw[f] * R->fh[f]));
+    // steps 0 .. ns-2 write a rig buffer (the last one writes the caller's), in turn: a step never writes the buffer it reads
+    R->mosaic_bytes = 0;
+    for (int k = 0; k + 1 < ns; ++k) R->mosaic_bytes = std::max(R->mosaic_bytes, align256((size_t)3 * R->steps[k].geom.cw * R->steps[k].geom.ch));
+    for (int b = 0; b < std::min(2, ns - 1); ++b)
+        if (!R->mosaic[b]) HIPCHK(hipMalloc((void**)&R->mosaic[b], (size_t)R->max_sets * R->mosaic_bytes));
+    R->device = dev;
+    return STITCH_OK;
+}
+
+// The seam records of the plans' last calls, read before a plan is used again and before the call returns.
+struct RigOutcome {
+    stitch_rig* R;
+    int32_t* set_status;
+    stitch_seam* seams;
+    int n_steps;
+    std::vector<int> pending_step;  // per plan: the step whose records are unread, or -1
+    int set0 = 0, m = 0;            // the sequence in flight
+    int hip_fault = STITCH_OK;
+    std::string hip_text;
+    std::vector<int> fail_step;  // per set: the first step whose seam scan failed, or n_steps
+    RigOutcome(stitch_rig* r, int n_sets, int32_t* st, stitch_seam* sm)
+        : R(r), set_status(st), seams(sm), n_steps((int)r->steps.size()), pending_step(r->plans.size(), -1), fail_step((size_t)n_sets, (int)r->steps.size()) {}
+    // waits for the plan's last call
+    void read(int pi) {
+        const int k = pending_step[pi];
+        if (k < 0) return;
+        pending_step[pi] = -1;
+        for (int i = 0; i < m; ++i) {
+            stitch_seam sm;
+            std::memset(&sm, 0, sizeof sm);
+            const int rc = stitch_plan_status_at(R->plans[pi], i, &sm);
+            const int set = set0 + i;
+            if (rc == STITCH_ERR_HIP) {  // a sticky hand-off time-out (or a failed wait): nothing of this call counts
+                if (!hip_fault) {
+                    hip_fault = rc;
+                    hip_text = g_err;
+                }
+                (void)stitch_plan_clear_fault(R->plans[pi]);
+                return;
+            }
+            if (seams) seams[(size_t)set * n_steps + k] = sm;
+            if (rc != STITCH_OK && k < fail_step[set]) {  // plans are read in plan order, not in step order
+                set_status[set] = rc;
+                fail_step[set] = k;
+            }
+        }
+    }
+    void read_all() {
+        for (size_t pi = 0; pi < pending_step.size(); ++pi) read((int)pi);
+    }
+    // every return path: no plan keeps an unread call or an unacknowledged fault behind
+    ~RigOutcome() {
+        for (size_t pi = 0; pi < pending_step.size(); ++pi)
+            if (pending_step[pi] >= 0 && stitch_plan_status_at(R->plans[pi], 0, nullptr) == STITCH_ERR_HIP) (void)stitch_plan_clear_fault(R->plans[pi]);
+    }
+};
+
+int rig_many_args(const void* a, const void* b, int count, int w, int h, const char* what) {
+    if (!a || !b || count < 1 || count > kRigMaxImages || w <= 0 || h <= 0)
+        return fail(STITCH_ERR_ARG, "%s: null table, %d images (1 .. %d) or bad size %dx%d", what, count, kRigMaxImages, w, h);
+    return STITCH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void stitch_rig_opts_default(stitch_rig_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->fov_deg = 15.0f;
+    o->finish = 1;
+    o->num = 19.0;
+    o->den = 20.0;
+    o->max_sets = kRigMaxSets;
+}
+
+int stitch_rig_create(const int32_t* frame_wh, int n, int start, const stitch_panorama_step* steps, int n_steps, const stitch_rig_opts* opts,
+                      stitch_rig** out) {
+    if (out) *out = nullptr;
+    if (!out || !frame_wh || n_steps < 0 || (n_steps > 0 && !steps)) return fail(STITCH_ERR_ARG, "rig: null argument or %d steps", n_steps);
+    if (n < 1 || n > kPanoMaxFrames) return fail(STITCH_ERR_ARG, "rig: %d frames (1 .. %d)", n, kPanoMaxFrames);
+    std::unique_ptr<stitch_rig> R(new stitch_rig());
+    int rc = rig_cfg(opts, R.get());
+    if (rc) return rc;
+    R->n = n;
+    for (int i = 0; i < n; ++i) {
+        const int w = frame_wh[2 * i], h = frame_wh[2 * i + 1];
+        if (w <= 0 || h <= 0) return fail(STITCH_ERR_ARG, "rig: frame %d has a bad size %d x %d", i, w, h);
+        R->fw.push_back(w);
+        R->fh.push_back(h);
+    }
+    if (start < 0 || start >= n) return fail(STITCH_ERR_ARG, "rig: start frame %d outside 0 .. %d", start, n - 1);
+    R->start = start;
+    R->needed.push_back(start);
+    int mw = R->fw[start], mh = R->fh[start];  // the projection keeps a frame's size
+    for (int k = 0; k < n_steps; ++k) {
+        const stitch_panorama_step& st = steps[k];
+        if (st.dst < 0 || st.dst >= n) return fail(STITCH_ERR_ARG, "rig: step %d warps frame %d, outside 0 .. %d", k, st.dst, n - 1);
+        for (int j = 0; j < 8; ++j)
+            if (!std::isfinite(st.p_fwd[j]) || !std::isfinite(st.p_bwd[j])) return fail(STITCH_ERR_ARG, "rig: step %d has a map coefficient that is not finite", k);
+        stitch_step_geom g;
+        if ((rc = stitch_step_geometry(R->fw[st.dst], R->fh[st.dst], st.p_fwd, mw, mh, &g))) return rc;
+        const stitch_step_geom& r = st.geom;
+        if (!same_bits(g.min_x, r.min_x) || !same_bits(g.min_y, r.min_y) || g.cw != r.cw || g.ch != r.ch || g.ox != r.ox || g.oy != r.oy)
+            return fail(STITCH_ERR_ARG,
+                        "rig: step %d records the canvas %d x %d, offsets (%.9g, %.9g) / (%d, %d); its forward map on a %d x %d mosaic gives %d x %d, "
+                        "(%.9g, %.9g) / (%d, %d)",
+                        k, r.cw, r.ch, (double)r.min_x, (double)r.min_y, r.ox, r.oy, mw, mh, g.cw, g.ch, (double)g.min_x, (double)g.min_y, g.ox, g.oy);
+        if (std::find(R->needed.begin(), R->needed.end(), st.dst) == R->needed.end()) R->needed.push_back(st.dst);
+        R->steps.push_back(st);
+        mw = g.cw;
+        mh = g.ch;
+    }
+    R->out_w = mw;
+    R->out_h = mh;
+    *out = R.release();
+    return STITCH_OK;
+}
+
+int stitch_rig_from_panorama(const stitch_panorama* pano, const stitch_frame_u8* frames, int n, const stitch_rig_opts* opts, stitch_rig** out) {
+    if (out) *out = nullptr;
+    if (!pano || !frames || !out) return fail(STITCH_ERR_ARG, "rig_from_panorama: null argument");
+    if (n < 1 || n > kPanoMaxFrames) return fail(STITCH_ERR_ARG, "rig: %d frames (1 .. %d)", n, kPanoMaxFrames);
+    std::vector<int32_t> wh;
+    for (int i = 0; i < n; ++i) {
+        wh.push_back(frames[i].width);
+        wh.push_back(frames[i].height);
+    }
+    return stitch_rig_create(wh.data(), n, pano->start, pano->steps.data(), (int)pano->steps.size(), opts, out);
+}
+
+int stitch_rig_info(const stitch_rig* rig, int* width, int* height, int* n_frames, int* n_steps, int* max_sets) {
+    if (!rig) return fail(STITCH_ERR_ARG, "rig_info: null handle");
+    if (width) *width = rig->out_w;
+    if (height) *height = rig->out_h;
+    if (n_frames) *n_frames = rig->n;
+    if (n_steps) *n_steps = (int)rig->steps.size();
+    if (max_sets) *max_sets = rig->max_sets;
+    return STITCH_OK;
+}
+
+const stitch_plan* stitch_rig_step_plan(const stitch_rig* rig, int k) {
+    return rig && k >= 0 && k < (int)rig->plan_of_step.size() ? rig->plans[rig->plan_of_step[k]] : nullptr;
+}
+
+int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status,
+                             stitch_seam* seams, void* stream) {
+    int rc = need_device();
+    if (rc) return rc;
+    if (!rig || !frames || !d_out || !set_status || n_sets < 1) return fail(STITCH_ERR_ARG, "rig_stitch: null argument or %d sets", n_sets);
+    stitch_rig* R = rig;
+    const int n = R->n, ns = (int)R->steps.size();
+    const size_t out_bytes = (size_t)3 * R->out_w * R->out_h;
+    for (int i = 0; i < n_sets; ++i) {
+        if (!d_out[i]) return fail(STITCH_ERR_ARG, "rig_stitch: set %d has no output buffer", i);
+        for (int f = 0; f < n; ++f) {
+            const stitch_frame_u8& fr = frames[(size_t)i * n + f];
+            if (fr.width != R->fw[f] || fr.height != R->fh[f])
+                return fail(STITCH_ERR_ARG, "rig_stitch: set %d frame %d is %d x %d, the rig was made for %d x %d", i, f, fr.width, fr.height, R->fw[f], R->fh[f]);
+        }
+        for (int f : R->needed) {
+            const stitch_frame_u8& fr = frames[(size_t)i * n + f];
+            if (!fr.data) return fail(STITCH_ERR_ARG, "rig_stitch: set %d frame %d has no data", i, f);
+            const size_t fb = (size_t)3 * fr.width * fr.height;
+            for (int j = 0; j < n_sets; ++j)
+                if (d_out[j] && ranges_overlap(d_out[j], out_bytes, fr.data, fb)) return fail(STITCH_ERR_ARG, "rig_stitch: the output of set %d overlaps frame %d of set %d", j, f, i);
+        }
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(d_out[j], out_bytes, d_out[i], out_bytes)) return fail(STITCH_ERR_ARG, "rig_stitch: the outputs of sets %d and %d overlap", j, i);
+    }
+    if ((rc = rig_workspaces(R))) return rc;
+    hipStream_t s = as_stream(stream);
+    for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
+
+    // ---- the pointer tables of the whole call, uploaded once: per sequence one slice per projected frame, then the outputs ----
+    const int n_need = (int)R->needed.size();
+    const std::vector<int> seqs = rig_sequences(n_sets, R->max_sets);
+    std::vector<RigImage> tab((size_t)(n_need + 1) * n_sets);
+    {
+        size_t at = 0;
+        int set0 = 0;
+        for (int m : seqs) {
+            for (int f : R->needed)
+                for (int i = 0; i < m; ++i) {
+                    // zero steps: the start frame is projected straight into the caller's buffer
+                    uint8_t* dst = ns == 0 ? d_out[set0 + i] : R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
+                    tab[at++] = RigImage{frames[(size_t)(set0 + i) * n + f].data, dst};
+                }
+            for (int i = 0; i < m; ++i) tab[at++] = RigImage{nullptr, d_out[set0 + i]};
+            set0 += m;
+        }
+    }
+    PanoArena A(s);
+    RigImage* d_tab = nullptr;
+    int32_t* d_eq = nullptr;
+    if ((rc = A.take(&d_tab, sizeof(RigImage) * tab.size()))) return rc;
+    if (R->finish && (rc = A.take(&d_eq, sizeof(int32_t) * RIG_EQ_WORDS * n_sets))) return rc;
+    PanoWait wait{s};         // `tab` is read by its upload, and what the arena frees is idle: every return path below waits for the stream
+    RigOutcome O(R, n_sets, set_status, seams);  // destroyed before the wait: reads what is pending
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(RigImage) * tab.size(), hipMemcpyHostToDevice, s));
+    if (R->finish) HIPCHK(hipMemsetAsync(d_eq, 0, sizeof(int32_t) * RIG_EQ_WORDS * n_sets, s));
+
+    size_t at = 0;
+    int set0 = 0;
+    std::vector<stitch_pair_desc> pd((size_t)R->max_sets);
+    for (int m : seqs) {
+        O.set0 = set0;
+        O.m = m;
+        for (int f : R->needed) {
+            if ((rc = rig_project_many(tab.data() + at, d_tab + at, m, R->fw[f], R->fh[f], R->fov_deg, s))) return rc;
+            at += m;
+        }
+        const uint8_t* cur = ns ? R->proj[R->start] : nullptr;
+        size_t cur_stride = (size_t)3 * R->fw[R->start] * R->fh[R->start];
+        int mw = R->fw[R->start], mh = R->fh[R->start];
+        for (int k = 0; k < ns; ++k) {
+            const stitch_panorama_step& st = R->steps[k];
+            const int pi = R->plan_of_step[k], f = st.dst;
+            O.read(pi);  // the same workspace twice: its seam records are read before they are overwritten
+            const bool last = k + 1 == ns;
+            for (int i = 0; i < m; ++i) {
+                stitch_pair_desc& d = pd[i];
+                std::memset(&d, 0, sizeof d);
+                d.frame = R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
+                d.fw = R->fw[f];
+                d.fh = R->fh[f];
+                std::memcpy(d.p, st.p_bwd, sizeof d.p);
+                d.offx = st.geom.min_x;
+                d.offy = st.geom.min_y;
+                d.mosaic = cur + (size_t)i * cur_stride;
+                d.mw = mw;
+                d.mh = mh;
+                d.ox = st.geom.ox;
+                d.oy = st.geom.oy;
+                d.out = last ? d_out[set0 + i] : R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes;
+            }
+            if ((rc = stitch_dev_pairs_u8(R->plans[pi], pd.data(), m, s))) return rc;
+            O.pending_step[pi] = k;
+            cur = R->mosaic[k & 1];
+            cur_stride = R->mosaic_bytes;
+            mw = st.geom.cw;
+            mh = st.geom.ch;
+        }
+        if (R->finish && (rc = rig_finish_many(tab.data() + at, d_tab + at, d_eq + (size_t)RIG_EQ_WORDS * set0, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
+        at += m;
+        O.read_all();  // the next sequence uses the same workspaces
+        if (O.hip_fault) break;
+        set0 += m;
+    }
+    if (O.hip_fault) {
+        for (int i = 0; i < n_sets; ++i) set_status[i] = O.hip_fault;
+        return fail(O.hip_fault, "rig_stitch: %s", O.hip_text.c_str());
+    }
+    HIPCHK(hipStreamSynchronize(s));  // the finish pass of the last sequence (read_all waited for the steps only)
+    for (int i = 0; i < n_sets; ++i)
+        if (set_status[i] != STITCH_OK)
+            return fail(set_status[i], "rig_stitch: set %d, step %d (frame %d): %s", i, O.fail_step[i], R->steps[O.fail_step[i]].dst,
+                        set_status[i] == STITCH_ERR_EMPTY_MIDROW ? "channel 0 of the warped canvas's middle row is empty"
+                                                                 : "the two canvases do not overlap on the middle row");
+    return STITCH_OK;
+}
+
+void stitch_rig_destroy(stitch_rig* rig) { delete rig; }
+
+int stitch_dev_project_many_u8(const uint8_t* const* d_src, uint8_t* const* d_dst, int count, int w, int h, float fov_deg, void* stream) {
+    int rc = need_device();
+    if (rc) return rc;
+    if ((rc = rig_many_args(d_src, d_dst, count, w, h, "project_many"))) return rc;
+    std::vector<RigImage> tab((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        if (!d_src[i] || !d_dst[i]) return fail(STITCH_ERR_ARG, "project_many: image %d has a null buffer", i);
+        tab[i] = RigImage{d_src[i], d_dst[i]};
+    }
+    hipStream_t s = as_stream(stream);
+    PanoArena A(s);
+    RigImage* d_tab = nullptr;
+    if ((rc = A.take(&d_tab, sizeof(RigImage) * count))) return rc;
+    PanoWait wait{s};  // `tab` is read by its upload
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(RigImage) * count, hipMemcpyHostToDevice, s));
+    return rig_project_many(tab.data(), d_tab, count, w, h, fov_deg, s);
+}
+
+int stitch_dev_finish_many_u8(uint8_t* const* d_result, int count, int w, int h, double num, double den, void* stream) {
+    int rc = need_device();
+    if (rc) return rc;
+    if ((rc = rig_many_args(d_result, d_result, count, w, h, "finish_many"))) return rc;
+    if ((long long)w * h > 0x7fffffffLL) return fail(STITCH_ERR_ARG, "finish_many: w*h overflows int (the reference's int product)");
+    std::vector<RigImage> tab((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        if (!d_result[i]) return fail(STITCH_ERR_ARG, "finish_many: mosaic %d has a null buffer", i);
+        tab[i] = RigImage{nullptr, d_result[i]};
+    }
+    hipStream_t s = as_stream(stream);
+    PanoArena A(s);
+    RigImage* d_tab = nullptr;
+    int32_t* d_eq = nullptr;
+    if ((rc = A.take(&d_tab, sizeof(RigImage) * count)) || (rc = A.take(&d_eq, sizeof(int32_t) * RIG_EQ_WORDS * count))) return rc;
+    PanoWait wait{s};  // `tab` is read by its upload
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(RigImage) * count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_eq, 0, sizeof(int32_t) * RIG_EQ_WORDS * count, s));
+    return rig_finish_many(tab.data(), d_tab, d_eq, count, w, h, num, den, s);
+}
+
+}  // extern "C"
