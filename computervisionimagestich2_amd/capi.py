@@ -141,6 +141,15 @@ RIG_SIGNATURES = _signatures(
     ("stitch_dev_finish_many_u8", i32, vp, i32, i32, i32, f64, f64, vp),
 )
 
+# The same for include/stitch_exposure.h, the colour transfer inside the chain; tests/test_exposure_host.py holds it to that header.
+EXPOSURE_SIGNATURES = _signatures(
+    ("stitch_exposure_opts_default", None, vp), ("stitch_dev_running_stats_f32", i32, vp, vp, vp, i32, i32, vp, vp, vp, vp),
+    ("stitch_dev_transfer_form_u8", i32, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp),
+    ("stitch_dev_panorama_exposure_from_features_u8", i32, vp, vp, i32, vp, vp, vp, vp), ("stitch_dev_panorama_exposure_u8", i32, vp, i32, vp, vp, vp, vp),
+    ("stitch_panorama_exposure_u8", i32, vp, i32, vp, vp, vp), ("stitch_panorama_exposure_stats", i32, vp, i32, vp),
+    ("stitch_panorama_exposure_frame_copy", i32, vp, i32, vp, sz, i32, vp),
+)
+
 _lib = None
 
 
@@ -159,7 +168,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -328,15 +337,45 @@ def transfer(src, tem):
     return out, st
 
 
-def dev_transfer(d_src, d_tem, out=None, stats=None):
-    """Device-resident colour transfer; out may be d_src itself."""
+def dev_transfer(d_src, d_tem, out=None, stats=None, stats_form=0, keep_black=False, diag=None):
+    """Device-resident colour transfer; out may be d_src itself.  stats_form 1 / 2 form the statistics by scan (the same bits,
+    include/stitch_exposure.h), keep_black leaves (0,0,0) source pixels black; diag: optional (6, 4) int32 tensor for the
+    scan's counters.  The defaults are stitch_dev_transfer_u8 itself."""
     import torch
     for t in (d_src, d_tem):
         assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape[0] == 3
     out = torch.empty_like(d_src) if out is None else out
-    _chk(lib().stitch_dev_transfer_u8(_dp(d_src), d_src.shape[2], d_src.shape[1], _dp(d_tem), d_tem.shape[2], d_tem.shape[1], _dp(out),
-                                      _dp(stats), _stream()))
+    if stats_form == 0 and not keep_black and diag is None:
+        _chk(lib().stitch_dev_transfer_u8(_dp(d_src), d_src.shape[2], d_src.shape[1], _dp(d_tem), d_tem.shape[2], d_tem.shape[1], _dp(out),
+                                          _dp(stats), _stream()))
+    else:
+        _chk(lib().stitch_dev_transfer_form_u8(_dp(d_src), d_src.shape[2], d_src.shape[1], _dp(d_tem), d_tem.shape[2], d_tem.shape[1], _dp(out),
+                                               _dp(stats), int(stats_form), int(bool(keep_black)), _dp(diag), _stream()))
     return out
+
+
+STATS_DIAG = ("plain_adds", "spans_o1", "spans_redone", "tiles_serial")  # STITCH_STATS_DIAG counters per plane
+
+
+def dev_running_stats(planes, form=2, counts=None, want_diag=False):
+    """stitch_dev_running_stats_f32: mean and sd of 1 .. 6 float32 device tensors (each flattened, each with its own length) as
+    transfer.cpp:128-164 accumulates them, float sums in index order; counts default to the lengths.  form 0: the serial walk,
+    1: one workgroup's scan, 2: spans + walk -- the same bits.  Returns (mean, sd) device tensors, with want_diag also an
+    (n, 4) int32 tensor of STATS_DIAG counters.  Enqueued on torch's current stream."""
+    import torch
+    planes = [p.reshape(-1) for p in planes]
+    for p in planes:
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError("expected contiguous float32 tensors on the HIP device")
+    n = len(planes)
+    ptrs = (C.c_void_p * max(n, 1))(*[p.data_ptr() for p in planes])
+    lens = (C.c_size_t * max(n, 1))(*[p.numel() for p in planes])
+    cnts = (C.c_float * max(n, 1))(*[float(p.numel()) if counts is None else float(counts[i]) for i, p in enumerate(planes)])
+    dev = planes[0].device if planes else None
+    mean, sd = torch.zeros(max(n, 1), dtype=torch.float32, device=dev), torch.zeros(max(n, 1), dtype=torch.float32, device=dev)
+    diag = torch.zeros((max(n, 1), len(STATS_DIAG)), dtype=torch.int32, device=dev) if want_diag else None
+    _chk(lib().stitch_dev_running_stats_f32(ptrs, lens, cnts, n, int(form), _dp(mean), _dp(sd), _dp(diag), _stream()))
+    return (mean, sd, diag) if want_diag else (mean, sd)
 
 
 class BmpInfo(C.Structure):
@@ -777,7 +816,31 @@ def _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_
     return o
 
 
-def _panorama_result(h, device, return_steps, keep_steps):
+class ExposureOpts(C.Structure):
+    """stitch_exposure_opts (include/stitch_exposure.h)."""
+    _fields_ = [("mode", C.c_int32), ("stats_form", C.c_int32), ("keep_black", C.c_int32)]
+
+
+def _exposure(exposure):
+    """None / 0 -> None (the chain as it is); a mode 1 / 2 -> the library's defaults with that mode; a dict(mode=, stats_form=,
+    keep_black=) or an ExposureOpts -> as given."""
+    if exposure is None or (isinstance(exposure, int) and exposure == 0):
+        return None
+    if isinstance(exposure, ExposureOpts):
+        return exposure
+    o = ExposureOpts()
+    lib().stitch_exposure_opts_default(C.byref(o))
+    if isinstance(exposure, dict):
+        for k, v in exposure.items():
+            if k not in ("mode", "stats_form", "keep_black"):
+                raise ValueError(f"exposure: unknown key {k!r}")
+            setattr(o, k, int(v))
+    else:
+        o.mode = int(exposure)
+    return o
+
+
+def _panorama_result(h, device, return_steps, keep_steps, exposure=None, frame_sizes=None):
     """The handle's mosaic (and steps) as torch tensors / dicts shaped like pipeline.panorama_from_features's; destroys the handle."""
     import torch
     L = lib()
@@ -798,6 +861,14 @@ def _panorama_result(h, device, return_steps, keep_steps):
             steps.append(dict(start=start.value, src=s.dst, mosaic_src=s.src, p=np.array(s.p_bwd[:]), p_fwd=np.array(s.p_fwd[:]), offx=g.min_x, offy=g.min_y,
                               ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch, out=out, seam=s.seam.as_tuple(),
                               info=np.array([list(s.info[0]), list(s.info[1])], np.int64)))
+            if exposure is not None and exposure.mode:
+                st12 = np.zeros(12, np.float32)
+                _chk(L.stitch_panorama_exposure_stats(h, k, _p(st12)))
+                steps[-1]["exposure_stats"] = st12
+                if keep_steps:
+                    fw, fh = frame_sizes[s.dst]
+                    steps[-1]["transferred"] = torch.empty((3, fh, fw), dtype=torch.uint8, device=device)
+                    _chk(L.stitch_panorama_exposure_frame_copy(h, k, _dp(steps[-1]["transferred"]), 3 * fw * fh, 1, _stream()))
         torch.cuda.current_stream().synchronize()  # the copies have left the handle's buffers
     finally:
         L.stitch_panorama_destroy(h)
@@ -813,20 +884,26 @@ def _frames_u8(frames):
 
 
 def dev_panorama(frames, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, keep_steps=False, sift_opts=None, ransac_opts=None,
-                 kp_cap=4096, feat_cap=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+                 kp_cap=4096, feat_cap=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0, exposure=None):
     """The whole of ImageProcess::ImageProcess plus matching() in ONE library call (stitch_dev_panorama_u8): frames is a list of
     (3, H, W) uint8 device tensors (unprojected).  Returns the mosaic as a tensor; with return_steps also a list of dicts with the
     keys of pipeline.panorama_from_features's steps ("src" is the warped frame; "out" the step's mosaic with keep_steps, else
-    None).  Runs on torch's current stream and waits for it."""
+    None).  Runs on torch's current stream and waits for it.  exposure (include/stitch_exposure.h): None is this chain; 1 / 2 or
+    dict(mode=, stats_form=, keep_black=) recolours every frame before its step (stitch_dev_panorama_exposure_u8); the steps then
+    also hold "exposure_stats" and, with keep_steps, "transferred"."""
     frames, arr = _frames_u8(frames)
     keep, h = [], C.c_void_p()
     o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, keep_steps, ratio, match_threshold, fov_deg, keep)
-    _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
-    return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+    if exposure is None:
+        _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
+        return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+    e = _exposure(exposure)
+    _chk(lib().stitch_dev_panorama_exposure_u8(arr, len(frames), C.byref(o), None if e is None else C.byref(e), _stream(), C.byref(h)))
+    return _panorama_result(h, frames[0].device, return_steps, keep_steps, e, [(f.shape[2], f.shape[1]) for f in frames])
 
 
 def dev_panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, keep_steps=False,
-                               ransac_opts=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+                               ransac_opts=None, ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0, exposure=None):
     """stitch_dev_panorama_from_features_u8: as dev_panorama, from the frames and per frame (descriptors (n, 128), x, y) float32
     device tensors in map order, which are left unchanged."""
     frames, arr = _frames_u8(frames)
@@ -835,19 +912,27 @@ def dev_panorama_from_features(frames, features, opts=None, finish=True, num=19.
     sets = (FeatureSet * max(len(frames), 1))(*[_feature_set(*f) for f in features])
     keep, h = [], C.c_void_p()
     o = _panorama_opts(opts, finish, num, den, None, ransac_opts, 4096, None, keep_steps, ratio, match_threshold, fov_deg, keep)
-    _chk(lib().stitch_dev_panorama_from_features_u8(arr, sets, len(frames), C.byref(o), _stream(), C.byref(h)))
-    return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+    if exposure is None:
+        _chk(lib().stitch_dev_panorama_from_features_u8(arr, sets, len(frames), C.byref(o), _stream(), C.byref(h)))
+        return _panorama_result(h, frames[0].device, return_steps, keep_steps)
+    e = _exposure(exposure)
+    _chk(lib().stitch_dev_panorama_exposure_from_features_u8(arr, sets, len(frames), C.byref(o), None if e is None else C.byref(e), _stream(), C.byref(h)))
+    return _panorama_result(h, frames[0].device, return_steps, keep_steps, e, [(f.shape[2], f.shape[1]) for f in frames])
 
 
 def panorama(frames, opts=None, finish=True, num=19.0, den=20.0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None,
-             ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
+             ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0, exposure=None):
     """stitch_panorama_u8: the whole panorama from (3, H, W) uint8 HOST arrays -> the mosaic as a numpy array."""
     frames = [np.ascontiguousarray(_img(f), np.uint8) for f in frames]
     arr = (FrameU8 * max(len(frames), 1))(*[FrameU8(f.ctypes.data, f.shape[2], f.shape[1]) for f in frames])
     keep, h = [], C.c_void_p()
     o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, False, ratio, match_threshold, fov_deg, keep)
     L = lib()
-    _chk(L.stitch_panorama_u8(arr, len(frames), C.byref(o), C.byref(h)))
+    if exposure is None:
+        _chk(L.stitch_panorama_u8(arr, len(frames), C.byref(o), C.byref(h)))
+    else:
+        e = _exposure(exposure)
+        _chk(L.stitch_panorama_exposure_u8(arr, len(frames), C.byref(o), None if e is None else C.byref(e), C.byref(h)))
     try:
         w, ht = C.c_int(), C.c_int()
         _chk(L.stitch_panorama_info(h, C.byref(w), C.byref(ht), None, None))

@@ -167,14 +167,10 @@ __global__ __launch_bounds__(256) void k_tr_to_lab(const uint8_t* __restrict__ r
 // not associative, so the order is kept: one wavefront per (image, channel) chain walks its plane serially; the 64
 // lanes only fetch (256 samples ahead, double-buffered in LDS) and square, every lane then adds the same samples in
 // the same order.  Six chains run side by side.  stats = [mean_src[3], sd_src[3], mean_tem[3], sd_tem[3]].
-__global__ __launch_bounds__(64) void k_tr_stats(const float* __restrict__ lab_s, size_t ns, float cnt_s, const float* __restrict__ lab_t,
-                                                 size_t nt, float cnt_t, float* __restrict__ stats) {
-    __shared__ __attribute__((aligned(16))) float buf[2][256];
-    const int chain = blockIdx.x, c = chain % 3, lane = threadIdx.x;
-    const bool is_t = chain >= 3;
-    const size_t n = is_t ? nt : ns;
-    const float* __restrict__ p = (is_t ? lab_t : lab_s) + (size_t)c * n;
-    const float cnt = is_t ? cnt_t : cnt_s;
+// One chain: the wavefront's walk over plane p of n samples (csrc/k_exposure.inc runs the same walk as its form 0).
+__device__ __forceinline__ void tr_stats_chain(const float* __restrict__ p, size_t n, float cnt, float* __restrict__ mean_out, float* __restrict__ sd_out,
+                                               float (*buf)[256]) {
+    const int lane = threadIdx.x;
     const size_t nblk = (n + 255) / 256;
     float mean = 0.f;
     for (int pass = 0; pass < 2; ++pass) {
@@ -226,10 +222,18 @@ __global__ __launch_bounds__(64) void k_tr_stats(const float* __restrict__ lab_s
         if (pass == 0)
             mean = acc / cnt;
         else if (lane == 0) {
-            stats[(is_t ? 6 : 0) + c] = mean;
-            stats[(is_t ? 9 : 3) + c] = sqrtf(acc / cnt);
+            *mean_out = mean;
+            *sd_out = sqrtf(acc / cnt);
         }
     }
+}
+__global__ __launch_bounds__(64) void k_tr_stats(const float* __restrict__ lab_s, size_t ns, float cnt_s, const float* __restrict__ lab_t,
+                                                 size_t nt, float cnt_t, float* __restrict__ stats) {
+    __shared__ __attribute__((aligned(16))) float buf[2][256];
+    const int chain = blockIdx.x, c = chain % 3;
+    const bool is_t = chain >= 3;
+    const size_t n = is_t ? nt : ns;
+    tr_stats_chain((is_t ? lab_t : lab_s) + (size_t)c * n, n, is_t ? cnt_t : cnt_s, stats + (is_t ? 6 : 0) + c, stats + (is_t ? 9 : 3) + c, buf);
 }
 __global__ __launch_bounds__(256) void k_tr_apply(const float* __restrict__ lab, size_t n, const float* __restrict__ stats, TrK k,
                                                   uint8_t* __restrict__ out) {

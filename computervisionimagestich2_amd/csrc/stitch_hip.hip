@@ -22,6 +22,7 @@
 #include "stitch_handoff.h"
 #include "stitch_panorama.h"
 #include "stitch_rig.h"
+#include "stitch_exposure.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2559,3 +2560,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_sift.inc"
 #include "stitch_panorama.inc"
 #include "stitch_rig.inc"
+#include "stitch_exposure.inc"

@@ -15,6 +15,11 @@ struct stitch_panorama {
     uint8_t* final_px = nullptr;
     std::vector<stitch_panorama_step> steps;
     std::vector<uint8_t*> step_px;  // with keep: one per step
+    // include/stitch_exposure.h: twelve statistics per step, and with keep each step's recoloured frame with its size
+    int exposure_mode = 0;
+    std::vector<float> exposure_stats;
+    std::vector<uint8_t*> exposure_px;
+    std::vector<int> exposure_wh;
     // device copies enqueued by stitch_panorama_copy and not yet waited for: one event each, behind the copy on its stream
     mutable std::mutex mu;
     mutable std::vector<hipEvent_t> copies;
@@ -25,6 +30,8 @@ struct stitch_panorama {
         }
         if (final_px) (void)hipFreeAsync(final_px, nullptr);
         for (uint8_t* p : step_px)
+            if (p) (void)hipFreeAsync(p, nullptr);
+        for (uint8_t* p : exposure_px)
             if (p) (void)hipFreeAsync(p, nullptr);
     }
 };
@@ -62,9 +69,16 @@ struct PanoArena {
 struct PanoCfg {
     stitch_panorama_opts o;
     int feat_cap;
+    stitch_exposure_opts ex;  // mode 0: the chain without a transfer
 };
 
-int pano_cfg(const stitch_panorama_opts* opts, PanoCfg* c) {
+int pano_cfg(const stitch_panorama_opts* opts, const stitch_exposure_opts* exposure, PanoCfg* c) {
+    c->ex = stitch_exposure_opts{0, 0, 0};
+    if (exposure) {
+        c->ex = *exposure;
+        if (c->ex.mode < 0 || c->ex.mode > 2) return fail(STITCH_ERR_ARG, "panorama: exposure mode %d (0 .. 2)", c->ex.mode);
+        if (c->ex.stats_form < 0 || c->ex.stats_form > 2) return fail(STITCH_ERR_ARG, "panorama: exposure stats_form %d (0 .. 2)", c->ex.stats_form);
+    }
     if (opts)
         c->o = *opts;
     else
@@ -185,6 +199,13 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
     int32_t* d_info10 = reinterpret_cast<int32_t*>(d_maps + 16 * sizeof(double));
     int32_t* d_sel_count = d_info10 + 2 * STITCH_RANSAC_INFO;
 
+    float* d_ex_stats = nullptr;  // twelve per step
+    P->exposure_mode = c.ex.mode;
+    if (c.ex.mode && n_steps) {
+        if ((rc = A.take(&d_ex_stats, sizeof(float) * 12 * n_steps))) return rc;
+        P->exposure_stats.assign((size_t)12 * n_steps, 0.f);
+    }
+
     for (int k = 0; k < n_steps; ++k) {
         const int src = order[2 * k], dst = order[2 * k + 1];
         if ((rc = pano_select_and_fit(list_of(src, dst), d_counts + (size_t)src * n + dst, list_of(dst, src), d_counts + (size_t)dst * n + src, fx[src],
@@ -213,6 +234,24 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
         const size_t samples = (size_t)3 * st.geom.cw * st.geom.ch;
         uint8_t* next = nullptr;
         if ((rc = A.take(&next, samples))) return rc;
+        if (c.ex.mode) {
+            // ImageProcess.cpp:180-182, switched on: the frame about to be warped takes the colour statistics of what is
+            // already stitched, in place on its stored projection (a later step that warps or reads it again sees the result)
+            if ((rc = projected(src))) return rc;
+            const uint8_t* tem = c.ex.mode == 1 ? proj[src] : result;
+            const int tw = c.ex.mode == 1 ? frames[src].width : rw, th = c.ex.mode == 1 ? frames[src].height : rh;
+            if ((rc = stitch_dev_transfer_form_u8(proj[dst], fw, fh, tem, tw, th, proj[dst], d_ex_stats + 12 * k, c.ex.stats_form, c.ex.keep_black, nullptr, s)))
+                return rc;
+            if (c.o.keep_steps) {
+                uint8_t* copy = nullptr;
+                if ((rc = A.take(&copy, (size_t)3 * fw * fh))) return rc;
+                HIPCHK(hipMemcpyAsync(copy, proj[dst], (size_t)3 * fw * fh, hipMemcpyDeviceToDevice, s));
+                A.give_up(copy);
+                P->exposure_px.push_back(copy);
+                P->exposure_wh.push_back(fw);
+                P->exposure_wh.push_back(fh);
+            }
+        }
         if ((rc = stitch_dev_step_u8(proj[dst], fw, fh, st.p_fwd, st.p_bwd, result, rw, rh, c.o.blend, next, samples, &st.geom, &st.seam, s))) return rc;
         // :226-227: the warped frame's key points go through the forward map, those of the frame warped before move by the offsets
         if ((rc = stitch_dev_map_points(fx[dst], fy[dst], nullptr, nullptr, feats[dst].n, st.p_fwd, st.geom.min_x, st.geom.min_y, s))) return rc;
@@ -229,6 +268,8 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
             P->step_px.push_back(next);
         }
     }
+    // the callers wait for the stream before the handle leaves them
+    if (d_ex_stats) HIPCHK(hipMemcpyAsync(P->exposure_stats.data(), d_ex_stats, sizeof(float) * 12 * n_steps, hipMemcpyDeviceToHost, s));
     // ---- the finish pass works on a copy where the last step's mosaic is kept ----
     uint8_t* fin = result;
     const size_t bytes = (size_t)3 * rw * rh;
@@ -392,8 +433,12 @@ int stitch_dev_pair_maps(const stitch_feature_set* src, const stitch_feature_set
                                d_info10, s);
 }
 
-int stitch_dev_panorama_from_features_u8(const stitch_frame_u8* frames, const stitch_feature_set* feats, int n, const stitch_panorama_opts* opts,
-                                         void* stream, stitch_panorama** out) {
+}  // extern "C"
+
+namespace {
+
+int pano_from_features(const stitch_frame_u8* frames, const stitch_feature_set* feats, int n, const stitch_panorama_opts* opts,
+                       const stitch_exposure_opts* exposure, void* stream, stitch_panorama** out) {
     int rc = need_device();
     if (rc) {
         if (out) *out = nullptr;
@@ -405,7 +450,7 @@ int stitch_dev_panorama_from_features_u8(const stitch_frame_u8* frames, const st
         if (feats[i].n < 0 || (feats[i].n > 0 && (!feats[i].d_desc || !feats[i].d_x || !feats[i].d_y)))
             return fail(STITCH_ERR_ARG, "panorama: feature set %d lacks an array", i);
     PanoCfg c;
-    if ((rc = pano_cfg(opts, &c))) return rc;
+    if ((rc = pano_cfg(opts, exposure, &c))) return rc;
     hipStream_t s = as_stream(stream);
     PanoArena A(s);
     std::unique_ptr<stitch_panorama> P(new stitch_panorama());
@@ -427,7 +472,8 @@ int stitch_dev_panorama_from_features_u8(const stitch_frame_u8* frames, const st
     return STITCH_OK;
 }
 
-int stitch_dev_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, void* stream, stitch_panorama** out) {
+int pano_from_frames(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, const stitch_exposure_opts* exposure, void* stream,
+                     stitch_panorama** out) {
     int rc = need_device();
     if (rc) {
         if (out) *out = nullptr;
@@ -435,7 +481,7 @@ int stitch_dev_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_pa
     }
     if ((rc = pano_check_frames(frames, n, out))) return rc;
     PanoCfg c;
-    if ((rc = pano_cfg(opts, &c))) return rc;
+    if ((rc = pano_cfg(opts, exposure, &c))) return rc;
     hipStream_t s = as_stream(stream);
     PanoArena A(s);
     std::unique_ptr<stitch_panorama> P(new stitch_panorama());
@@ -539,13 +585,16 @@ int stitch_dev_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_pa
     return STITCH_OK;
 }
 
-int stitch_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, stitch_panorama** out) {
+int pano_from_host_frames(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, const stitch_exposure_opts* exposure,
+                          stitch_panorama** out) {
     int rc = need_device();
     if (rc) {
         if (out) *out = nullptr;
         return rc;
     }
     if ((rc = pano_check_frames(frames, n, out))) return rc;
+    PanoCfg c;  // refused options are refused before a frame goes up
+    if ((rc = pano_cfg(opts, exposure, &c))) return rc;
     std::vector<DevBuf> up((size_t)n);
     std::vector<stitch_frame_u8> dev((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -554,7 +603,24 @@ int stitch_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_panora
         H2D(up[i].p, frames[i].data, bytes);
         dev[i] = stitch_frame_u8{up[i].as<uint8_t>(), frames[i].width, frames[i].height};
     }
-    return stitch_dev_panorama_u8(dev.data(), n, opts, nullptr, out);
+    return pano_from_frames(dev.data(), n, opts, exposure, nullptr, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int stitch_dev_panorama_from_features_u8(const stitch_frame_u8* frames, const stitch_feature_set* feats, int n, const stitch_panorama_opts* opts,
+                                         void* stream, stitch_panorama** out) {
+    return pano_from_features(frames, feats, n, opts, nullptr, stream, out);
+}
+
+int stitch_dev_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, void* stream, stitch_panorama** out) {
+    return pano_from_frames(frames, n, opts, nullptr, stream, out);
+}
+
+int stitch_panorama_u8(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, stitch_panorama** out) {
+    return pano_from_host_frames(frames, n, opts, nullptr, out);
 }
 
 int stitch_panorama_info(const stitch_panorama* pano, int* width, int* height, int* start, int* n_steps) {

@@ -116,7 +116,17 @@ def sequence_sizes(count, per_seq, lanes):
     return [count // m + (1 if i < count % m else 0) for i in range(m)]
 
 
-def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None):
+def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_form=2, stats=None):
+    """The reference's dead `transfer tran(X, T, X)` of ImageProcess.cpp:180-182, switched on: recolours the projected frame about
+    to be warped, in place.  exposure 1: T is the projected frame it is stitched to; 2: T is the running mosaic; 0: nothing."""
+    if exposure not in (0, 1, 2):
+        raise ValueError(f"exposure {exposure!r} (0, 1 or 2)")
+    if exposure:
+        capi.dev_transfer(proj_dst, proj_src if exposure == 1 else result, out=proj_dst, stats=stats, stats_form=stats_form, keep_black=keep_black)
+    return proj_dst
+
+
+def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -125,6 +135,8 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     plans: optional dict kept by the caller across calls; the workspace of every canvas size met is created once and
     reused (a camera rig stitches every frame with the same geometry: without it half of a small panorama's time is
     the creation of the three workspaces).  Close them with close_plans(plans).
+    exposure 1 / 2: every step first matches the frame's colours to the frame it is stitched to (the step's "mosaic_src") / to the
+    running mosaic (exposure_match; include/stitch_exposure.h), keep_black leaving the projection's black corners black.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     proj = {}
 
@@ -144,6 +156,8 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
                 plans[key] = plan
         elif plan in used:  # the same workspace twice in one chain: its seam record must be read before it is overwritten
             plan.status()
+        if exposure:
+            exposure_match(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black)
         result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])
         used.append(plan)
     if finish:
@@ -816,12 +830,15 @@ class KeyPointTrack:
         self.pre = dst
 
 
-def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False):
+def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, exposure=0, keep_black=True):
     """ImageProcess::matching (ImageProcess.cpp:101-268) from the frames and their SIFT features alone: frames is a list of
     (3, H, W) uint8 device tensors (unprojected), features a list of (descriptors (n, 128), keypoints (n, 2) x/y) in the
     std::map's order (feature_order).  Neighbour matrix, stitch order, per step both maps (pair_maps), the stitch step and the
-    feature updates of :226-227.  Returns the final mosaic (and, with return_steps, what every step used and produced)."""
+    feature updates of :226-227.  exposure / keep_black: as stitch_chain; a step's dict then holds the transfer's twelve
+    statistics ("exposure_stats") and a copy of the recoloured frame ("transferred").
+    Returns the final mosaic (and, with return_steps, what every step used and produced)."""
     import numpy as np
+    import torch
     desc = [np.ascontiguousarray(d, dtype=np.float32) for d, _ in features]
     start, order = stitch_order(match_counts(desc))
     track = KeyPointTrack([k for _, k in features], start)
@@ -839,10 +856,16 @@ def panorama_from_features(frames, features, opts=None, finish=True, num=19.0, d
         p_fwd, p_bwd, info = pair_maps(desc[src], kps[src], desc[dst], kps[dst])
         if info[0][0] != capi.RANSAC_OK or info[1][0] != capi.RANSAC_OK:
             raise capi.StitchError(-1, f"frames {src} -> {dst}: no map (RANSAC status {int(info[0][0])} / {int(info[1][0])}, {int(info[0][1])} pairs)")
+        extra = {}
+        if exposure:
+            stats = torch.zeros(12, dtype=torch.float32, device=result.device)
+            exposure_match(projected(dst), projected(src), result, exposure, keep_black, stats=stats)
+            if return_steps:
+                extra = dict(exposure_stats=stats, transferred=projected(dst).clone())
         result, g, _seam = capi.dev_step(projected(dst), p_fwd, p_bwd, result, opts)
         track.stitched(src, dst, p_fwd, g)  # :226-227
         steps.append(dict(start=start, src=dst, mosaic_src=src, p=p_bwd, p_fwd=p_fwd, offx=g.min_x, offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch,
-                          out=result, info=info))
+                          out=result, info=info, **extra))
     if finish:
         result = result.clone() if return_steps and steps else result
         capi.dev_finish(result, num, den)
@@ -878,10 +901,10 @@ def sift_features(frames, opts=None, kp_cap=4096, feat_cap=None):
 
 
 def panorama_from_frames(frames, opts=None, finish=True, num=19.0, den=20.0, return_steps=False, sift_opts=None, kp_cap=4096,
-                         feat_cap=None):
+                         feat_cap=None, exposure=0, keep_black=True):
     """The whole of ImageProcess::ImageProcess plus matching() from decoded frames alone: sift_features (kp_cap / feat_cap are
     its per-frame capacities; a frame that needs more raises StitchError with the counts found), then panorama_from_features."""
-    return panorama_from_features(frames, sift_features(frames, sift_opts, kp_cap, feat_cap), opts, finish, num, den, return_steps)
+    return panorama_from_features(frames, sift_features(frames, sift_opts, kp_cap, feat_cap), opts, finish, num, den, return_steps, exposure, keep_black)
 
 
 # ---- the same chain as ONE call of the C ABI (include/stitch_panorama.h): what a C++ caller gets ----------------------------------
