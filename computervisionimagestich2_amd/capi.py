@@ -150,6 +150,13 @@ EXPOSURE_SIGNATURES = _signatures(
     ("stitch_panorama_exposure_frame_copy", i32, vp, i32, vp, sz, i32, vp),
 )
 
+# The same for include/stitch_rig_exposure.h, the colour transfer in a rig's replay; tests/test_rig_exposure_host.py holds it to that header.
+RIG_EXPOSURE_SIGNATURES = _signatures(
+    ("stitch_rig_create_exposure", i32, vp, i32, i32, vp, i32, vp, vp, vp), ("stitch_rig_from_panorama_exposure", i32, vp, vp, i32, vp, vp, vp),
+    ("stitch_dev_rig_stitch_exposure_u8", i32, vp, vp, i32, vp, vp, vp, vp, vp),
+    ("stitch_dev_transfer_many_u8", i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp),
+)
+
 _lib = None
 
 
@@ -168,7 +175,8 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) \
+                + list(RIG_EXPOSURE_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -1273,12 +1281,16 @@ class Panorama(_Handle):
 
 
 def dev_panorama_handle(frames, opts=None, finish=True, num=19.0, den=20.0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None,
-                        ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0):
-    """dev_panorama, but the result stays behind its handle -> Panorama (close() it when done)."""
+                        ratio=RATIO_THRESHOLD, match_threshold=20, fov_deg=15.0, exposure=None):
+    """dev_panorama, but the result stays behind its handle -> Panorama (close() it when done).  exposure: as dev_panorama's."""
     frames, arr = _frames_u8(frames)
     keep, h = [], C.c_void_p()
     o = _panorama_opts(opts, finish, num, den, sift_opts, ransac_opts, kp_cap, feat_cap, False, ratio, match_threshold, fov_deg, keep)
-    _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
+    e = _exposure(exposure)
+    if e is None:
+        _chk(lib().stitch_dev_panorama_u8(arr, len(frames), C.byref(o), _stream(), C.byref(h)))
+    else:
+        _chk(lib().stitch_dev_panorama_exposure_u8(arr, len(frames), C.byref(o), C.byref(e), _stream(), C.byref(h)))
     return Panorama(h, frames[0].device)
 
 
@@ -1326,9 +1338,12 @@ class Rig(_Handle):
         self.width, self.height, self.n_frames, self.n_steps, self.max_sets = (x.value for x in v)
 
     @classmethod
-    def from_steps(cls, frame_sizes, start, steps, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0):
+    def from_steps(cls, frame_sizes, start, steps, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True,
+                   stats_form=2):
         """stitch_rig_create (host only): frame_sizes = (width, height) of every decoded frame; steps = step dicts as rig_steps
-        takes them (`src` is the WARPED frame) or a ready PanoramaStep array; start may be None to take steps[0]["start"]."""
+        takes them (`src` is the WARPED frame) or a ready PanoramaStep array; start may be None to take steps[0]["start"].
+        exposure 1 / 2 (stitch_rig_create_exposure): every step of the replay first matches the frame's colours to the frame it is
+        stitched to (the step's "mosaic_src", which must then be a frame already placed) / to the running mosaic, per set."""
         if isinstance(steps, C.Array):
             arr, n_steps = steps, len(steps)
         else:
@@ -1338,24 +1353,35 @@ class Rig(_Handle):
         wh = np.ascontiguousarray(np.array(frame_sizes, np.int32).reshape(-1, 2))
         keep, h = [], C.c_void_p()
         o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
-        _chk(lib().stitch_rig_create(_p(wh), wh.shape[0], int(start), arr, n_steps, C.byref(o), C.byref(h)))
+        if exposure:
+            e = _exposure(dict(mode=exposure, keep_black=bool(keep_black), stats_form=stats_form))
+            _chk(lib().stitch_rig_create_exposure(_p(wh), wh.shape[0], int(start), arr, n_steps, C.byref(o), C.byref(e), C.byref(h)))
+        else:
+            _chk(lib().stitch_rig_create(_p(wh), wh.shape[0], int(start), arr, n_steps, C.byref(o), C.byref(h)))
         return cls(h)
 
     @classmethod
-    def from_panorama(cls, pano, frames, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0):
-        """stitch_rig_from_panorama: pano is a Panorama (dev_panorama_handle), frames the tensors it was made from (sizes only)."""
+    def from_panorama(cls, pano, frames, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True, stats_form=2):
+        """stitch_rig_from_panorama: pano is a Panorama (dev_panorama_handle), frames the tensors it was made from (sizes only).
+        exposure 1 / 2: stitch_rig_from_panorama_exposure, as from_steps; the handle's own mode is not read."""
         arr = (FrameU8 * max(len(frames), 1))(*[FrameU8(None, f.shape[2], f.shape[1]) for f in frames])
         keep, h = [], C.c_void_p()
         o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
-        _chk(lib().stitch_rig_from_panorama(pano._h, arr, len(frames), C.byref(o), C.byref(h)))
+        if exposure:
+            e = _exposure(dict(mode=exposure, keep_black=bool(keep_black), stats_form=stats_form))
+            _chk(lib().stitch_rig_from_panorama_exposure(pano._h, arr, len(frames), C.byref(o), C.byref(e), C.byref(h)))
+        else:
+            _chk(lib().stitch_rig_from_panorama(pano._h, arr, len(frames), C.byref(o), C.byref(h)))
         return cls(h)
 
     def step_plan(self, k):
         """stitch_rig_step_plan: the address of the batched workspace step k runs on (None before the first stitch call)."""
         return lib().stitch_rig_step_plan(self._h, int(k))
 
-    def stitch(self, sets, out=None):
-        """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for.  sets: a list of frame sets, each a list of
+    def stitch(self, sets, out=None, return_stats=False):
+        """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for (with return_stats
+        stitch_dev_rig_stitch_exposure_u8, and a fourth result: an (n_sets, n_steps, 12) float32 array of every transfer's
+        statistics; the rig must have been made with an exposure mode).  sets: a list of frame sets, each a list of
         n_frames (3, H, W) uint8 device tensors.  Returns (outputs, statuses, seams): one (3, height, width) tensor per set, each
         set's status (OK, ERR_EMPTY_MIDROW or ERR_ZERO_OVERLAP: a failed set does not raise, the others are valid), and per set the
         Seam tuples of its steps.  self.last_rc keeps the call's return value (the status of the first set that is not OK).
@@ -1375,13 +1401,17 @@ class Rig(_Handle):
         ptrs = (C.c_void_p * max(n_sets, 1))(*[o.data_ptr() for o in out])
         status = (C.c_int32 * max(n_sets, 1))()
         seams = (Seam * max(n_sets * self.n_steps, 1))()
-        rc = lib().stitch_dev_rig_stitch_u8(self._h, arr, n_sets, ptrs, status, seams, _stream())
+        stats = np.zeros((n_sets, self.n_steps, 12), np.float32) if return_stats else None
+        if return_stats:
+            rc = lib().stitch_dev_rig_stitch_exposure_u8(self._h, arr, n_sets, ptrs, status, seams, _p(stats), _stream())
+        else:
+            rc = lib().stitch_dev_rig_stitch_u8(self._h, arr, n_sets, ptrs, status, seams, _stream())
         statuses = list(status[:n_sets])
         seam_rows = [[seams[i * self.n_steps + k].as_tuple() for k in range(self.n_steps)] for i in range(n_sets)]
         self.last_rc = rc
         if rc < 0 and rc not in (ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP):
             raise StitchError(rc, lib().stitch_last_error().decode())
-        return out, statuses, seam_rows
+        return (out, statuses, seam_rows, stats) if return_stats else (out, statuses, seam_rows)
 
 
 def _ptr_table(tensors):
@@ -1409,3 +1439,22 @@ def dev_finish_many(results, num=19.0, den=20.0):
         raise ValueError("expected uint8 mosaics of one size")
     _chk(lib().stitch_dev_finish_many_u8(_ptr_table(results), len(results), w, h, num, den, _stream()))
     return results
+
+
+def dev_transfer_many(srcs, tems, out=None, stats_form=2, keep_black=False, want_stats=False, want_diag=False):
+    """stitch_dev_transfer_many_u8: the colour transfer of many (source, template) pairs in the launches of one -- all sources of
+    one size, all templates of one size, (3, H, W) uint8 device tensors; out[i] may be srcs[i].  Returns the outputs, with
+    want_stats also a (count, 12) float32 device tensor, with want_diag also a (count, 6, 4) int32 tensor of STATS_DIAG counters."""
+    import torch
+    srcs, tems = [_timg(t) for t in srcs], [_timg(t) for t in tems]
+    out = [torch.empty_like(t) for t in srcs] if out is None else list(out)
+    (_, sh, sw), (_, th, tw) = srcs[0].shape, tems[0].shape
+    if any(tuple(t.shape) != (3, sh, sw) or t.dtype != torch.uint8 for t in srcs + out) or any(tuple(t.shape) != (3, th, tw) or t.dtype != torch.uint8 for t in tems) \
+            or not len(srcs) == len(tems) == len(out):
+        raise ValueError("expected uint8 sources of one size, templates of one size, and one template and one output per source")
+    n, dev = len(srcs), srcs[0].device
+    stats = torch.zeros((n, 12), dtype=torch.float32, device=dev) if want_stats else None
+    diag = torch.zeros((n, 6, len(STATS_DIAG)), dtype=torch.int32, device=dev) if want_diag else None
+    _chk(lib().stitch_dev_transfer_many_u8(_ptr_table(srcs), _ptr_table(tems), _ptr_table(out), n, sw, sh, tw, th, int(stats_form), int(bool(keep_black)),
+                                           _dp(stats), _dp(diag), _stream()))
+    return (out,) + ((stats,) if want_stats else ()) + ((diag,) if want_diag else ()) if (want_stats or want_diag) else out

@@ -339,70 +339,60 @@ __device__ __forceinline__ double ex_block_sum(ExShared& sh, double v) {
     return s;
 }
 
-// Form 0: the serial walk of k_tr_stats, one wavefront per plane.
-__global__ __launch_bounds__(64) void k_ex_stats_serial(ExArgs a) {
-    __shared__ __attribute__((aligned(16))) float buf[2][256];
-    const int pl = blockIdx.x;
-    tr_stats_chain(a.p[pl], (size_t)a.n[pl], a.cnt[pl], a.mean[pl], a.sd[pl], buf);
-}
+// The kernels' bodies, per plane or per image: the kernels below run them on the planes an ExArgs holds by value, the many-plane
+// forms of k_rig_exposure.inc on the records of a device table.  `sums`, `table` and `diag_out` are the plane's own rows.
 
-// Form 2, first launch of a pass: every span's sum in double.  sums[plane * max_spans + span].
-__global__ __launch_bounds__(EX_T) void k_ex_span_sums(ExArgs a, int pass, int max_spans, double* __restrict__ sums) {
-    __shared__ ExShared sh;
-    const int pl = blockIdx.y, span = blockIdx.x;
-    const size_t n = (size_t)a.n[pl], b = (size_t)span * EX_SPAN;
+// Form 2, first launch of a pass: one span's sum in double.
+__device__ __forceinline__ void ex_span_sum_plane(ExShared& sh, const float* __restrict__ p, size_t n, const float* mean_at, int pass, int span,
+                                                  double* __restrict__ sums) {
+    const size_t b = (size_t)span * EX_SPAN;
     if (b >= n) return;
     const size_t e = b + EX_SPAN < n ? b + EX_SPAN : n;
-    const float mean = pass ? *a.mean[pl] : 0.f;
-    const float* __restrict__ p = a.p[pl];
+    const float mean = pass ? *mean_at : 0.f;
     double v = 0.0;
     for (size_t i = b + threadIdx.x; i < e; i += EX_T) v += (double)ex_addend(p[i], pass, mean);
     v = ex_block_sum(sh, v);
-    if (threadIdx.x == 0) sums[(size_t)pl * max_spans + span] = v;
+    if (threadIdx.x == 0) sums[span] = v;
 }
 
 // Form 2, second launch: the guess of the state at the span's entry (the double prefix of the spans before it, rounded to
 // float), then the span reduced under that guess.
-__global__ __launch_bounds__(EX_T) void k_ex_span_maps(ExArgs a, int pass, int max_spans, const double* __restrict__ sums, ExSpanEntry* __restrict__ table) {
-    __shared__ ExShared sh;
-    const int pl = blockIdx.y, span = blockIdx.x;
-    const size_t n = (size_t)a.n[pl], b = (size_t)span * EX_SPAN;
+__device__ __forceinline__ void ex_span_map_plane(ExShared& sh, const float* __restrict__ p, size_t n, const float* mean_at, int pass, int span,
+                                                  const double* __restrict__ sums, ExSpanEntry* __restrict__ table) {
+    const size_t b = (size_t)span * EX_SPAN;
     if (b >= n) return;
     const size_t e = b + EX_SPAN < n ? b + EX_SPAN : n;
     double v = 0.0;
-    for (int k = threadIdx.x; k < span; k += EX_T) v += sums[(size_t)pl * max_spans + k];
+    for (int k = threadIdx.x; k < span; k += EX_T) v += sums[k];
     const uint32_t key = ex_bits((float)ex_block_sum(sh, v)) >> 23;
     ExSpanEntry en;
     en.pad = 0;
     if (ex_key_normal(key)) {
         en.key = key;
-        en.m = ex_span_map(sh, a.p[pl], b, e, pass, pass ? *a.mean[pl] : 0.f, key);
+        en.m = ex_span_map(sh, p, b, e, pass, pass ? *mean_at : 0.f, key);
     } else {
         en.key = EX_NO_GUESS;
         en.m = ex_identity();
     }
-    if (threadIdx.x == 0) table[(size_t)pl * max_spans + span] = en;
+    if (threadIdx.x == 0) table[span] = en;
 }
 
-// One workgroup per plane goes over the plane in order with the true state.  table == nullptr: the single-workgroup form, both
-// passes in this launch.  With a table: one pass, the spans in order.
-__global__ __launch_bounds__(EX_T) void k_ex_walk(ExArgs a, int pass, int max_spans, const ExSpanEntry* __restrict__ table, uint32_t* __restrict__ diag_out) {
-    __shared__ ExShared sh;
-    const int pl = blockIdx.x;
-    const size_t n = (size_t)a.n[pl];
-    const float* __restrict__ p = a.p[pl];
+// One workgroup goes over the plane in order with the true state.  table == nullptr: the single-workgroup form, both passes in
+// this launch.  With a table: one pass, the spans in order.
+__device__ __forceinline__ void ex_walk_plane(ExShared& sh, const float* __restrict__ p, size_t n, float cnt, float* mean_at, float* sd_at, int pass,
+                                              const ExSpanEntry* __restrict__ table, uint32_t* __restrict__ diag_out) {
     uint32_t diag[EX_DIAG_N] = {0, 0, 0, 0};
     float mean = 0.f, acc = 0.f;
     if (!table) {
         acc = ex_redo(sh, p, 0, n, 0.f, 0, 0.f, diag);
-        mean = acc / a.cnt[pl];
+        mean = acc / cnt;
         acc = ex_redo(sh, p, 0, n, 0.f, 1, mean, diag);
     } else {
-        mean = pass ? *a.mean[pl] : 0.f;
+        mean = pass ? *mean_at : 0.f;
         const size_t spans = (n + EX_SPAN - 1) / EX_SPAN;
         for (size_t s0 = 0; s0 < spans; s0 += EX_WALK_CHUNK) {
             const int m = (int)(spans - s0 < (size_t)EX_WALK_CHUNK ? spans - s0 : (size_t)EX_WALK_CHUNK);
-            if ((int)threadIdx.x < m) sh.spans[threadIdx.x] = table[(size_t)pl * max_spans + s0 + threadIdx.x];
+            if ((int)threadIdx.x < m) sh.spans[threadIdx.x] = table[s0 + threadIdx.x];
             __syncthreads();
             for (int k = 0; k < m; ++k) {
                 const size_t b = (s0 + k) * EX_SPAN;
@@ -413,19 +403,20 @@ __global__ __launch_bounds__(EX_T) void k_ex_walk(ExArgs a, int pass, int max_sp
     }
     if (threadIdx.x == 0) {
         if (table && pass == 0)
-            *a.mean[pl] = acc / a.cnt[pl];
+            *mean_at = acc / cnt;
         else {
-            *a.mean[pl] = mean;
-            *a.sd[pl] = sqrtf(acc / a.cnt[pl]);
+            *mean_at = mean;
+            *sd_at = sqrtf(acc / cnt);
         }
         if (diag_out)
-            for (int k = 0; k < EX_DIAG_N; ++k) diag_out[pl * EX_DIAG_N + k] += diag[k];
+            for (int k = 0; k < EX_DIAG_N; ++k) diag_out[k] += diag[k];
     }
 }
 
-// k_tr_apply with keep_black: where src is given, a source pixel that is (0,0,0) stays (0,0,0).  out may be src.
-__global__ __launch_bounds__(256) void k_ex_apply(const float* __restrict__ lab, size_t n, const float* __restrict__ stats, TrK k, const uint8_t* src,
-                                                  uint8_t* out) {
+// k_tr_apply with keep_black: where src is given, a source pixel that is (0,0,0) stays (0,0,0).  out may be src.  One image's
+// pixels, strided over the x dimension of the grid.
+__device__ __forceinline__ void ex_apply_image(const float* __restrict__ lab, size_t n, const float* __restrict__ stats, const TrK& k, const uint8_t* src,
+                                               uint8_t* out) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     float st[12];
 #pragma unroll
@@ -440,5 +431,37 @@ __global__ __launch_bounds__(256) void k_ex_apply(const float* __restrict__ lab,
         out[i + n] = black ? (uint8_t)0 : px_store<uint8_t>(G);
         out[i + 2 * n] = black ? (uint8_t)0 : px_store<uint8_t>(B);
     }
+}
+
+// Form 0: the serial walk of k_tr_stats, one wavefront per plane.
+__global__ __launch_bounds__(64) void k_ex_stats_serial(ExArgs a) {
+    __shared__ __attribute__((aligned(16))) float buf[2][256];
+    const int pl = blockIdx.x;
+    tr_stats_chain(a.p[pl], (size_t)a.n[pl], a.cnt[pl], a.mean[pl], a.sd[pl], buf);
+}
+
+// sums[plane * max_spans + span], table[plane * max_spans + span], diag_out[plane * EX_DIAG_N + counter]
+__global__ __launch_bounds__(EX_T) void k_ex_span_sums(ExArgs a, int pass, int max_spans, double* __restrict__ sums) {
+    __shared__ ExShared sh;
+    const int pl = blockIdx.y;
+    ex_span_sum_plane(sh, a.p[pl], (size_t)a.n[pl], a.mean[pl], pass, (int)blockIdx.x, sums + (size_t)pl * max_spans);
+}
+
+__global__ __launch_bounds__(EX_T) void k_ex_span_maps(ExArgs a, int pass, int max_spans, const double* __restrict__ sums, ExSpanEntry* __restrict__ table) {
+    __shared__ ExShared sh;
+    const int pl = blockIdx.y;
+    ex_span_map_plane(sh, a.p[pl], (size_t)a.n[pl], a.mean[pl], pass, (int)blockIdx.x, sums + (size_t)pl * max_spans, table + (size_t)pl * max_spans);
+}
+
+__global__ __launch_bounds__(EX_T) void k_ex_walk(ExArgs a, int pass, int max_spans, const ExSpanEntry* __restrict__ table, uint32_t* __restrict__ diag_out) {
+    __shared__ ExShared sh;
+    const int pl = blockIdx.x;
+    ex_walk_plane(sh, a.p[pl], (size_t)a.n[pl], a.cnt[pl], a.mean[pl], a.sd[pl], pass, table ? table + (size_t)pl * max_spans : nullptr,
+                  diag_out ? diag_out + pl * EX_DIAG_N : nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_ex_apply(const float* __restrict__ lab, size_t n, const float* __restrict__ stats, TrK k, const uint8_t* src,
+                                                  uint8_t* out) {
+    ex_apply_image(lab, n, stats, k, src, out);
 }
 #endif

@@ -153,7 +153,8 @@ __device__ __forceinline__ void tr_lab_to_rgb(const TrK& k, float L, float a, fl
     G = g > 0.0f ? (g < 255.0f ? g : 255.0f) : 0.0f;
     B = bb > 0.0f ? (bb < 255.0f ? bb : 255.0f) : 0.0f;
 }
-__global__ __launch_bounds__(256) void k_tr_to_lab(const uint8_t* __restrict__ rgb, size_t n, TrK k, float* __restrict__ lab) {
+// One image's pixels, strided over the x dimension of the grid (k_rig_exposure.inc runs the same per image of a many-image launch).
+__device__ __forceinline__ void tr_to_lab_image(const uint8_t* __restrict__ rgb, size_t n, const TrK& k, float* __restrict__ lab) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         float L, a, b;
@@ -162,6 +163,9 @@ __global__ __launch_bounds__(256) void k_tr_to_lab(const uint8_t* __restrict__ r
         lab[i + n] = a;
         lab[i + 2 * n] = b;
     }
+}
+__global__ __launch_bounds__(256) void k_tr_to_lab(const uint8_t* __restrict__ rgb, size_t n, TrK k, float* __restrict__ lab) {
+    tr_to_lab_image(rgb, n, k, lab);
 }
 // transfer.cpp:128-164: mean and standard deviation with FLOAT accumulators in raster order.  A float running sum is
 // not associative, so the order is kept: one wavefront per (image, channel) chain walks its plane serially; the 64

@@ -33,6 +33,19 @@ int ex_run_stats(const ExArgs& a, int n_planes, int form, uint32_t* d_diag, Pano
     return STITCH_OK;
 }
 
+// The transfer's constants, as stitch_dev_transfer_u8 forms them.
+TrK ex_constants() {
+    TrK k{};
+    k.a1 = (float)(1.0 / std::sqrt(3.0));
+    k.b1 = (float)(1.0 / std::sqrt(6.0));
+    k.c1 = (float)(1.0 / std::sqrt(2.0));
+    k.a2 = (float)(std::sqrt(3.0) / 3.0);
+    k.b2 = (float)(std::sqrt(6.0) / 6.0);
+    k.c2 = (float)(std::sqrt(2.0) / 2.0);
+    k.ln10 = 2.302585092994046;  // log(10)
+    return k;
+}
+
 }  // namespace
 
 extern "C" {
@@ -75,14 +88,7 @@ int stitch_dev_transfer_form_u8(const uint8_t* d_src, int sw, int sh, const uint
         return fail(STITCH_ERR_ARG, "transfer: w*h overflows int (the reference's int product)");
     if (stats_form < 0 || stats_form > 2) return fail(STITCH_ERR_ARG, "transfer: stats_form %d (0 .. 2)", stats_form);
     const size_t ns = (size_t)sw * sh, nt = (size_t)tw * th;
-    TrK k{};  // as stitch_dev_transfer_u8 forms them
-    k.a1 = (float)(1.0 / std::sqrt(3.0));
-    k.b1 = (float)(1.0 / std::sqrt(6.0));
-    k.c1 = (float)(1.0 / std::sqrt(2.0));
-    k.a2 = (float)(std::sqrt(3.0) / 3.0);
-    k.b2 = (float)(std::sqrt(6.0) / 6.0);
-    k.c2 = (float)(std::sqrt(2.0) / 2.0);
-    k.ln10 = 2.302585092994046;  // log(10)
+    const TrK k = ex_constants();
     hipStream_t s = as_stream(stream);
     PanoArena A(s);
     float* scratch = nullptr;

@@ -23,6 +23,7 @@
 #include "stitch_panorama.h"
 #include "stitch_rig.h"
 #include "stitch_exposure.h"
+#include "stitch_rig_exposure.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2561,3 +2562,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_panorama.inc"
 #include "stitch_rig.inc"
 #include "stitch_exposure.inc"
+#include "stitch_rig_exposure.inc"

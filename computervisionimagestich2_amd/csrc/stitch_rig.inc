@@ -23,8 +23,17 @@ struct stitch_rig {
     std::vector<uint8_t*> proj;        // per frame: max_sets projected frames (NULL for a frame no step uses)
     uint8_t* mosaic[2] = {nullptr, nullptr};  // max_sets mosaics each, `mosaic_bytes` apart
     size_t mosaic_bytes = 0;
+    // ---- the colour transfer before every step (include/stitch_rig_exposure.h; stitch_rig_exposure.inc) ----
+    stitch_exposure_opts ex{0, 0, 0};  // mode 0: the replay as it is
+    size_t ex_src_px = 0, ex_tem_px = 0;  // the largest frame a step warps, the largest template
+    float* ex_lab = nullptr;              // max_sets * 3 * ex_src_px floats of frames, then max_sets * 3 * ex_tem_px of templates
+    float* ex_stats = nullptr;            // 16 floats per set and step, set-major
+    double* ex_sums = nullptr;            // form 2: per span of 6 * max_sets planes of the longest plane
+    void* ex_table = nullptr;             // form 2: the span table (ExSpanEntry)
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
+        for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
+            if (p) (void)hipFree(p);
         for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
         for (uint8_t* p : proj)
             if (p) (void)hipFree(p);
@@ -36,6 +45,13 @@ struct stitch_rig {
 namespace {
 
 constexpr int kRigMaxSets = 16, kRigMaxImages = 65535;
+
+// The transfer of a rig with a mode (stitch_rig_exposure.inc): its scratch, its plane and image tables -- one block for the whole
+// call, valid for every sequence, since it names the rig's own buffers only -- and step k's transfer over the m sets in flight.
+int rig_ex_workspaces(stitch_rig* R);
+size_t rig_ex_table_bytes(const stitch_rig* R);
+void rig_ex_fill_tables(const stitch_rig* R, unsigned char* host);
+int rig_ex_transfer(stitch_rig* R, const unsigned char* d_tables, int k, int m, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -139,6 +155,10 @@ int rig_workspaces(stitch_rig* R) {
     for (int k = 0; k + 1 < ns; ++k) R->mosaic_bytes = std::max(R->mosaic_bytes, align256((size_t)3 * R->steps[k].geom.cw * R->steps[k].geom.ch));
     for (int b = 0; b < std::min(2, ns - 1); ++b)
         if (!R->mosaic[b]) HIPCHK(hipMalloc((void**)&R->mosaic[b], (size_t)R->max_sets * R->mosaic_bytes));
+    if (R->ex.mode && ns) {
+        const int rc = rig_ex_workspaces(R);
+        if (rc) return rc;
+    }
     R->device = dev;
     return STITCH_OK;
 }
@@ -197,28 +217,20 @@ int rig_many_args(const void* a, const void* b, int count, int w, int h, const c
     return STITCH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void stitch_rig_opts_default(stitch_rig_opts* o) {
-    if (!o) return;
-    std::memset(o, 0, sizeof *o);
-    o->fov_deg = 15.0f;
-    o->finish = 1;
-    o->num = 19.0;
-    o->den = 20.0;
-    o->max_sets = kRigMaxSets;
-}
-
-int stitch_rig_create(const int32_t* frame_wh, int n, int start, const stitch_panorama_step* steps, int n_steps, const stitch_rig_opts* opts,
-                      stitch_rig** out) {
+// stitch_rig_create, and stitch_rig_create_exposure with its options (NULL: mode 0)
+int rig_create(const int32_t* frame_wh, int n, int start, const stitch_panorama_step* steps, int n_steps, const stitch_rig_opts* opts,
+               const stitch_exposure_opts* exposure, stitch_rig** out) {
     if (out) *out = nullptr;
     if (!out || !frame_wh || n_steps < 0 || (n_steps > 0 && !steps)) return fail(STITCH_ERR_ARG, "rig: null argument or %d steps", n_steps);
     if (n < 1 || n > kPanoMaxFrames) return fail(STITCH_ERR_ARG, "rig: %d frames (1 .. %d)", n, kPanoMaxFrames);
     std::unique_ptr<stitch_rig> R(new stitch_rig());
     int rc = rig_cfg(opts, R.get());
     if (rc) return rc;
+    if (exposure) {
+        if (exposure->mode < 0 || exposure->mode > 2) return fail(STITCH_ERR_ARG, "rig: exposure mode %d (0 .. 2)", exposure->mode);
+        if (exposure->stats_form < 0 || exposure->stats_form > 2) return fail(STITCH_ERR_ARG, "rig: exposure stats_form %d (0 .. 2)", exposure->stats_form);
+        if (exposure->mode) R->ex = *exposure;
+    }
     R->n = n;
     for (int i = 0; i < n; ++i) {
         const int w = frame_wh[2 * i], h = frame_wh[2 * i + 1];
@@ -243,6 +255,18 @@ int stitch_rig_create(const int32_t* frame_wh, int n, int start, const stitch_pa
                         "rig: step %d records the canvas %d x %d, offsets (%.9g, %.9g) / (%d, %d); its forward map on a %d x %d mosaic gives %d x %d, "
                         "(%.9g, %.9g) / (%d, %d)",
                         k, r.cw, r.ch, (double)r.min_x, (double)r.min_y, r.ox, r.oy, mw, mh, g.cw, g.ch, (double)g.min_x, (double)g.min_y, g.ox, g.oy);
+        if (R->ex.mode) {
+            // the template of the step's transfer: the projected frame src, which must have been placed (`needed` holds the
+            // frames placed so far), or the running mosaic before the step
+            if (R->ex.mode == 1 && std::find(R->needed.begin(), R->needed.end(), st.src) == R->needed.end())
+                return fail(STITCH_ERR_ARG, "rig: step %d takes frame %d as its template, which is neither the start frame nor warped by an earlier step", k,
+                            st.src);
+            const long long f_px = (long long)R->fw[st.dst] * R->fh[st.dst];
+            const long long t_px = R->ex.mode == 1 ? (long long)R->fw[st.src] * R->fh[st.src] : (long long)mw * mh;
+            if (f_px > 0x7fffffffLL || t_px > 0x7fffffffLL) return fail(STITCH_ERR_ARG, "rig: step %d: w*h of the frame or of the template overflows int", k);
+            R->ex_src_px = std::max(R->ex_src_px, (size_t)f_px);
+            R->ex_tem_px = std::max(R->ex_tem_px, (size_t)t_px);
+        }
         if (std::find(R->needed.begin(), R->needed.end(), st.dst) == R->needed.end()) R->needed.push_back(st.dst);
         R->steps.push_back(st);
         mw = g.cw;
@@ -254,7 +278,8 @@ int stitch_rig_create(const int32_t* frame_wh, int n, int start, const stitch_pa
     return STITCH_OK;
 }
 
-int stitch_rig_from_panorama(const stitch_panorama* pano, const stitch_frame_u8* frames, int n, const stitch_rig_opts* opts, stitch_rig** out) {
+int rig_from_panorama(const stitch_panorama* pano, const stitch_frame_u8* frames, int n, const stitch_rig_opts* opts, const stitch_exposure_opts* exposure,
+                      stitch_rig** out) {
     if (out) *out = nullptr;
     if (!pano || !frames || !out) return fail(STITCH_ERR_ARG, "rig_from_panorama: null argument");
     if (n < 1 || n > kPanoMaxFrames) return fail(STITCH_ERR_ARG, "rig: %d frames (1 .. %d)", n, kPanoMaxFrames);
@@ -263,7 +288,30 @@ int stitch_rig_from_panorama(const stitch_panorama* pano, const stitch_frame_u8*
         wh.push_back(frames[i].width);
         wh.push_back(frames[i].height);
     }
-    return stitch_rig_create(wh.data(), n, pano->start, pano->steps.data(), (int)pano->steps.size(), opts, out);
+    return rig_create(wh.data(), n, pano->start, pano->steps.data(), (int)pano->steps.size(), opts, exposure, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+void stitch_rig_opts_default(stitch_rig_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->fov_deg = 15.0f;
+    o->finish = 1;
+    o->num = 19.0;
+    o->den = 20.0;
+    o->max_sets = kRigMaxSets;
+}
+
+int stitch_rig_create(const int32_t* frame_wh, int n, int start, const stitch_panorama_step* steps, int n_steps, const stitch_rig_opts* opts,
+                      stitch_rig** out) {
+    return rig_create(frame_wh, n, start, steps, n_steps, opts, nullptr, out);
+}
+
+int stitch_rig_from_panorama(const stitch_panorama* pano, const stitch_frame_u8* frames, int n, const stitch_rig_opts* opts, stitch_rig** out) {
+    return rig_from_panorama(pano, frames, n, opts, nullptr, out);
 }
 
 int stitch_rig_info(const stitch_rig* rig, int* width, int* height, int* n_frames, int* n_steps, int* max_sets) {
@@ -280,12 +328,18 @@ const stitch_plan* stitch_rig_step_plan(const stitch_rig* rig, int k) {
     return rig && k >= 0 && k < (int)rig->plan_of_step.size() ? rig->plans[rig->plan_of_step[k]] : nullptr;
 }
 
-int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status,
-                             stitch_seam* seams, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// stitch_dev_rig_stitch_u8, and stitch_dev_rig_stitch_exposure_u8 with its statistics (a host array, or NULL)
+int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status, stitch_seam* seams, float* stats,
+               void* stream) {
     int rc = need_device();
     if (rc) return rc;
     if (!rig || !frames || !d_out || !set_status || n_sets < 1) return fail(STITCH_ERR_ARG, "rig_stitch: null argument or %d sets", n_sets);
     stitch_rig* R = rig;
+    if (stats && !R->ex.mode) return fail(STITCH_ERR_ARG, "rig_stitch: statistics asked of a rig made without a transfer (mode 0)");
     const int n = R->n, ns = (int)R->steps.size();
     const size_t out_bytes = (size_t)3 * R->out_w * R->out_h;
     for (int i = 0; i < n_sets; ++i) {
@@ -327,14 +381,28 @@ int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int
             set0 += m;
         }
     }
+    // a rig with a mode: the plane and image tables of its transfers go up behind the pointer table, in the same copy
+    const size_t tab_bytes = sizeof(RigImage) * tab.size(), ex_at = (tab_bytes + 15) & ~size_t(15), ex_bytes = ns ? rig_ex_table_bytes(R) : 0;
+    std::vector<unsigned char> up;
+    if (ex_bytes) {
+        up.resize(ex_at + ex_bytes);
+        std::memcpy(up.data(), tab.data(), tab_bytes);
+        rig_ex_fill_tables(R, up.data() + ex_at);
+    }
+    const size_t up_bytes = ex_bytes ? up.size() : tab_bytes;
+    const void* up_from = ex_bytes ? (const void*)up.data() : (const void*)tab.data();
+    std::vector<float> h_stats(stats ? (size_t)16 * ns * n_sets : 0);  // 16 floats per set and step, as on the device
     PanoArena A(s);
-    RigImage* d_tab = nullptr;
+    unsigned char* d_up = nullptr;
     int32_t* d_eq = nullptr;
-    if ((rc = A.take(&d_tab, sizeof(RigImage) * tab.size()))) return rc;
+    if ((rc = A.take(&d_up, up_bytes))) return rc;
+    RigImage* d_tab = reinterpret_cast<RigImage*>(d_up);
     if (R->finish && (rc = A.take(&d_eq, sizeof(int32_t) * RIG_EQ_WORDS * n_sets))) return rc;
-    PanoWait wait{s};         // `tab` is read by its upload, and what the arena frees is idle: every return path below waits for the stream
+    // the tables are read by their upload, h_stats is written by the statistics' copies, and what the arena frees is idle: every
+    // return path below waits for the stream
+    PanoWait wait{s};
     RigOutcome O(R, n_sets, set_status, seams);  // destroyed before the wait: reads what is pending
-    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(RigImage) * tab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_up, up_from, up_bytes, hipMemcpyHostToDevice, s));
     if (R->finish) HIPCHK(hipMemsetAsync(d_eq, 0, sizeof(int32_t) * RIG_EQ_WORDS * n_sets, s));
 
     size_t at = 0;
@@ -371,6 +439,8 @@ int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int
                 d.oy = st.geom.oy;
                 d.out = last ? d_out[set0 + i] : R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes;
             }
+            // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
+            if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
             if ((rc = stitch_dev_pairs_u8(R->plans[pi], pd.data(), m, s))) return rc;
             O.pending_step[pi] = k;
             cur = R->mosaic[k & 1];
@@ -380,6 +450,9 @@ int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int
         }
         if (R->finish && (rc = rig_finish_many(tab.data() + at, d_tab + at, d_eq + (size_t)RIG_EQ_WORDS * set0, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
         at += m;
+        // the sequence's statistics leave the device in one copy, behind its last transfer; the next sequence overwrites them
+        if (!h_stats.empty())
+            HIPCHK(hipMemcpyAsync(h_stats.data() + (size_t)16 * ns * set0, R->ex_stats, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
         O.read_all();  // the next sequence uses the same workspaces
         if (O.hip_fault) break;
         set0 += m;
@@ -389,12 +462,22 @@ int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int
         return fail(O.hip_fault, "rig_stitch: %s", O.hip_text.c_str());
     }
     HIPCHK(hipStreamSynchronize(s));  // the finish pass of the last sequence (read_all waited for the steps only)
+    for (size_t j = 0; j < h_stats.size() / 16; ++j) std::memcpy(stats + 12 * j, h_stats.data() + 16 * j, sizeof(float) * 12);
     for (int i = 0; i < n_sets; ++i)
         if (set_status[i] != STITCH_OK)
             return fail(set_status[i], "rig_stitch: set %d, step %d (frame %d): %s", i, O.fail_step[i], R->steps[O.fail_step[i]].dst,
                         set_status[i] == STITCH_ERR_EMPTY_MIDROW ? "channel 0 of the warped canvas's middle row is empty"
                                                                  : "the two canvases do not overlap on the middle row");
     return STITCH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status,
+                             stitch_seam* seams, void* stream) {
+    return rig_stitch(rig, frames, n_sets, d_out, set_status, seams, nullptr, stream);
 }
 
 void stitch_rig_destroy(stitch_rig* rig) { delete rig; }
