@@ -157,6 +157,15 @@ RIG_EXPOSURE_SIGNATURES = _signatures(
     ("stitch_dev_transfer_many_u8", i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp),
 )
 
+# The same for include/stitch_calibrate.h, a rig calibrated from several captures; tests/test_calibrate_host.py holds it to that header.
+CALIBRATE_SIGNATURES = _signatures(
+    ("stitch_calibrate_opts_default stitch_calibration_destroy", None, vp), ("stitch_dev_calibrate_u8", i32, vp, i32, i32, vp, vp, vp),
+    ("stitch_dev_calibrate_from_features_u8", i32, vp, vp, i32, i32, vp, vp, vp), ("stitch_calibrate_u8", i32, vp, i32, i32, vp, vp),
+    ("stitch_calibration_info", i32, vp, vp, vp, vp, vp, vp, vp), ("stitch_calibration_step_at", i32, vp, i32, vp),
+    ("stitch_calibration_counts", i32, vp, vp, vp), ("stitch_calibration_step_support", i32, vp, i32, vp, vp),
+    ("stitch_rig_from_calibration", i32, vp, vp, vp, vp),
+)
+
 _lib = None
 
 
@@ -176,7 +185,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) \
-                + list(RIG_EXPOSURE_SIGNATURES.items()):
+                + list(RIG_EXPOSURE_SIGNATURES.items()) + list(CALIBRATE_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -1374,6 +1383,16 @@ class Rig(_Handle):
             _chk(lib().stitch_rig_from_panorama(pano._h, arr, len(frames), C.byref(o), C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def from_calibration(cls, cal, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True, stats_form=2):
+        """stitch_rig_from_calibration: cal is a Calibration (dev_calibrate); its frame sizes, start and steps make the rig.
+        exposure 1 / 2: as from_steps."""
+        keep, h = [], C.c_void_p()
+        o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
+        e = _exposure(dict(mode=exposure, keep_black=bool(keep_black), stats_form=stats_form)) if exposure else None
+        _chk(lib().stitch_rig_from_calibration(cal._h, C.byref(o), None if e is None else C.byref(e), C.byref(h)))
+        return cls(h)
+
     def step_plan(self, k):
         """stitch_rig_step_plan: the address of the batched workspace step k runs on (None before the first stitch call)."""
         return lib().stitch_rig_step_plan(self._h, int(k))
@@ -1412,6 +1431,92 @@ class Rig(_Handle):
         if rc < 0 and rc not in (ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP):
             raise StitchError(rc, lib().stitch_last_error().decode())
         return (out, statuses, seam_rows, stats) if return_stats else (out, statuses, seam_rows)
+
+
+# ---- a rig calibrated from several captures: include/stitch_calibrate.h -----------------------------------------------------
+class CalibrateOpts(C.Structure):
+    """stitch_calibrate_opts."""
+    _fields_ = [("pano", C.c_void_p), ("pooled_threshold", C.c_int32)]
+
+
+class Calibration(_Handle):
+    """stitch_calibration: one stitch order and one set of steps from several captures of the same cameras (host data).
+    start, width, height; steps: dicts with the keys of dev_panorama's steps (`src` is the WARPED camera, "mosaic_src" the one it is
+    stitched to, "out" None, "seam" zeros); counts ((n_sets, n, n) int32) and pooled ((n, n)); support ((n_steps, n_sets, 2) int32:
+    per step and capture the pairs it put into the chosen pooled list and its inliers of the forward map)."""
+    _destroy = "stitch_calibration_destroy"
+
+    def __init__(self, h):
+        self._h = h
+        L = lib()
+        v = [C.c_int() for _ in range(6)]
+        _chk(L.stitch_calibration_info(h, *[C.byref(x) for x in v]))
+        self.n_sets, self.n, self.start, self.n_steps, self.width, self.height = (x.value for x in v)
+        self.counts, self.pooled = np.zeros((self.n_sets, self.n, self.n), np.int32), np.zeros((self.n, self.n), np.int32)
+        _chk(L.stitch_calibration_counts(h, _p(self.counts), _p(self.pooled)))
+        self.support = np.zeros((self.n_steps, self.n_sets, 2), np.int32)
+        self.steps = []
+        for k in range(self.n_steps):
+            s, pairs, inl = PanoramaStep(), np.zeros(self.n_sets, np.int32), np.zeros(self.n_sets, np.int32)
+            _chk(L.stitch_calibration_step_at(h, k, C.byref(s)))
+            _chk(L.stitch_calibration_step_support(h, k, _p(pairs), _p(inl)))
+            self.support[k, :, 0], self.support[k, :, 1] = pairs, inl
+            g = s.geom
+            self.steps.append(dict(start=self.start, src=s.dst, mosaic_src=s.src, p=np.array(s.p_bwd[:]), p_fwd=np.array(s.p_fwd[:]), offx=g.min_x,
+                                   offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch, out=None, seam=s.seam.as_tuple(),
+                                   info=np.array([list(s.info[0]), list(s.info[1])], np.int64)))
+
+
+def _calibrate_opts(pooled_threshold, sift_opts, ransac_opts, kp_cap, feat_cap, ratio, match_threshold, fov_deg, keep):
+    keep.append(_panorama_opts(None, True, 19.0, 20.0, sift_opts, ransac_opts, kp_cap, feat_cap, False, ratio, match_threshold, fov_deg, keep))
+    return CalibrateOpts(C.addressof(keep[-1]), int(pooled_threshold))
+
+
+def _capture_list(sets):
+    sets = [list(fs) for fs in sets]
+    if not sets or any(len(fs) != len(sets[0]) for fs in sets):
+        raise ValueError("every capture has the same number of cameras")
+    return sets
+
+
+def dev_calibrate(sets, pooled_threshold=0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None, ratio=RATIO_THRESHOLD, match_threshold=20,
+                  fov_deg=15.0):
+    """stitch_dev_calibrate_u8: sets is a list of captures, each a list of the n cameras' (3, H, W) uint8 device tensors
+    (unprojected; camera i has one size in every capture).  Returns a Calibration.  Runs on torch's current stream and waits for it.
+    pooled_threshold 0: n_sets * match_threshold."""
+    sets = _capture_list(sets)
+    flat, arr = _frames_u8([f for fs in sets for f in fs])
+    keep, h = [], C.c_void_p()
+    o = _calibrate_opts(pooled_threshold, sift_opts, ransac_opts, kp_cap, feat_cap, ratio, match_threshold, fov_deg, keep)
+    _chk(lib().stitch_dev_calibrate_u8(arr, len(sets), len(sets[0]), C.byref(o), _stream(), C.byref(h)))
+    return Calibration(h)
+
+
+def dev_calibrate_from_features(frame_sizes, features, pooled_threshold=0, ransac_opts=None, ratio=RATIO_THRESHOLD, match_threshold=20):
+    """stitch_dev_calibrate_from_features_u8: frame_sizes = (width, height) per camera; features = per capture a list with, per
+    camera, (descriptors (n, 128), x, y) float32 device tensors in map order, which are left unchanged."""
+    features = _capture_list(features)
+    wh = np.ascontiguousarray(np.array(frame_sizes, np.int32).reshape(-1, 2))
+    if wh.shape[0] != len(features[0]):
+        raise ValueError("one frame size per camera")
+    flat = [f for fs in features for f in fs]
+    fs = (FeatureSet * len(flat))(*[_feature_set(*f) for f in flat])
+    keep, h = [], C.c_void_p()
+    o = _calibrate_opts(pooled_threshold, None, ransac_opts, 4096, None, ratio, match_threshold, 15.0, keep)
+    _chk(lib().stitch_dev_calibrate_from_features_u8(_p(wh), fs, len(features), len(features[0]), C.byref(o), _stream(), C.byref(h)))
+    return Calibration(h)
+
+
+def calibrate(sets, pooled_threshold=0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None, ratio=RATIO_THRESHOLD, match_threshold=20,
+              fov_deg=15.0):
+    """stitch_calibrate_u8: as dev_calibrate, from (3, H, W) uint8 HOST arrays."""
+    sets = [[np.ascontiguousarray(_img(f), np.uint8) for f in fs] for fs in _capture_list(sets)]
+    flat = [f for fs in sets for f in fs]
+    arr = (FrameU8 * len(flat))(*[FrameU8(f.ctypes.data, f.shape[2], f.shape[1]) for f in flat])
+    keep, h = [], C.c_void_p()
+    o = _calibrate_opts(pooled_threshold, sift_opts, ransac_opts, kp_cap, feat_cap, ratio, match_threshold, fov_deg, keep)
+    _chk(lib().stitch_calibrate_u8(arr, len(sets), len(sets[0]), C.byref(o), C.byref(h)))
+    return Calibration(h)
 
 
 def _ptr_table(tensors):

@@ -24,6 +24,7 @@
 #include "stitch_rig.h"
 #include "stitch_exposure.h"
 #include "stitch_rig_exposure.h"
+#include "stitch_calibrate.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2563,3 +2564,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_rig.inc"
 #include "stitch_exposure.inc"
 #include "stitch_rig_exposure.inc"
+#include "stitch_calibrate.inc"

@@ -907,5 +907,86 @@ def panorama_from_frames(frames, opts=None, finish=True, num=19.0, den=20.0, ret
     return panorama_from_features(frames, sift_features(frames, sift_opts, kp_cap, feat_cap), opts, finish, num, den, return_steps, exposure, keep_black)
 
 
+# ---- a rig calibrated from several captures (include/stitch_calibrate.h): the chain spelled out on the stage calls ---------------
+CALIBRATE_MAX_PAIRS = 65536  # STITCH_CALIBRATE_MAX_PAIRS: the pairs of a list stitch_dev_ransac_many tests
+
+
+def calibrate_from_features(frame_sizes, features, pooled_threshold=0, ransac_opts=None, ratio=capi.RATIO_THRESHOLD, match_threshold=MATCH_THRESHOLD):
+    """matching() without the pixels, over several captures of the same cameras: frame_sizes = (width, height) per camera;
+    features = per capture a list with, per camera, (descriptors (n, 128), keypoints (n, 2) x/y) in the std::map's order.
+      * camera i's key points of all captures lie in one device array, capture k's rows from base[k][i] on;
+      * getImgPair for every capture and ordered camera pair in one dev_match_many; pooled = the sum of the captures' counts;
+      * the order is stitch_order(pooled, T), T = pooled_threshold or n_sets * match_threshold;
+      * step (src, dst): the captures' accepted lists one behind the other, capture k's rows moved by base[k][src] and
+        base[k][dst]; the longer-list rule once, on the pooled totals (the C chain decides it on the device; the counts are on the
+        host here since the order needed them); both estimations on the pooled list, forward = the mirrored list first; the step's
+        canvas; dst's points of all captures through the forward map, those of the camera warped before moved by the offsets.
+    Returns a dict: start, steps (the keys of panorama_from_features's steps, "out" None), counts (n_sets, n, n), pooled (n, n),
+    support (n_steps, n_sets, 2: per capture the pairs it put into the chosen list and its inliers of the forward map), width,
+    height."""
+    import numpy as np
+    import torch
+    n_sets, n = len(features), len(features[0])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    desc = [_device_sets([d for d, _ in fs]) for fs in features]
+    rows = np.array([[d.shape[0] for d in ds] for ds in desc], np.int64)
+    base = np.concatenate([np.zeros((1, n), np.int64), np.cumsum(rows, 0)[:-1]])  # base[k][i]
+    xy = [torch.as_tensor(np.concatenate([np.asarray(fs[i][1], np.float32).reshape(-1, 2) for fs in features])).to(dev) for i in range(n)]
+    X, Y = [t[:, 0].contiguous() for t in xy], [t[:, 1].contiguous() for t in xy]
+    kij = [(k, i, j) for k in range(n_sets) for i in range(n) for j in range(n) if i != j]
+    outs = capi.dev_match_many([(desc[k][i], desc[k][j]) for k, i, j in kij], ratio, want_dist=False)
+    lists = dict(zip(kij, outs))
+    counts = np.zeros((n_sets, n, n), np.int32)
+    if kij:
+        for (k, i, j), c in zip(kij, torch.cat([o["count"] for o in outs]).cpu().numpy()):
+            counts[k, i, j] = int(c)
+    pooled = counts.sum(0, dtype=np.int32)
+    start, order = stitch_order(pooled, pooled_threshold or n_sets * match_threshold)
+    rw, rh = frame_sizes[start]
+    steps, support, pre = [], [], start
+    for src, dst in order:
+        use_sd = int(pooled[src, dst]) > int(pooled[dst, src])
+        parts = []
+        for k in range(n_sets):
+            shift = torch.tensor([int(base[k, src]), int(base[k, dst])], dtype=torch.int32, device=dev)
+            if use_sd:  # (src row, dst row) as getImgPair(src, dst) lists them
+                parts.append(lists[k, src, dst]["pairs"][:counts[k, src, dst]] + shift)
+            else:       # the mirror of getImgPair(dst, src)
+                parts.append(lists[k, dst, src]["pairs"][:counts[k, dst, src]].flip(1) + shift)
+        off = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])])
+        if off[-1] > CALIBRATE_MAX_PAIRS:
+            raise capi.StitchError(-1, f"cameras {src} -> {dst}: the pooled list has {int(off[-1])} pairs (at most {CALIBRATE_MAX_PAIRS})")
+        lst = dict(src_x=X[src], src_y=Y[src], dst_x=X[dst], dst_y=Y[dst], pairs=torch.cat(parts).contiguous())
+        p, info, inl = capi.dev_ransac_many([dict(lst, mirror=True), dict(lst, mirror=False)], ransac_opts)
+        got = torch.cat([p, info.to(torch.float64)], 1).cpu().numpy()
+        p_fwd, p_bwd, info = got[0, :8].copy(), got[1, :8].copy(), got[:, 8:].astype(np.int64)
+        if info[0][0] != capi.RANSAC_OK or info[1][0] != capi.RANSAC_OK:
+            raise capi.StitchError(-1, f"cameras {src} -> {dst}: no map (RANSAC status {int(info[0][0])} / {int(info[1][0])}, {int(info[0][1])} pooled pairs)")
+        win = inl[0][:int(info[0][3])].cpu().numpy()  # positions in the pooled list, increasing
+        support.append([[int(off[k + 1] - off[k]), int(((win >= off[k]) & (win < off[k + 1])).sum())] for k in range(n_sets)])
+        g = capi.step_geometry(frame_sizes[dst][0], frame_sizes[dst][1], p_fwd, rw, rh)
+        capi.dev_map_points(X[dst], Y[dst], p_fwd, g.min_x, g.min_y, want_int=False)  # :226-227, every capture at once
+        capi.dev_shift_points(X[pre], Y[pre], g.ox, g.oy, want_int=False)
+        pre, rw, rh = dst, g.cw, g.ch
+        steps.append(dict(start=start, src=dst, mosaic_src=src, p=p_bwd, p_fwd=p_fwd, offx=g.min_x, offy=g.min_y, ox=g.ox, oy=g.oy, cw=g.cw, ch=g.ch,
+                          out=None, info=info))
+    return dict(start=start, steps=steps, counts=counts, pooled=pooled, support=np.array(support, np.int32).reshape(len(steps), n_sets, 2), width=rw,
+                height=rh)
+
+
+def calibrate_from_sets(sets, pooled_threshold=0, sift_opts=None, ransac_opts=None, kp_cap=4096, feat_cap=None, ratio=capi.RATIO_THRESHOLD,
+                        match_threshold=MATCH_THRESHOLD):
+    """capi.dev_calibrate (stitch_dev_calibrate_u8) spelled out: sets is a list of captures, each a list of the n cameras'
+    (3, H, W) uint8 device tensors (unprojected).  sift_features over the frames of ALL captures -- one dev_sift_many call, one
+    read-back -- then calibrate_from_features."""
+    n = len(sets[0])
+    if any(len(fs) != n for fs in sets) or any(f.shape != g.shape for fs in sets for f, g in zip(fs, sets[0])):
+        raise ValueError("every capture has the same cameras, each with one frame size")
+    feats = sift_features([f for fs in sets for f in fs], sift_opts, kp_cap, feat_cap)
+    return calibrate_from_features([(f.shape[2], f.shape[1]) for f in sets[0]], [feats[k * n:(k + 1) * n] for k in range(len(sets))], pooled_threshold,
+                                   ransac_opts, ratio, match_threshold)
+
+
 # ---- the same chain as ONE call of the C ABI (include/stitch_panorama.h): what a C++ caller gets ----------------------------------
 panorama_c = capi.dev_panorama
+calibrate_c = capi.dev_calibrate
