@@ -2560,6 +2560,7 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_match.inc"
 #include "stitch_ransac.inc"
 #include "stitch_sift.inc"
+#include "stitch_chain.inc"
 #include "stitch_panorama.inc"
 #include "stitch_rig.inc"
 #include "stitch_exposure.inc"

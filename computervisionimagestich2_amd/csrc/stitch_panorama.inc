@@ -1,5 +1,6 @@
 // stitch_panorama.inc -- the whole panorama as one call (include/stitch_panorama.h; kernels in k_panorama.inc).
-// Included at the end of stitch_hip.hip (one translation unit).
+// Included in stitch_hip.hip (one translation unit) behind stitch_chain.inc, which holds the call's scratch, the SIFT front end,
+// the all-pairs matching and a step's two estimations.
 //
 // The chain restates pipeline.py's panorama_from_frames / panorama_from_features step for step on top of the C entry points of
 // the stages.  Per call the host waits three times for data: (1) the SIFT heads and the descriptor rows written, for the
@@ -8,8 +9,6 @@
 // (only the index array of the map order goes up, k_feat_gather builds the ordered sets), and a step takes its two lists from
 // the all-pairs matching of (2) instead of matching the pair again -- descriptors never change after SIFT, so they are the lists
 // pair_maps would recompute.
-#include <memory>
-
 struct stitch_panorama {
     int w = 0, h = 0, start = 0, keep = 0;
     uint8_t* final_px = nullptr;
@@ -40,32 +39,6 @@ namespace {
 
 constexpr int kPanoMaxFrames = 64;
 
-// Stream-ordered blocks of one call: whatever is still listed when the call ends -- on every error path too -- is freed on the
-// call's stream.  give_up() hands a block over to the result handle.
-struct PanoArena {
-    hipStream_t s;
-    std::vector<void*> blocks;
-    explicit PanoArena(hipStream_t s_) : s(s_) {}
-    ~PanoArena() {
-        for (void* p : blocks) (void)hipFreeAsync(p, s);
-    }
-    template <typename T>
-    int take(T** out, size_t bytes) {
-        void* p = nullptr;
-        keep_pool_memory();
-        HIPCHK(hipMallocAsync(&p, std::max<size_t>(bytes, 4), s));
-        blocks.push_back(p);
-        *out = static_cast<T*>(p);
-        return STITCH_OK;
-    }
-    void forget(void* p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); }
-    void give_up(void* p) { forget(p); }
-    void release(void* p) {
-        forget(p);
-        (void)hipFreeAsync(p, s);
-    }
-};
-
 struct PanoCfg {
     stitch_panorama_opts o;
     int feat_cap;
@@ -76,8 +49,8 @@ int pano_cfg(const stitch_panorama_opts* opts, const stitch_exposure_opts* expos
     c->ex = stitch_exposure_opts{0, 0, 0};
     if (exposure) {
         c->ex = *exposure;
-        if (c->ex.mode < 0 || c->ex.mode > 2) return fail(STITCH_ERR_ARG, "panorama: exposure mode %d (0 .. 2)", c->ex.mode);
-        if (c->ex.stats_form < 0 || c->ex.stats_form > 2) return fail(STITCH_ERR_ARG, "panorama: exposure stats_form %d (0 .. 2)", c->ex.stats_form);
+        int rc = chain_check_exposure(c->ex, "panorama");
+        if (rc) return rc;
     }
     if (opts)
         c->o = *opts;
@@ -90,25 +63,17 @@ int pano_cfg(const stitch_panorama_opts* opts, const stitch_exposure_opts* expos
     return STITCH_OK;
 }
 
+// What every entry point starts with: *out cleared, a device, then the frames.
 int pano_check_frames(const stitch_frame_u8* frames, int n, stitch_panorama** out) {
     if (out) *out = nullptr;
+    int rc = need_device();
+    if (rc) return rc;
     if (!out || !frames || n < 1 || n > kPanoMaxFrames) return fail(STITCH_ERR_ARG, "panorama: %d frames (1 .. %d) or a null argument", n, kPanoMaxFrames);
     for (int i = 0; i < n; ++i)
         if (!frames[i].data || frames[i].width <= 0 || frames[i].height <= 0)
             return fail(STITCH_ERR_ARG, "panorama: frame %d has no data or a bad size %d x %d", i, frames[i].width, frames[i].height);
     return STITCH_OK;
 }
-
-int pano_sync(hipStream_t s) {
-    HIPCHK(hipStreamSynchronize(s));
-    return STITCH_OK;
-}
-
-// Declared behind a host buffer that an enqueued copy reads: no return path lets the buffer go before the copy has run.
-struct PanoWait {
-    hipStream_t s;
-    ~PanoWait() { (void)hipStreamSynchronize(s); }
-};
 
 int dev_points_args(const float* x, const float* y, int n, const char* what) {
     if (n < 0 || (n > 0 && (!x || !y))) return fail(STITCH_ERR_ARG, "%s: bad argument", what);
@@ -124,24 +89,7 @@ int pano_select_and_fit(const int32_t* d_sd, const int32_t* d_count_sd, const in
     k_pair_select<<<(unsigned)std::min((cap + 255) / 256, 64), 256, 0, s>>>(d_sd, d_count_sd, n_dst, d_ds, d_count_ds, n_src, 0, cap, d_sel, d_sel_count);
     int rc = launch_check("k_pair_select");
     if (rc) return rc;
-    stitch_ransac_desc r[2];
-    std::memset(r, 0, sizeof r);
-    // a frame without features has no coordinate arrays: its lists are empty, the estimation never reads a point, and the
-    // descriptor only needs an address
-    const float* none = reinterpret_cast<const float*>(d_sel);
-    for (int k = 0; k < 2; ++k) {
-        r[k].src_x = src_x ? src_x : none;
-        r[k].src_y = src_y ? src_y : none;
-        r[k].dst_x = dst_x ? dst_x : none;
-        r[k].dst_y = dst_y ? dst_y : none;
-        r[k].pairs = d_sel;
-        r[k].count = d_sel_count;
-        r[k].n_max = cap;
-        r[k].mirror = k == 0;
-        r[k].p = d_p16 + 8 * k;
-        r[k].info = d_info10 + STITCH_RANSAC_INFO * k;
-    }
-    return stitch_dev_ransac_many(r, 2, ransac, s);
+    return chain_step_fit(src_x, src_y, dst_x, dst_y, d_sel, d_sel_count, cap, ransac, d_p16, d_info10, nullptr, s);
 }
 
 // Everything from the ordered features on: counts, order, steps, finish.  x / y of `feats` are this call's own arrays (the steps
@@ -150,28 +98,11 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
                std::vector<float*>& fy, int n, const PanoCfg& c, PanoArena& A, hipStream_t s, stitch_panorama* P) {
     int rc = STITCH_OK;
     // ---- all ordered pairs in one matcher call; the lists stay on the device ----
-    int32_t* d_counts = nullptr;
-    if ((rc = A.take(&d_counts, sizeof(int32_t) * n * n))) return rc;
-    HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * n * n, s));
-    std::vector<size_t> list_off((size_t)n * n, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            if (i != j) {
-                list_off[(size_t)i * n + j] = total;
-                total += align256(sizeof(int32_t) * 2 * std::max(feats[j].n, 1));
-            }
-    char* d_lists = nullptr;
-    if ((rc = A.take(&d_lists, total))) return rc;
-    auto list_of = [&](int i, int j) { return reinterpret_cast<int32_t*>(d_lists + list_off[(size_t)i * n + j]); };
-    std::vector<stitch_match_desc> md;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            if (i != j) md.push_back(stitch_match_desc{feats[i].d_desc, feats[j].d_desc, feats[i].n, feats[j].n, nullptr, nullptr, list_of(i, j), d_counts + (size_t)i * n + j});
-    if ((rc = stitch_dev_match_l1_ratio_many(md.data(), (int)md.size(), c.o.ratio, s))) return rc;
+    PairLists L;
+    if ((rc = chain_match_all(feats, 1, n, c.o.ratio, 0, A, s, &L))) return rc;
     // ---- read-back 2: the counts ----
     std::vector<int32_t> counts((size_t)n * n);
-    HIPCHK(hipMemcpyAsync(counts.data(), d_counts, sizeof(int32_t) * n * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(counts.data(), L.d_counts, L.count_bytes, hipMemcpyDeviceToHost, s));
     if ((rc = pano_sync(s))) return rc;
     std::vector<int32_t> order((size_t)2 * n * std::max(n - 1, 1));
     int start = 0, n_steps = 0;
@@ -193,11 +124,8 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
     int max_n = 1;
     for (int i = 0; i < n; ++i) max_n = std::max(max_n, feats[i].n);
     int32_t* d_sel = nullptr;
-    char* d_maps = nullptr;  // 16 doubles, 10 int32, the selected count
-    if ((rc = A.take(&d_sel, sizeof(int32_t) * 2 * max_n)) || (rc = A.take(&d_maps, 16 * sizeof(double) + 12 * sizeof(int32_t)))) return rc;
-    double* d_p16 = reinterpret_cast<double*>(d_maps);
-    int32_t* d_info10 = reinterpret_cast<int32_t*>(d_maps + 16 * sizeof(double));
-    int32_t* d_sel_count = d_info10 + 2 * STITCH_RANSAC_INFO;
+    StepBlock B;
+    if ((rc = A.take(&d_sel, sizeof(int32_t) * 2 * max_n)) || (rc = A.take(&B.d, StepBlock::kHead))) return rc;
 
     float* d_ex_stats = nullptr;  // twelve per step
     P->exposure_mode = c.ex.mode;
@@ -208,26 +136,15 @@ int pano_steps(const stitch_frame_u8* frames, std::vector<uint8_t*>& proj, const
 
     for (int k = 0; k < n_steps; ++k) {
         const int src = order[2 * k], dst = order[2 * k + 1];
-        if ((rc = pano_select_and_fit(list_of(src, dst), d_counts + (size_t)src * n + dst, list_of(dst, src), d_counts + (size_t)dst * n + src, fx[src],
-                                      fy[src], feats[src].n, fx[dst], fy[dst], feats[dst].n, d_sel, d_sel_count, c.o.ransac, d_p16, d_info10, s)))
+        if ((rc = pano_select_and_fit(L.list_of(0, src, dst), L.count_of(0, src, dst), L.list_of(0, dst, src), L.count_of(0, dst, src), fx[src], fy[src],
+                                      feats[src].n, fx[dst], fy[dst], feats[dst].n, d_sel, B.sel_count(), c.o.ransac, B.p16(), B.info10(), s)))
             return rc;
         // ---- read-back 3: 16 doubles and 10 ints ----
-        struct {
-            double p[16];
-            int32_t info[2 * STITCH_RANSAC_INFO];
-        } got;
-        HIPCHK(hipMemcpyAsync(&got, d_maps, 16 * sizeof(double) + 2 * STITCH_RANSAC_INFO * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if ((rc = pano_sync(s))) return rc;
-        if (got.info[0] != STITCH_RANSAC_OK || got.info[STITCH_RANSAC_INFO] != STITCH_RANSAC_OK)
-            return fail(STITCH_ERR_NO_MAP, "frames %d -> %d: no map (RANSAC status %d / %d, %d pairs)", src, dst, got.info[0], got.info[STITCH_RANSAC_INFO],
-                        got.info[1]);
+        unsigned char got[StepBlock::kBack];
         stitch_panorama_step st;
-        std::memset(&st, 0, sizeof st);
-        st.src = src;
-        st.dst = dst;
-        std::memcpy(st.p_fwd, got.p, sizeof st.p_fwd);
-        std::memcpy(st.p_bwd, got.p + 8, sizeof st.p_bwd);
-        std::memcpy(st.info, got.info, sizeof st.info);
+        bool ok = false;
+        if ((rc = chain_step_read(B, sizeof got, src, dst, s, got, &st, &ok))) return rc;
+        if (!ok) return fail(STITCH_ERR_NO_MAP, "frames %d -> %d: no map (RANSAC status %d / %d, %d pairs)", src, dst, st.info[0][0], st.info[1][0], st.info[0][1]);
         if ((rc = projected(dst))) return rc;
         const int fw = frames[dst].width, fh = frames[dst].height;
         if ((rc = stitch_step_geometry(fw, fh, st.p_fwd, rw, rh, &st.geom))) return rc;
@@ -418,7 +335,7 @@ int stitch_dev_pair_maps(const stitch_feature_set* src, const stitch_feature_set
     if (rc) return rc;
     if (!src || !dst || !d_p16 || !d_info10 || src->n < 0 || dst->n < 0) return fail(STITCH_ERR_ARG, "pair_maps: bad argument");
     for (const stitch_feature_set* f : {src, dst})
-        if (f->n > 0 && (!f->d_desc || !f->d_x || !f->d_y)) return fail(STITCH_ERR_ARG, "pair_maps: a feature set lacks an array");
+        if (feature_set_lacks_array(*f)) return fail(STITCH_ERR_ARG, "pair_maps: a feature set lacks an array");
     hipStream_t s = as_stream(stream);
     PanoArena A(s);
     const int cap = std::max(std::max(src->n, dst->n), 1);
@@ -439,16 +356,11 @@ namespace {
 
 int pano_from_features(const stitch_frame_u8* frames, const stitch_feature_set* feats, int n, const stitch_panorama_opts* opts,
                        const stitch_exposure_opts* exposure, void* stream, stitch_panorama** out) {
-    int rc = need_device();
-    if (rc) {
-        if (out) *out = nullptr;
-        return rc;
-    }
-    if ((rc = pano_check_frames(frames, n, out))) return rc;
+    int rc = pano_check_frames(frames, n, out);
+    if (rc) return rc;
     if (!feats) return fail(STITCH_ERR_ARG, "panorama: no feature sets");
     for (int i = 0; i < n; ++i)
-        if (feats[i].n < 0 || (feats[i].n > 0 && (!feats[i].d_desc || !feats[i].d_x || !feats[i].d_y)))
-            return fail(STITCH_ERR_ARG, "panorama: feature set %d lacks an array", i);
+        if (feature_set_lacks_array(feats[i])) return fail(STITCH_ERR_ARG, "panorama: feature set %d lacks an array", i);
     PanoCfg c;
     if ((rc = pano_cfg(opts, exposure, &c))) return rc;
     hipStream_t s = as_stream(stream);
@@ -464,145 +376,52 @@ int pano_from_features(const stitch_frame_u8* frames, const stitch_feature_set* 
         HIPCHK(hipMemcpyAsync(fy[i], feats[i].d_y, b, hipMemcpyDeviceToDevice, s));
     }
     std::vector<uint8_t*> proj((size_t)n, nullptr);
-    rc = pano_steps(frames, proj, feats, fx, fy, n, c, A, s, P.get());
-    const int rc2 = pano_sync(s);  // the finish pass and the copies above are complete; what the arena frees next is idle
-    if (rc) return rc;
-    if (rc2) return rc2;
-    *out = P.release();
-    return STITCH_OK;
+    return chain_publish(pano_steps(frames, proj, feats, fx, fy, n, c, A, s, P.get()), s, P, out);
 }
 
 int pano_from_frames(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, const stitch_exposure_opts* exposure, void* stream,
                      stitch_panorama** out) {
-    int rc = need_device();
-    if (rc) {
-        if (out) *out = nullptr;
-        return rc;
-    }
-    if ((rc = pano_check_frames(frames, n, out))) return rc;
+    int rc = pano_check_frames(frames, n, out);
+    if (rc) return rc;
     PanoCfg c;
     if ((rc = pano_cfg(opts, exposure, &c))) return rc;
     hipStream_t s = as_stream(stream);
     PanoArena A(s);
     std::unique_ptr<stitch_panorama> P(new stitch_panorama());
-    // ---- a. projection + gray per frame, one SIFT call over all of them ----
-    const size_t kc = (size_t)std::max(c.o.kp_cap, 1), fc = (size_t)std::max(c.feat_cap, 1);
+    // every frame's projected colours are kept: the steps warp them
     std::vector<uint8_t*> proj((size_t)n, nullptr);
-    std::vector<stitch_sift_desc> sd((size_t)n);
-    int32_t* d_heads = nullptr;  // per frame {counts[2], status[4], -, -}
-    if ((rc = A.take(&d_heads, sizeof(int32_t) * 8 * n))) return rc;
-    std::vector<void*> sift_blocks;
-    for (int i = 0; i < n; ++i) {
-        const int w = frames[i].width, h = frames[i].height;
-        uint8_t* gray = nullptr;
-        stitch_sift_desc& d = sd[i];
-        std::memset(&d, 0, sizeof d);
-        if ((rc = A.take(&proj[i], (size_t)3 * w * h)) || (rc = A.take(&gray, (size_t)w * h)) || (rc = A.take(&d.keypoints, kc * sizeof(StitchSiftKeypoint))) ||
-            (rc = A.take(&d.feat_kp, fc * sizeof(int32_t))) || (rc = A.take(&d.feat_angle, fc * sizeof(double))) ||
-            (rc = A.take(&d.feat_desc, fc * STITCH_DESCRIPTOR_DIM * sizeof(float))))
-            return rc;
-        for (void* p : {(void*)gray, (void*)d.keypoints, (void*)d.feat_kp, (void*)d.feat_angle, (void*)d.feat_desc}) sift_blocks.push_back(p);
-        if ((rc = stitch_dev_project_gray_u8(frames[i].data, w, h, c.o.fov_deg, proj[i], gray, nullptr, s))) return rc;
-        d.image = gray;
-        d.width = w;
-        d.height = h;
-        d.pitch = w;
-        d.is_f32 = 0;
-        d.kp_cap = c.o.kp_cap;
-        d.feat_cap = c.feat_cap;
-        d.counts = d_heads + 8 * i;
-        d.status = d_heads + 8 * i + 2;
-    }
-    if ((rc = stitch_dev_sift_many(sd.data(), n, c.o.sift, s))) return rc;
-    // ---- b. read-back 1: the heads, then the descriptor rows that were written ----
-    std::vector<int32_t> heads((size_t)8 * n);
-    HIPCHK(hipMemcpyAsync(heads.data(), d_heads, sizeof(int32_t) * 8 * n, hipMemcpyDeviceToHost, s));
-    if ((rc = pano_sync(s))) return rc;
-    size_t rows_total = 0;
-    for (int i = 0; i < n; ++i) {
-        const int32_t* hd = &heads[(size_t)8 * i];
-        if (hd[2] != STITCH_SIFT_OK)
-            return fail(STITCH_ERR_CAPACITY, "frame %d: SIFT capacities too small (%d keypoints, %d features found)", i, hd[3], hd[4]);
-        rows_total += (size_t)hd[1];
-    }
-    std::vector<float> rows(rows_total * STITCH_DESCRIPTOR_DIM);
-    std::vector<size_t> row0((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        const size_t cnt = (size_t)heads[(size_t)8 * i + 1];
-        row0[i + 1] = row0[i] + cnt;
-        if (cnt)
-            HIPCHK(hipMemcpyAsync(rows.data() + row0[i] * STITCH_DESCRIPTOR_DIM, sd[i].feat_desc, cnt * STITCH_DESCRIPTOR_DIM * sizeof(float),
-                                  hipMemcpyDeviceToHost, s));
-    }
-    if ((rc = pano_sync(s))) return rc;
-    // the map order on the host; only the index array goes back up
-    std::vector<int32_t> index(std::max<size_t>(rows_total, 1));
-    std::vector<int> kept((size_t)n, 0);
-    for (int i = 0; i < n; ++i)
-        if ((rc = stitch_feature_order(rows.data() + row0[i] * STITCH_DESCRIPTOR_DIM, (int)(row0[i + 1] - row0[i]), index.data() + row0[i], &kept[i]))) return rc;
-    int32_t* d_index = nullptr;
-    if ((rc = A.take(&d_index, sizeof(int32_t) * index.size()))) return rc;
-    PanoWait index_in_use{s};
-    HIPCHK(hipMemcpyAsync(d_index, index.data(), sizeof(int32_t) * index.size(), hipMemcpyHostToDevice, s));
+    auto colour_dst = [&](int i, uint8_t** p) -> int {
+        const int rc_ = A.take(&proj[i], (size_t)3 * frames[i].width * frames[i].height);
+        *p = proj[i];
+        return rc_;
+    };
+    SiftOrder S;
+    if ((rc = chain_sift_order(frames, n, c.o, c.feat_cap, colour_dst, [](int i) { return "frame " + std::to_string(i); }, A, s, &S))) return rc;
+    // a frame's ordered rows: its own three blocks; the steps update x / y in place
     std::vector<stitch_feature_set> feats((size_t)n);
     std::vector<float*> fx((size_t)n, nullptr), fy((size_t)n, nullptr);
-    for (int i0 = 0; i0 < n; i0 += PANO_MAXFRAMES) {
-        const int m = std::min(PANO_MAXFRAMES, n - i0);
-        FeatGatherArgs ga;
-        std::memset(&ga, 0, sizeof ga);
-        int max_rows = 0;
-        for (int k = 0; k < m; ++k) {
-            const int i = i0 + k;
-            float* od = nullptr;
-            if (kept[i] && ((rc = A.take(&od, sizeof(float) * STITCH_DESCRIPTOR_DIM * kept[i])) || (rc = A.take(&fx[i], sizeof(float) * kept[i])) ||
-                            (rc = A.take(&fy[i], sizeof(float) * kept[i]))))
-                return rc;
-            feats[i] = stitch_feature_set{od, fx[i], fy[i], kept[i]};
-            FeatGatherFrame& g = ga.f[k];
-            g.desc = sd[i].feat_desc;
-            g.fkp = sd[i].feat_kp;
-            g.kp = reinterpret_cast<const SiftKeypoint*>(sd[i].keypoints);
-            g.index = d_index + row0[i];
-            g.out_desc = od;
-            g.out_x = fx[i];
-            g.out_y = fy[i];
-            g.n = kept[i];
-            g.n_rows = heads[(size_t)8 * i + 1];
-            g.n_kp = heads[(size_t)8 * i];
-            max_rows = std::max(max_rows, kept[i]);
-        }
-        if (max_rows) {
-            k_feat_gather<<<dim3((unsigned)((max_rows + PANO_GATHER_T / WAVE - 1) / (PANO_GATHER_T / WAVE)), (unsigned)m), PANO_GATHER_T, 0, s>>>(ga);
-            if ((rc = launch_check("k_feat_gather"))) return rc;
-        }
-    }
-    for (void* p : sift_blocks) A.release(p);  // freed in stream order, behind the gather
-    rc = pano_steps(frames, proj, feats.data(), fx, fy, n, c, A, s, P.get());
-    const int rc2 = pano_sync(s);  // also: `index` has been read by its upload
-    if (rc) return rc;
-    if (rc2) return rc2;
-    *out = P.release();
-    return STITCH_OK;
+    auto place = [&](int i, float** od, float** ox, float** oy) -> int {
+        const size_t k = (size_t)S.kept[i];
+        int rc_ = STITCH_OK;
+        if (k && ((rc_ = A.take(od, sizeof(float) * STITCH_DESCRIPTOR_DIM * k)) || (rc_ = A.take(&fx[i], sizeof(float) * k)) || (rc_ = A.take(&fy[i], sizeof(float) * k))))
+            return rc_;
+        *ox = fx[i];
+        *oy = fy[i];
+        return STITCH_OK;
+    };
+    if ((rc = chain_gather(S, n, place, feats.data(), A, s))) return rc;
+    return chain_publish(pano_steps(frames, proj, feats.data(), fx, fy, n, c, A, s, P.get()), s, P, out);
 }
 
 int pano_from_host_frames(const stitch_frame_u8* frames, int n, const stitch_panorama_opts* opts, const stitch_exposure_opts* exposure,
                           stitch_panorama** out) {
-    int rc = need_device();
-    if (rc) {
-        if (out) *out = nullptr;
-        return rc;
-    }
-    if ((rc = pano_check_frames(frames, n, out))) return rc;
+    int rc = pano_check_frames(frames, n, out);
+    if (rc) return rc;
     PanoCfg c;  // refused options are refused before a frame goes up
     if ((rc = pano_cfg(opts, exposure, &c))) return rc;
-    std::vector<DevBuf> up((size_t)n);
-    std::vector<stitch_frame_u8> dev((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const size_t bytes = (size_t)3 * frames[i].width * frames[i].height;
-        if ((rc = up[i].alloc(bytes))) return rc;
-        H2D(up[i].p, frames[i].data, bytes);
-        dev[i] = stitch_frame_u8{up[i].as<uint8_t>(), frames[i].width, frames[i].height};
-    }
+    std::vector<DevBuf> up;
+    std::vector<stitch_frame_u8> dev;
+    if ((rc = chain_upload_frames(frames, n, &up, &dev))) return rc;
     return pano_from_frames(dev.data(), n, opts, exposure, nullptr, out);
 }
 

@@ -227,8 +227,7 @@ int rig_create(const int32_t* frame_wh, int n, int start, const stitch_panorama_
     int rc = rig_cfg(opts, R.get());
     if (rc) return rc;
     if (exposure) {
-        if (exposure->mode < 0 || exposure->mode > 2) return fail(STITCH_ERR_ARG, "rig: exposure mode %d (0 .. 2)", exposure->mode);
-        if (exposure->stats_form < 0 || exposure->stats_form > 2) return fail(STITCH_ERR_ARG, "rig: exposure stats_form %d (0 .. 2)", exposure->stats_form);
+        if ((rc = chain_check_exposure(*exposure, "rig"))) return rc;
         if (exposure->mode) R->ex = *exposure;
     }
     R->n = n;

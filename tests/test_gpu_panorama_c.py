@@ -144,6 +144,41 @@ def test_without_the_finish_pass(st, gpu):
     assert _sha(got) == _golden()["runs"]["2"]["steps"][-1]["out_sha256"]
 
 
+def test_more_frames_than_one_gather_launch(st, gpu):
+    """18 frames in one call: k_feat_gather takes 16 frames per launch, so the second, partial launch and the offsets into the one
+    index upload behind frame 15 are reached by the panorama itself, not only by the calibration.  Frames 0 .. 13 are black 128 x 96
+    frames: no feature, no neighbour, left out of the order.  The committed frames 1 .. 4 are frames 14 .. 17, so the launch boundary
+    lies between them and every step needs ordered sets from both launches.  The control is the Python chain composed of the stage
+    calls; the outcome (seen on an MI355X) is a mosaic of three steps, asserted as such.
+
+    The first 18 frames of the small17 captures were tried first: both chains end in the blend of a step with ERR_EMPTY_MIDROW and
+    a text that names no frame, which would hold nothing behind frame 15."""
+    import torch
+    black = torch.zeros((3, 96, 128), dtype=torch.uint8, device=gpu)
+    frames = [black.clone() for _ in range(14)] + _frames((1, 2, 3, 4), gpu)
+    assert len(frames) == 18 > 16
+    want, wsteps = pipeline.panorama_from_frames(frames, return_steps=True)
+    got, gsteps = capi.dev_panorama(frames, return_steps=True, keep_steps=True)
+    assert len(gsteps) == len(wsteps) == 3
+    used = {gsteps[0]["start"]} | {s["src"] for s in gsteps}
+    assert used == {14, 15, 16, 17}, used
+    for a, b in zip(gsteps, wsteps):
+        assert (a["start"], a["src"], a["mosaic_src"]) == (b["start"], b["src"], b["mosaic_src"])
+        assert ransac_ref.same_p(a["p"], b["p"]) and ransac_ref.same_p(a["p_fwd"], b["p_fwd"]), f"maps of step src {a['src']}"
+        assert np.float32(a["offx"]).tobytes() == np.float32(b["offx"]).tobytes() and np.float32(a["offy"]).tobytes() == np.float32(b["offy"]).tobytes()
+        assert (a["ox"], a["oy"], a["cw"], a["ch"]) == (b["ox"], b["oy"], b["cw"], b["ch"])
+        assert np.array_equal(a["info"], b["info"])
+        assert a["out"].shape == b["out"].shape and a["out"].cpu().numpy().tobytes() == b["out"].cpu().numpy().tobytes()
+    assert got.shape == want.shape and got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
+    # the order is the one the recorded match counts of the four frames give at frames 14 .. 17.  It is not the recorded run's order
+    # moved by 14 (start 16): getMiddleIndex compares a frame's index with queue positions, which skips frames only at low indices.
+    counts = np.zeros((18, 18), np.int32)
+    counts[14:, 14:] = np.load(os.path.join(GOLD, "match_pairs.npz"))["counts"]
+    start, order = capi.stitch_order_c(counts, 20)
+    assert (start, [tuple(o) for o in order]) == (15, [(15, 16), (15, 14), (16, 17)])
+    assert [(s["start"], s["mosaic_src"], s["src"]) for s in gsteps] == [(start, a, b) for a, b in order]
+
+
 def test_bad_frame_counts(st, gpu):
     f = _frames((1,), gpu)
     for frames in ([], f * 65):
