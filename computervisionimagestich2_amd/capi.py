@@ -166,6 +166,14 @@ CALIBRATE_SIGNATURES = _signatures(
     ("stitch_rig_from_calibration", i32, vp, vp, vp, vp),
 )
 
+# The same for include/stitch_rig_seams.h, fixed seams for a rig; tests/test_rig_seams_host.py holds it to that header.
+RIG_SEAMS_SIGNATURES = _signatures(
+    ("stitch_seam_from_sums", i32, i32, i32, i32, i32, i32, i32, vp), ("stitch_dev_pairs_seamed_*", i32, vp, vp, i32, vp, vp),
+    ("stitch_rig_fix_seams stitch_rig_seams", i32, vp, vp, i32), ("stitch_rig_clear_seams", i32, vp),
+    ("stitch_dev_rig_geometric_seams", i32, vp, vp, vp), ("stitch_dev_rig_coverage_u8", i32, vp, i32, i32, vp, vp),
+    ("stitch_rig_step_canvas", i32, vp, i32, vp, vp),
+)
+
 _lib = None
 
 
@@ -185,7 +193,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(PANORAMA_SIGNATURES.items()) + list(RIG_SIGNATURES.items()) + list(EXPOSURE_SIGNATURES.items()) \
-                + list(RIG_EXPOSURE_SIGNATURES.items()) + list(CALIBRATE_SIGNATURES.items()):
+                + list(RIG_EXPOSURE_SIGNATURES.items()) + list(CALIBRATE_SIGNATURES.items()) + list(RIG_SEAMS_SIGNATURES.items()):
             try:
                 f = getattr(L, name)
             except AttributeError:
@@ -234,6 +242,25 @@ def _opts(opts):
     if isinstance(opts, BlendOpts):
         return opts
     return BlendOpts(**opts)
+
+
+def _seam_array(seams):
+    """Seams as the library takes them, by their four integers: Seam records, or tuples whose first four entries are
+    (sum_a_x, n_a, sum_ov_x, n_ov) -- Seam.as_tuple() and the records of a step dict qualify."""
+    seams = list(seams)
+    arr = (Seam * max(len(seams), 1))()
+    for d, sm in zip(arr, seams):
+        v = sm.as_tuple() if isinstance(sm, Seam) else tuple(sm)
+        d.sum_a_x, d.n_a, d.sum_ov_x, d.n_ov = (int(x) for x in v[:4])
+    return arr
+
+
+def seam_from_sums(sum_a_x, n_a, sum_ov_x, n_ov, seam_rule, cw):
+    """stitch_seam_from_sums (host only): the Seam the scan derives from these four integers under seam_rule on a canvas cw wide;
+    raises StitchError(ERR_ARG) for integers no middle row of cw columns can give."""
+    s = Seam()
+    _chk(lib().stitch_seam_from_sums(int(sum_a_x), int(n_a), int(sum_ov_x), int(n_ov), int(seam_rule), int(cw), C.byref(s)))
+    return s
 
 
 def device_count():
@@ -1133,21 +1160,28 @@ class Plan(_Handle):
         _chk(_fn("stitch_dev_blend_", a)(self._h, _dp(a), _dp(b), _dp(out), _stream()))
         return out
 
-    def pair(self, frame, p, offx, offy, mosaic, ox, oy, out=None):
-        """Enqueue warp+move+blend of one pair on torch's current stream; `out` is (3,ch,cw)."""
+    def pair(self, frame, p, offx, offy, mosaic, ox, oy, out=None, seam=None):
+        """Enqueue warp+move+blend of one pair on torch's current stream; `out` is (3,ch,cw).  seam: as pairs' seams, one record."""
         import torch
         frame, mosaic = _timg(frame), _timg(mosaic)
         if out is None:
             out = torch.empty((3, self.ch, self.cw), dtype=frame.dtype, device=frame.device)
+        if seam is not None:
+            return self.pairs([(frame, p, offx, offy, mosaic, ox, oy, out)], seams=[seam])[0]
         _chk(_fn("stitch_dev_pair_", frame)(self._h, _dp(frame), frame.shape[2], frame.shape[1], _map8(p), offx, offy, _dp(mosaic),
                                             mosaic.shape[2], mosaic.shape[1], int(ox), int(oy), _dp(out), _stream()))
         return out
 
-    def pairs(self, items):
+    def pairs(self, items, seams=None):
         """Enqueue n <= max_pairs independent pairs as ONE launch sequence.  items: iterable of
         (frame, p, offx, offy, mosaic, ox, oy, out[, out_u8]) with device tensors; out_u8 (float frames only) receives the
-        mosaic as unsigned char as well.  Returns the list of `out` tensors."""
+        mosaic as unsigned char as well.  seams (stitch_dev_pairs_seamed_*): one Seam or (sum_a_x, n_a, sum_ov_x, n_ov, ...) tuple
+        per item, which replaces that pair's seam scan.  Returns the list of `out` tensors."""
         items = list(items)
+        if seams is not None:
+            seams = list(seams)
+            if len(seams) != len(items):
+                raise ValueError("one seam per item")
         arr = (PairDesc * len(items))()
         fn = None
         for d, it in zip(arr, items):
@@ -1166,7 +1200,10 @@ class Plan(_Handle):
                 import torch
                 assert out8.is_cuda and out8.is_contiguous() and out8.dtype == torch.uint8 and tuple(out8.shape) == (3, self.ch, self.cw)
                 d.out_u8 = out8.data_ptr()
-        _chk(fn(self._h, arr, len(items), _stream()))
+        if seams is not None:
+            _chk(_fn("stitch_dev_pairs_seamed_", items[0][0])(self._h, arr, len(items), _seam_array(seams), _stream()))
+        else:
+            _chk(fn(self._h, arr, len(items), _stream()))
         return [it[7] for it in items]
 
     def status(self, index=0):
@@ -1370,9 +1407,13 @@ class Rig(_Handle):
         return cls(h)
 
     @classmethod
-    def from_panorama(cls, pano, frames, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True, stats_form=2):
+    def from_panorama(cls, pano, frames, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True, stats_form=2,
+                      seams=None):
         """stitch_rig_from_panorama: pano is a Panorama (dev_panorama_handle), frames the tensors it was made from (sizes only).
-        exposure 1 / 2: stitch_rig_from_panorama_exposure, as from_steps; the handle's own mode is not read."""
+        exposure 1 / 2: stitch_rig_from_panorama_exposure, as from_steps; the handle's own mode is not read.
+        seams="recorded": fix_seams from the records of the panorama's own steps."""
+        if seams not in (None, "recorded"):
+            raise ValueError('seams: None or "recorded"')
         arr = (FrameU8 * max(len(frames), 1))(*[FrameU8(None, f.shape[2], f.shape[1]) for f in frames])
         keep, h = [], C.c_void_p()
         o = _rig_opts(opts, finish, num, den, max_sets, fov_deg, keep)
@@ -1381,7 +1422,15 @@ class Rig(_Handle):
             _chk(lib().stitch_rig_from_panorama_exposure(pano._h, arr, len(frames), C.byref(o), C.byref(e), C.byref(h)))
         else:
             _chk(lib().stitch_rig_from_panorama(pano._h, arr, len(frames), C.byref(o), C.byref(h)))
-        return cls(h)
+        rig = cls(h)
+        if seams == "recorded":
+            rec = []
+            for k in range(rig.n_steps):
+                st = PanoramaStep()
+                _chk(lib().stitch_panorama_step_at(pano._h, k, C.byref(st)))
+                rec.append(st.seam.as_tuple())
+            rig.fix_seams(rec)
+        return rig
 
     @classmethod
     def from_calibration(cls, cal, opts=None, finish=True, num=19.0, den=20.0, max_sets=16, fov_deg=15.0, exposure=0, keep_black=True, stats_form=2):
@@ -1396,6 +1445,45 @@ class Rig(_Handle):
     def step_plan(self, k):
         """stitch_rig_step_plan: the address of the batched workspace step k runs on (None before the first stitch call)."""
         return lib().stitch_rig_step_plan(self._h, int(k))
+
+    def fix_seams(self, seams):
+        """stitch_rig_fix_seams (host only): one Seam or (sum_a_x, n_a, sum_ov_x, n_ov, ...) tuple per step; every later stitch()
+        uses them for every set, and no set fails for its pixels.  Returns self."""
+        seams = list(seams)
+        _chk(lib().stitch_rig_fix_seams(self._h, _seam_array(seams), len(seams)))
+        return self
+
+    def clear_seams(self):
+        """stitch_rig_clear_seams: back to content seams.  Returns self."""
+        _chk(lib().stitch_rig_clear_seams(self._h))
+        return self
+
+    @property
+    def seams(self):
+        """stitch_rig_seams: the fixed records as Seam tuples, one per step ([] = content seams)."""
+        arr = (Seam * max(self.n_steps, 1))()
+        n = _chk(lib().stitch_rig_seams(self._h, arr, self.n_steps))
+        return [arr[k].as_tuple() for k in range(n)]
+
+    def geometric_seams(self):
+        """stitch_dev_rig_geometric_seams on torch's current stream, which it waits for: the seams of the cameras' footprints,
+        computed on the device and fixed.  Raises StitchError (ERR_EMPTY_MIDROW / ERR_ZERO_OVERLAP naming the step) where the
+        footprints give no seam; the rig then keeps the seams it had.  Returns self."""
+        _chk(lib().stitch_dev_rig_geometric_seams(self._h, None, _stream()))
+        return self
+
+    def coverage(self, step=-1, which=2, out=None, device=None):
+        """stitch_dev_rig_coverage_u8 on torch's current stream: step's canvas as a (ch, cw) uint8 tensor of 0 / 255 -- which = 0 the
+        warped frame's footprint, 1 the moved mosaic's, 2 either; step -1 is the last step: the validity mask of the output."""
+        import torch
+        cw, ch = C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_step_canvas(self._h, int(step), C.byref(cw), C.byref(ch)))
+        w, h = cw.value, ch.value
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=device or "cuda")
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= w * h
+        _chk(lib().stitch_dev_rig_coverage_u8(self._h, int(step), int(which), _dp(out), _stream()))
+        return out
 
     def stitch(self, sets, out=None, return_stats=False):
         """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for (with return_stats

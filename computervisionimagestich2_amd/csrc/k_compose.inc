@@ -198,11 +198,49 @@ __global__ __launch_bounds__(256) void k_load_canvases(const PX* __restrict__ a,
 
 // ---- B1: seam scan, ImageProcess.cpp:659-671,686-698 --------------------------------------------------------
 // One workgroup walks the middle row of the level-0 planes; integer sums are reduced with wavefront shuffles
-// and one LDS exchange.  Thread 0 derives ratio / ov / branch / start exactly as the reference does.
+// and one LDS exchange.  Thread 0 derives ratio / ov / branch / start exactly as the reference does (seam_finish).
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
+}
+
+// The tail of the scan, ImageProcess.cpp:686-698: ratio / ov / branch / start from the four integers, exactly as the reference
+// derives them (rule 0 in float, rule 1 in double).  Shared by k_seam, by the seams a caller states (k_seam_given, k_cover_seam:
+// k_rig_seams.inc) and by the host's stitch_seam_from_sums, so a given seam is the record the scan would have written.
+__host__ __device__ __forceinline__ SeamDev seam_finish(int s_a, int n_a, int s_o, int n_o, int seam_rule, int cw) {
+    SeamDev s;
+    s.sum_a_x = s_a;
+    s.n_a = n_a;
+    s.sum_ov_x = s_o;
+    s.n_ov = n_o;
+    s.ratio = s.ov = 0.f;
+    s.branch = 1;
+    s.start = cw;  // neutral mask (all zero) when the scan fails
+    s.thr = 0.0;
+    s.status = 0;
+    s.pad = 0;
+    if (n_a == 0)
+        s.status = -2;
+    else if (n_o == 0)
+        s.status = -3;
+    else if (seam_rule == 0) {
+        const float ratio = (float)(1.0 * (double)s_a / (double)n_a);
+        const float ov = (float)(1.0 * (double)s_o / (double)n_o);
+        s.ratio = ratio;
+        s.ov = ov;
+        s.branch = (ratio < ov) ? 0 : 1;
+        s.start = (int)(ov + 1.f);
+        s.thr = (double)ov;
+    } else {
+        const double ratio = (double)s_a / (double)n_a, ov = (double)s_o / (double)n_o;
+        s.ratio = (float)ratio;
+        s.ov = (float)ov;
+        s.branch = (ratio < ov) ? 0 : 1;
+        s.start = (int)(ov + 1.0);
+        s.thr = ov;
+    }
+    return s;
 }
 
 template <typename PX>
@@ -265,38 +303,7 @@ __global__ __launch_bounds__(1024) void k_seam(const float* __restrict__ g0_all,
             s_o += red[2][i];
             n_o += red[3][i];
         }
-        SeamDev s;
-        s.sum_a_x = s_a;
-        s.n_a = n_a;
-        s.sum_ov_x = s_o;
-        s.n_ov = n_o;
-        s.ratio = s.ov = 0.f;
-        s.branch = 1;
-        s.start = cw;  // neutral mask (all zero) when the scan fails
-        s.thr = 0.0;
-        s.status = 0;
-        s.pad = 0;
-        if (n_a == 0)
-            s.status = -2;
-        else if (n_o == 0)
-            s.status = -3;
-        else if (seam_rule == 0) {
-            const float ratio = (float)(1.0 * (double)s_a / (double)n_a);
-            const float ov = (float)(1.0 * (double)s_o / (double)n_o);
-            s.ratio = ratio;
-            s.ov = ov;
-            s.branch = (ratio < ov) ? 0 : 1;
-            s.start = (int)(ov + 1.f);
-            s.thr = (double)ov;
-        } else {
-            const double ratio = (double)s_a / (double)n_a, ov = (double)s_o / (double)n_o;
-            s.ratio = (float)ratio;
-            s.ov = (float)ov;
-            s.branch = (ratio < ov) ? 0 : 1;
-            s.start = (int)(ov + 1.0);
-            s.thr = ov;
-        }
-        *out = s;
+        *out = seam_finish(s_a, n_a, s_o, n_o, seam_rule, cw);
     }
 }
 

@@ -25,6 +25,7 @@
 #include "stitch_exposure.h"
 #include "stitch_rig_exposure.h"
 #include "stitch_calibrate.h"
+#include "stitch_rig_seams.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -788,9 +789,12 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
 }
 
 template <typename PX>
-int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src) {
+int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const SeamInts* given) {
     const Level& a = p->lv[0];
-    {
+    if (given) {  // include/stitch_rig_seams.h: the records from the caller's integers instead of the scan
+        StageTimer t(p, s, STITCH_K_SEAM, 0);
+        k_seam_given<<<1, 64, 0, s>>>(*given, n, a.w, p->opts.seam_rule, p->d_seam);
+    } else {
         StageTimer t(p, s, STITCH_K_SEAM, 0);
         // 256 work-items, not 1024: a 16-wavefront workgroup waits for a CU with that much room when other batches fill the chip
         // (1.7 ms per launch with four batches in flight)
@@ -837,8 +841,9 @@ bool src_fused_call(const stitch_plan* p, int n) {
 }
 
 // The launch sequence of n pairs (or of one dense-canvas blend, pa.a_dense): S1, seam scan, REDUCE, collapse.
+// given: the pairs' seams as their four integers (stitch_dev_pairs_seamed_*), or nullptr for the scan.
 template <typename PX>
-int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, int n, hipStream_t s, bool src) {
+int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, int n, hipStream_t s, bool src, const SeamInts* given = nullptr) {
     const Level& a = p->lv[0];
     int rc;
     // source-fused: level 0 is a function of the inputs, evaluated by its three consumers (a warped frame through an index
@@ -862,7 +867,7 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
         else
             k_compose<PX><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, 0);
     }
-    if ((rc = run_seam_mask<PX>(p, n, s, pa, src))) return rc;
+    if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given))) return rc;
     if ((rc = run_reduce<PX>(p, n, s, pa, src, zi))) return rc;
     if ((rc = run_collapse<PX>(p, n, outs, s, pa, src))) return rc;
     p->last_stream = s;
@@ -900,9 +905,22 @@ int dev_blend(stitch_plan* p, const PX* d_a, const PX* d_b, PX* d_out, void* str
     return run_pairs<PX>(p, pa, outs, 1, as_stream(stream), src);
 }
 
+// The four integers of a stated seam against a canvas of width cw (include/stitch_rig_seams.h): counts within the row, the
+// overlap within a, and each sum a possible sum of n distinct columns of 0 .. cw-1.
+int seam_check_sums(long long sum_a_x, long long n_a, long long sum_ov_x, long long n_ov, int cw, const char* what, int index) {
+    auto possible = [cw](long long sum, long long n) { return sum >= n * (n - 1) / 2 && sum <= n * cw - n * (n + 1) / 2; };
+    if (cw < 1 || n_ov < 1 || n_ov > n_a || n_a > cw || sum_ov_x > sum_a_x || !possible(sum_a_x, n_a) || !possible(sum_ov_x, n_ov))
+        return fail(STITCH_ERR_ARG,
+                    "%s %d: the sums %lld / %lld (a) and %lld / %lld (overlap) are not those of a middle row of %d columns (1 <= n_ov <= n_a <= cw, "
+                    "sum_ov_x <= sum_a_x, n(n-1)/2 <= sum <= n*cw - n(n+1)/2)",
+                    what, index, sum_a_x, n_a, sum_ov_x, n_ov, cw);
+    return STITCH_OK;
+}
+
 // n independent pairs (n <= plan capacity) through one launch sequence: every kernel covers all n pairs.
+// seams (stitch_dev_pairs_seamed_*): n host records whose four integers replace the scan, checked here before anything is enqueued.
 template <typename PX>
-int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream) {
+int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, const stitch_seam* seams = nullptr) {
     if (!p || !d) return fail(STITCH_ERR_ARG, "null plan or descriptor array");
     if (n < 1 || n > p->cap) return fail(STITCH_ERR_ARG, "pairs: n=%d outside 1..%d (plan capacity)", n, p->cap);
     int dev = -1;
@@ -938,7 +956,16 @@ int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream) {
         for (int j = 0; src && j < n; ++j)
             src = !ranges_overlap(d[i].out, ob, d[j].frame, sizeof(PX) * (size_t)3 * d[j].fw * d[j].fh) &&
                   !ranges_overlap(d[i].out, ob, d[j].mosaic, sizeof(PX) * (size_t)3 * d[j].mw * d[j].mh);
-    return run_pairs<PX>(p, pa, outs, n, as_stream(stream), src);
+    SeamInts given{};
+    for (int i = 0; seams && i < n; ++i) {
+        const int rc = seam_check_sums(seams[i].sum_a_x, seams[i].n_a, seams[i].sum_ov_x, seams[i].n_ov, p->cw, "pairs_seamed: pair", i);
+        if (rc) return rc;
+        given.v[i][0] = seams[i].sum_a_x;
+        given.v[i][1] = seams[i].n_a;
+        given.v[i][2] = seams[i].sum_ov_x;
+        given.v[i][3] = seams[i].n_ov;
+    }
+    return run_pairs<PX>(p, pa, outs, n, as_stream(stream), src, seams ? &given : nullptr);
 }
 
 template <typename PX>
@@ -2566,3 +2593,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_exposure.inc"
 #include "stitch_rig_exposure.inc"
 #include "stitch_calibrate.inc"
+#include "stitch_rig_seams.inc"

@@ -30,8 +30,15 @@ struct stitch_rig {
     float* ex_stats = nullptr;            // 16 floats per set and step, set-major
     double* ex_sums = nullptr;            // form 2: per span of 6 * max_sets planes of the longest plane
     void* ex_table = nullptr;             // form 2: the span table (ExSpanEntry)
+    // ---- fixed seams and coverage (include/stitch_rig_seams.h; stitch_rig_seams.inc) ----
+    std::vector<stitch_seam> fixed;  // one record per step, or empty: content seams
+    int cover_device = -1;           // the device of the coverage planes, -1: not computed yet
+    unsigned long long* cover = nullptr;         // every plane, one block: C_proj per distinct frame size, then A, B, A | B per step
+    std::vector<size_t> cover_proj, cover_step;  // word offsets: per frame (its size's plane), per step (A; B and A | B follow)
+    std::vector<SeamDev> cover_seams;            // the scan of every step over coverage
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
+        if (cover) (void)hipFree(cover);
         for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
             if (p) (void)hipFree(p);
         for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
@@ -440,7 +447,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             }
             // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
             if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
-            if ((rc = stitch_dev_pairs_u8(R->plans[pi], pd.data(), m, s))) return rc;
+            if (!R->fixed.empty()) {  // include/stitch_rig_seams.h: the step's fixed record for each of the m sets
+                const std::vector<stitch_seam> given((size_t)m, R->fixed[k]);
+                if ((rc = stitch_dev_pairs_seamed_u8(R->plans[pi], pd.data(), m, given.data(), s))) return rc;
+            } else if ((rc = stitch_dev_pairs_u8(R->plans[pi], pd.data(), m, s)))
+                return rc;
             O.pending_step[pi] = k;
             cur = R->mosaic[k & 1];
             cur_stride = R->mosaic_bytes;

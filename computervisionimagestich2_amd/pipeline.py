@@ -126,7 +126,7 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
     return proj_dst
 
 
-def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True):
+def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -137,6 +137,8 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     the creation of the three workspaces).  Close them with close_plans(plans).
     exposure 1 / 2: every step first matches the frame's colours to the frame it is stitched to (the step's "mosaic_src") / to the
     running mosaic (exposure_match; include/stitch_exposure.h), keep_black leaving the projection's black corners black.
+    seams: per step a capi.Seam or a tuple (sum_a_x, n_a, sum_ov_x, n_ov, ...) that replaces the step's seam scan
+    (include/stitch_rig_seams.h): the single-set chain with given seams, the yardstick of a rig with fixed seams.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     proj = {}
 
@@ -145,9 +147,13 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             proj[i] = capi.dev_project(frames[i])
         return proj[i]
 
+    if seams is not None:
+        seams = list(seams)
+        if len(seams) != len(steps):
+            raise ValueError("one seam per step")
     result = projected(steps[0]["start"])
     used = []
-    for st in steps:
+    for k, st in enumerate(steps):
         key = (st["cw"], st["ch"])
         plan = plans.get(key) if plans is not None else None
         if plan is None:
@@ -158,7 +164,7 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             plan.status()
         if exposure:
             exposure_match(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black)
-        result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])
+        result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"], seam=None if seams is None else seams[k])
         used.append(plan)
     if finish:
         capi.dev_finish(result, num, den)
