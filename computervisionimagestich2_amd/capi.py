@@ -200,6 +200,8 @@ def lib():
                 raise ImportError(f"{LIB_PATH} does not export {name}: it was built from another include/stitch.h") from None
             f.restype, f.argtypes = res, args
         L.stitch_plan_handoff_counts.restype, L.stitch_plan_handoff_counts.argtypes = i32, [vp, vp]  # include/stitch_handoff.h
+        if hasattr(L, "stitch_plan_g_flag_counts"):  # include/stitch_g_flags.h (an A/B build of an earlier tree, STITCH_LIB, lacks it)
+            L.stitch_plan_g_flag_counts.restype, L.stitch_plan_g_flag_counts.argtypes = i32, [vp, vp]
         _lib = L
     return _lib
 
@@ -1222,6 +1224,13 @@ class Plan(_Handle):
         and as the one-word zero marker, and level-0 mask tiles recorded instead of stored (stitch_plan_handoff_counts)."""
         out = (C.c_uint64 * 3)()
         _chk(lib().stitch_plan_handoff_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def g_flag_counts(self):
+        """-> (level 1, level 2): tile columns of the pyramid planes that the plan's last call recorded as all +0 instead of storing
+        them (stitch_plan_g_flag_counts)."""
+        out = (C.c_uint64 * 2)()
+        _chk(lib().stitch_plan_g_flag_counts(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_handoff_spin_limit(self, polls):

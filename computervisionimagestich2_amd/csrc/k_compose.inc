@@ -125,6 +125,18 @@ struct ZeroTiles {
     __device__ __forceinline__ size_t index(long plane, int band, int tile) const { return ((size_t)plane * NC + tile) * NR + band; }
 };
 
+// G column flags: the same idea for the pyramid planes G_1 and G_2 of a batch, one byte per (plane, 64-column tile column), written
+// by the decimating sweep that produces the level (k_vv_y_bwd_dec) on every call.  A set byte means: every sample of the tile column,
+// in all rows, is +0.0f by bit pattern, BOTH neighbouring tile columns are +0.0f throughout as well (the plane's edge counts as
+// one), and the column was NOT stored -- the memory holds whatever an earlier call left.  Carried as a ZeroTiles with one "band":
+// index(plane, 0, tile) = plane * NC + tile.  Readers (k_vv_x_fwd, the collapse kernels) take zeros instead of loading; a 16-byte
+// load of the collapse that straddles two tile columns is zero when either column is flagged: a flagged column's neighbours are zero,
+// and an unflagged DATA column never has a flagged neighbour.
+__host__ __device__ inline ZeroTiles g_cols(uint8_t* flags, int w) { return ZeroTiles{flags, 0, 1, (w + 63) / 64}; }
+__device__ __forceinline__ bool g_col_flag(const uint8_t* __restrict__ flags, int nc, int plane, int col) {
+    return flags[(size_t)plane * nc + min(col >> 6, nc - 1)] != 0;
+}
+
 constexpr int SI_ROWS = 8;  // rows per workgroup of k_src_index (a one-row workgroup is launch-bound: 393k workgroups per batch)
 template <typename PX>
 __global__ __launch_bounds__(256) void k_src_index(PairArgs<PX> pa, float* __restrict__ g0_all, int cw, int ch, int pitch, size_t ps,

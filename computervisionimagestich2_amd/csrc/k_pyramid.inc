@@ -205,7 +205,17 @@ struct CollapseArgs {
     int u8_words;  // level 0: rows of the unsigned char destination(s) start on 32-bit boundaries (w % 4 == 0, aligned buffers)
     int lockstep;  // k_collapse4: the three channel wavefronts of a workgroup meet at a barrier every row (see collapse_cols4)
     int swizzle;   // k_collapse4: column blocks handed to the XCDs in contiguous runs (see k_collapse4)
+    // G column flags (g_cols) of this level and of level l+1, [7 planes per pair][tile columns]; nullptr: every column is stored.
+    // A flagged column is not loaded: the address goes to the zeros that lie behind the level's last plane for good (its slack
+    // rows, never written), zo / zon floats behind g_all / gn_all.  The loads themselves stay unconditional.
+    const uint8_t *gz, *gzn;
+    int gnc, gncn;
+    unsigned zo, zon;
 };
+// the samples at columns x and x2 (x <= x2 <= x + 3) of a plane are both taken as zeros: either tile column is flagged
+__device__ __forceinline__ bool g_span_flag(const uint8_t* __restrict__ flags, int nc, int plane, int x, int x2) {
+    return flags != nullptr && (g_col_flag(flags, nc, plane, x) || g_col_flag(flags, nc, plane, x2));
+}
 
 // one column x, rows [y0, y1) of pair pr
 template <typename OUT, bool DENSE>
@@ -227,13 +237,25 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
     const int ix = tb.ix[x], ix2 = ix < sw - 1 ? ix + 1 : ix;
     const double ax = tb.ax[x];
     const bool x_nearest = (sw == 1), y_nearest = (sh == 1);
+    // G column flags, looked up once per work-item: bit q = plane q of level l+1 at this column's two taps, bit 8 + q = plane q of
+    // this level at column x; a flagged sample is read from the zeros behind the level's last plane (CollapseArgs::zo / zon)
+    unsigned gzb = 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        if (g_span_flag(A.gzn, A.gncn, pr * 7 + q, ix, ix2)) gzb |= 1u << q;
+        if (!DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + q, x, x)) gzb |= 0x100u << q;
+    }
+    const size_t zn = (size_t)A.zon - (size_t)pr * 7 * sps, zg = (size_t)A.zo - (size_t)pr * 7 * ps;  // the zeros, from gn / g
     // x pass of one source row for the nine planes that are expanded: a0..a2, b0..b2 of G_{l+1}, then E_{l+1}
     auto xrow = [&](int row, float X[9]) {
         const size_t o1 = (size_t)row * spitch + ix, o2 = (size_t)row * spitch + ix2;
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
             const float* pl = q < 6 ? gn + q * sps : en + (q - 6) * sps;
-            X[q] = x_nearest ? pl[o1] : lerp_ref(ax, pl[o1], pl[o2]);
+            if (q < 6 && ((gzb >> q) & 1u) != 0)
+                X[q] = x_nearest ? gn[zn] : lerp_ref(ax, gn[zn], gn[zn + 1]);
+            else
+                X[q] = x_nearest ? pl[o1] : lerp_ref(ax, pl[o1], pl[o2]);
         }
     };
     float X1[9], X2[9];
@@ -261,7 +283,14 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
         const size_t o = (size_t)y * pitch + x;
         const float m = seam_l0 ? m_step : g[o + 6 * ps];
         float ga[3], gb[3];
-        level_ab(A.pa, pr, A.use_src, g, o, ps, x, y, ga, gb);
+        if (!DENSE && gzb >= 0x100u) {  // some plane of this level is flagged at x: its samples come from the zeros
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                ga[c] = g[((gzb >> (8 + c)) & 1u) != 0 ? zg : o + c * ps];
+                gb[c] = g[((gzb >> (11 + c)) & 1u) != 0 ? zg : o + (3 + c) * ps];
+            }
+        } else
+            level_ab(A.pa, pr, A.use_src, g, o, ps, x, y, ga, gb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float ea = y_nearest ? X1[c] : lerp_ref(ay, X1[c], X2[c]);
@@ -478,6 +507,17 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
         e1 = ix4.y >= A.sw - 1, e2 = ix4.z >= A.sw - 1, e3 = ix4.w >= A.sw - 1;
 #endif  // (column x0 itself never: a group spans three samples)
     }
+    // G column flags, looked up once per work-item: its four columns lie in one tile column of this level, their taps s0 .. s0+3 in
+    // one or two of level l+1 (g_cols).  A flagged plane is read from the zeros behind the level's last plane instead, every row from
+    // the same 16 bytes; the loads themselves stay unconditional.
+#ifdef STITCH_G_IGNORE_COARSER  // (defined only to prove that the stale-data test sees a collapse that ignores the coarser level's flags)
+    const bool za = false, zb = false;
+#else
+    const bool za = g_span_flag(A.gzn, A.gncn, pr * 7 + c, s0, s0 + 3), zb = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, s0, s0 + 3);
+#endif
+    const bool zga = !DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + c, x0, x0), zgb = !DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + 3 + c, x0, x0);
+    const unsigned zsa = (unsigned)((size_t)A.zon - ((size_t)pr * 7 + c) * sps), zsb = (unsigned)((size_t)A.zon - ((size_t)pr * 7 + 3 + c) * sps);
+    const size_t zg = (size_t)A.zo - (size_t)pr * 7 * ps;
     double axs[4];
     {
         const double2 a01 = *reinterpret_cast<const double2*>(tb.ax + x0), a23 = *reinterpret_cast<const double2*>(tb.ax + x0 + 2);
@@ -489,7 +529,7 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
 #if STITCH_C4_ABLATE == 1 || STITCH_C4_ABLATE >= 8  // counter experiments only (wrong results): the coarser level is not read
         const f4 v[3] = {f4{0.f, 0.f, 0.f, (float)o}, f4{0.f, 0.f, 0.f, 1.f}, f4{0.f, 0.f, 0.f, 2.f}};
 #else
-        const f4 v[3] = {*reinterpret_cast<const f4u*>(sa + o), *reinterpret_cast<const f4u*>(sb + o), *reinterpret_cast<const f4u*>(se + o)};
+        const f4 v[3] = {*reinterpret_cast<const f4u*>(sa + (za ? zsa : o)), *reinterpret_cast<const f4u*>(sb + (zb ? zsb : o)), *reinterpret_cast<const f4u*>(se + o)};
 #endif
 #if STITCH_C4_OPAQUE_ALPHA
         // registers are what bounds the number of resident wavefronts here: keep the four alphas, not also the four
@@ -540,7 +580,7 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
             src.issue(AD ? u4{0u, 0u, 0u, 0u} : *reinterpret_cast<const u4*>(g + o), y, ga, gb);
 #endif
         else {
-            const f4 va = *reinterpret_cast<const f4*>(g + o + c * ps), vb = *reinterpret_cast<const f4*>(g + o + (3 + c) * ps);
+            const f4 va = *reinterpret_cast<const f4*>(g + (zga ? zg : o + c * ps)), vb = *reinterpret_cast<const f4*>(g + (zgb ? zg : o + (3 + c) * ps));
 #pragma unroll
             for (int j = 0; j < 4; ++j) ga[j] = va[j], gb[j] = vb[j];
         }
@@ -716,12 +756,16 @@ __global__ __launch_bounds__(256) void k_collapse_px(CollapseArgs<float, false> 
         return;
     }
     const ExpandPos ep = expand_pos(A.tb, x, y, A.sw, A.sh, A.spitch);
+    const int ix = A.tb.ix[x], ix2 = ix < A.sw - 1 ? ix + 1 : ix;  // the two x taps (expand_pos)
     const float m = g[i + 6 * A.ps];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float ea = expand_at(gn + c * A.sps, ep), eb = expand_at(gn + (3 + c) * A.sps, ep), ee = expand_at(en + c * A.sps, ep);
-        const float la = g[i + c * A.ps] - ea;
-        const float lb = g[i + (3 + c) * A.ps] - eb;
+        // G column flags: a flagged sample is +0 and is not loaded (an interpolation between zeros is +0: the weights are in [0, 1])
+        const bool za = g_span_flag(A.gzn, A.gncn, pr * 7 + c, ix, ix2), zb = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, ix, ix2);
+        const bool zga = g_span_flag(A.gz, A.gnc, pr * 7 + c, x, x), zgb = g_span_flag(A.gz, A.gnc, pr * 7 + 3 + c, x, x);
+        const float ea = za ? 0.f : expand_at(gn + c * A.sps, ep), eb = zb ? 0.f : expand_at(gn + (3 + c) * A.sps, ep), ee = expand_at(en + c * A.sps, ep);
+        const float la = (zga ? 0.f : g[i + c * A.ps]) - ea;
+        const float lb = (zgb ? 0.f : g[i + (3 + c) * A.ps]) - eb;
         const float s_ = blend_ref(la, lb, m);
         float v = s_ + ee;
         if (v > 255.f)

@@ -176,7 +176,8 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
     // frame channels: tile t of this band lies outside the frame altogether (k_src_index's flag): its samples are +0
     auto tile_outside = [&](int t) -> bool {
         if constexpr (SRC) return gen_frame && zi.flags && zi.flags[zi.index(src_pr, src_y0 >> 6, t)];
-        return false;
+        // planes of G_1 / G_2: `zi` carries the level's G column flags (g_cols; per-plane bands) -- a flagged tile column was not stored
+        return zi.flags && zi.flags[zi.index(plane, 0, t)];
     };
     auto index_tile = [&](int t) {
         if constexpr (SRC)
@@ -197,6 +198,7 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
         iplus = gen_mask     ? (double)mask_step(sd, w - 1)
                 : gen_frame  ? (double)src_px<PX>(rs, true, reinterpret_cast<const unsigned*>(idx_rows)[(size_t)lane * pitch + (w - 1)])
                 : gen_mosaic ? (double)src_px<PX>(rs, false, mosaic_offset<PX>(mosaic_row<PX>(ms, src_y0 + lane), mosaic_col<PX>(ms, w - 1, w)))
+                : tile_outside(ntiles - 1) ? 0.0
                              : (double)in[(size_t)line * pitch + (w - 1)];
     double v1 = 0, v2 = 0, v3 = 0;
     f4 pre[16];
@@ -216,6 +218,8 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
                 else                                                           \
                     mosaic_indices<PX>(ms, ((T) + 1) * TS, lane, src_y0, w, nidx); \
             }                                                                  \
+        } else if (tile_outside(T)) {                                          \
+            _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) pre[i_] = f4{0.f, 0.f, 0.f, 0.f}; \
         } else                                                                 \
             tile_load(ib, pitch, (T) * TS, lane, pre);                         \
     } while (0)
@@ -236,13 +240,17 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
             if (lane == 0) zt.flags[zt.index(plane, band_y0 / TS, t)] = 1;
             continue;
         }
+        // a level without flags of T (level 2 of a batch), zeros in under a zero state: the tile of zeros is stored as it was
+        // fetched (it was not loaded: G column flags), the sweep over it is skipped -- the state stays +0
+        const bool zskip = !SRC && !CKPT && !zt.flags && tile_outside(t) &&
+                           (t == 0 || __ballot(live && (__double_as_longlong(v1) | __double_as_longlong(v2) | __double_as_longlong(v3)) != 0) == 0);
         if constexpr (SRC)
             if (!gen_mask) src_finish<PX>(gen_frame, pre);
         tile_to_lds(tile, lane, pre);
         if (t + 1 < ntiles) STITCH_X_FETCH(t + 1);
         __syncthreads();  // one wave per workgroup: orders the tile writes before the per-lane row reads
         float* row = tile + lane * TP;
-        const int jmax = min(TS, w - t * TS);
+        const int jmax = zskip ? 0 : min(TS, w - t * TS);
         if (t == 0) v1 = v2 = v3 = (double)row[0] / k.sumsq;  // CImg.h:34909
         if (CKPT && t > 0 && live) {
             double* c = ckpt + (size_t)(3 * t) * lines + line;
@@ -697,7 +705,7 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
                                                       VVK k, const double* __restrict__ state, float* __restrict__ dst,
                                                       int w2, int h2, int dpitch, size_t dps, ZeroTiles zt,
                                                       const double* __restrict__ resume, double* __restrict__ state_out, int wh, int wh2,
-                                                      int x_base = 0, int fill_l0 = 0) {
+                                                      int x_base = 0, int fill_l0 = 0, ZeroTiles gz = ZeroTiles{}) {
     static_assert(!(XCH && ODD), "column chunks: even widths");
     // wh, wh2: the heights the decimation's overlap weights are taken from (CImg.h:29557-29575 weights by the LEVEL's
     // heights): h, h2 for a whole level; for a row band of a split pair the level's, not the band's (the quotient is the same
@@ -805,11 +813,49 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
             const bool allz0 = __all(mine_all && sb == 0ull) && !fill_on;  // (on a fill plane a flag stands for row 0, not for zeros)
             if (lane == 0) s_allz = allz0 ? 1 : 0;
         }
+        // G column flags of the level being produced (even, whole-width launches only: a workgroup's 64 output columns are then ONE
+        // tile column, blockIdx.x): meanwhile the consumer wavefront asks the same question of the two neighbouring workgroups -- their
+        // input tiles flagged in every band, their y state and Triggs value +0 -- since the zeros are left unstored only where both
+        // neighbours are zero as well (see g_cols; the plane's edge counts as a zero neighbour, a fill plane never qualifies).
+        const bool gz_on = !ODD && !XCH && gz.flags != nullptr;  // workgroup-uniform
+        __shared__ int s_nbz;
+        if (gz_on && wave == 1) {
+            bool ok = !fill_on && blockIdx.y % 7 != 6;  // (the mask plane has no flags: the collapse reads it as it stands)
+            for (int side = -1; side <= 1; side += 2) {
+                const int nb = (int)blockIdx.x + side, tN = 2 * nb;
+                if (nb < 0 || nb >= gz.NC) continue;  // workgroup-uniform
+                bool flagged = tN + 1 < zt.NC;
+                for (int g = 0; g < 4 && flagged; ++g) {
+                    if (g * 64 < zt.NR) {
+                        const int band = g * 64 + lane;
+                        const bool inb = band < zt.NR;
+                        const unsigned char fa = inb ? zt.flags[zt.index(blockIdx.y, band, tN)] : 1;
+                        const unsigned char fb = inb ? zt.flags[zt.index(blockIdx.y, band, tN + 1)] : 1;
+                        flagged = __all(fa != 0 && fb != 0);
+                    }
+                }
+                unsigned long long sn = 0ull;
+                const int xn = (nb * WAVE + lane) * 2;
+                if (flagged && xn < pitch) {
+                    Y2 q;
+                    f2 qf;
+                    y2_triggs(k, state, (size_t)gridDim.y * sp, ystate_index(blockIdx.y, sp, xn), q, qf);
+                    sn = (unsigned long long)__double_as_longlong(q.a1) | (unsigned long long)__double_as_longlong(q.a2) |
+                         (unsigned long long)__double_as_longlong(q.a3) | (unsigned long long)__double_as_longlong(q.b1) |
+                         (unsigned long long)__double_as_longlong(q.b2) | (unsigned long long)__double_as_longlong(q.b3) |
+                         (unsigned long long)(__float_as_uint(qf.x) | __float_as_uint(qf.y));
+                }
+                ok = ok && flagged && __all(sn == 0ull);
+            }
+            if (lane == 0) s_nbz = ok ? 1 : 0;
+        }
         __syncthreads();
+        const bool g_skip = gz_on && s_allz != 0 && s_nbz != 0;  // workgroup-uniform
+        if (gz_on && threadIdx.x == 0 && (int)blockIdx.x < gz.NC) gz.flags[gz.index(blockIdx.y, 0, blockIdx.x)] = g_skip ? 1 : 0;  // every byte, every call
         if (s_allz != 0) {  // workgroup-uniform
             if (wave == 1) {
                 const int tx_ = blockIdx.x * ADV + lane + (XCH ? x_base / 2 : 0);
-                if (tx_ < w2 && (!ODD || lane < WAVE - 1)) {
+                if (!g_skip && tx_ < w2 && (!ODD || lane < WAVE - 1)) {
                     float* dc = dst + blockIdx.y * dps + tx_;
                     for (int t = 0; t < h2; ++t) dc[(size_t)t * dpitch] = 0.f;
                 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "stitch.h"
+#include "stitch_g_flags.h"
 #include "stitch_handoff.h"
 #include "stitch_panorama.h"
 #include "stitch_rig.h"
@@ -310,6 +311,8 @@ struct stitch_plan {
     uint8_t* zi = nullptr;         // [cap][tiles][bands] of level 0: "every pixel of the tile lies outside the frame" (k_src_index)
     uint8_t* zt = nullptr;         // zero-tile flags of T, [7*cap][bands][tiles] of level 0 (ZeroTiles); reused level by level
     bool zero_tiles = false;
+    uint8_t* gz[2] = {nullptr, nullptr};  // G column flags of levels 1 and 2, [7*cap][tile columns] (g_cols; g_flags_call decides per call)
+    bool gz_last[2] = {false, false};     // the last call used them (stitch_plan_g_flag_counts)
     const float* zero_page = nullptr;  // 4 KB of zeros in the arena (k_vv_xby_m's loader reads a flagged tile from here)
     int wf_max_wgs = 2304;  // persistent workgroups of the fused sweep (STITCH_XBYF_WGS)
     unsigned wf_spin_limit = 1u << 23;  // polls before a hand-off wait gives up, about 20 s (STITCH_XBYF_SPIN_LIMIT); 2^20 (2-3 s) was reached once in a warm-up
@@ -399,6 +402,36 @@ bool fused_sweep_call(const stitch_plan* p, int n) {
     return p->tune.wavefront >= 0 || p->tune.single_fast > 0 || n >= 2 || (p->tune.xbym == 0 && 7L * ((p->lv[0].h + TS - 1) / TS) >= 800);
 }
 
+// G column flags of level l (1 or 2) in a call with n pairs, or none (see g_cols, k_compose.inc): the ONE place that decides.  They are on
+// only where the level's producer AND every kernel that reads G_l later in the same call know them:
+//   producer        k_vv_y_bwd_dec with T flags behind the fused sweep of level l-1, even width (the ODD instance advances by 63 columns);
+//   x sweep of l    k_vv_x_fwd (not its CKPT form nor k_vv_xbyf MODE 1, which fetch G_l again: no flags under STITCH_RECOMPUTE; not
+//                   k_vv_x_m, which a small batch takes; not the copy of a width of 1);
+//   collapse        k_collapse4 / k_collapse / k_collapse_px of levels l-1 and l, all three (CollapseArgs::gz, gzn);
+//   not             k_coarse and k_blend_top (levels from coarse_from on, the top level), the band path and the coarse levels of a split
+//                   pair (planes_in), the lone-pair sweeps (they never run in a call that takes the fused sweep), k_decimate (its level
+//                   has no T flags, so no producer).
+// The collapse reads a flagged column from the level's slack rows, at a 32-bit offset from its plane: levels beyond that are left alone.
+// STITCH_NO_G_FLAGS (compile time, A/B libraries): never.
+ZeroTiles g_flags_call(const stitch_plan* p, int n, int l) {
+#ifdef STITCH_NO_G_FLAGS
+    return ZeroTiles{};
+#else
+    if (l < 1 || l > 2 || !p->gz[l - 1] || !p->zero_tiles || p->planes_in || p->no_fuse || p->opts.blur_kind != 0 || p->blur_skip ||
+        p->recompute != 0 || p->wf_dbg || !fused_sweep_call(p, n))
+        return ZeroTiles{};
+    if (l >= (p->coarse_from > 0 ? p->coarse_from : p->L - 1)) return ZeroTiles{};
+    const Level& a = p->lv[l - 1];
+    const Level& b = p->lv[l];
+    if (l - 1 >= p->wf_levels || a.w < 2 || a.h < 2 || (a.w & 1) != 0 || (a.h + TS - 1) / TS > 256 || (p->tune.gate64 && a.h % TS)) return ZeroTiles{};
+    if (b.w < 2) return ZeroTiles{};
+    const bool fused_l = l < p->wf_levels && b.h > 1;
+    if (!fused_l && p->tune.mover != 0 && 7L * n * ((b.h + TS - 1) / TS) <= 340) return ZeroTiles{};
+    if (7ull * p->cap * b.ps + 64ull * b.pitch >= (1ull << 32)) return ZeroTiles{};  // (in samples)
+    return g_cols(p->gz[l - 1], b.w);
+#endif
+}
+
 // One pair in flight: the anticausal x and the causal y sweep of level l as ONE launch of five-wavefront bands (k_vv_xby_m) where the
 // separate launches are bound by their bytes -- from STITCH_XBYM_MPIX megapixels per plane (default 20: 6144 x 4096).  Below that a level's time is
 // its chain of rows and columns either way, and the fused form adds a hand-off per 64-row band.  STITCH_XBYM=0: never; =1: the first
@@ -417,6 +450,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
     const bool any_lone_fused = lone_fused_level(p, n, 0);  // levels shrink: level 0 qualifies whenever any level does
     if (p->wf_levels > 0 || any_lone_fused) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
     const int l_end = p->coarse_from > 0 ? p->coarse_from : p->L - 1;  // levels [0, l_end) are reduced level by level
+    for (int i = 0; i < 2; ++i) p->gz_last[i] = g_flags_call(p, n, i + 1).flags != nullptr;
     for (int l = 0; l < l_end; ++l) {
         const Level& a = p->lv[l];
         const Level& b = p->lv[l + 1];
@@ -452,8 +486,12 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
         }
         // blocks of the x sweeps: per-plane bands wherever a block's treatment depends on its plane (implicit mask, source-fused
         // level 0, zero-tile flags), 64 stacked lines otherwise (fewer blocks when planes are shorter than 64 rows)
+        // G column flags (g_flags_call): of this level's planes for the causal x sweep, of the next level's for the sweep that produces them
+        const ZeroTiles gin = g_flags_call(p, n, l), gout = g_flags_call(p, n, l + 1);
+        if (gout.flags && !(wavefront && zt.flags && (a.w & 1) == 0)) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their producer", l + 1);
+        if (gin.flags && !do_x) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their reader", l);
         Bands bd{};
-        if (mk.enabled || (src && l == 0) || zt.flags) bd = Bands{NR, a.h};
+        if (mk.enabled || (src && l == 0) || zt.flags || gin.flags) bd = Bands{NR, a.h};
         const int nbx = bd.nr ? np * bd.nr : (int)((lines + TS - 1) / TS);
         const bool rowz = zt.flags && (a.h % YCH) != 0;  // fused anticausal-y + decimation: a chunk of rows may straddle bands
         if (wavefront) {
@@ -469,7 +507,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
                 } else if (rcmp)
                     k_vv_x_fwd<PX, false, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, ZeroTiles{}, p->ckpt, bd);
                 else
-                    k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, ZeroTiles{}, nullptr, bd);
+                    k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd);
             }
             Wavefront wf{};
             wf.yg = p->wf_yg;
@@ -516,9 +554,9 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             const int fill_l0 = wf.mask_l0 == 2;  // flagged tiles of the mask planes repeat the plane's row 0 (k_vv_xbyf)
             if ((a.w & 1) == 0 && !p->no_fuse) {
                 if (rowz)
-                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
+                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout);
                 else
-                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
+                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout);
                 decimated = true;
             } else if (odd_dec) {  // odd width: three-tap x decimation, workgroups overlap by two columns
                 const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
@@ -536,7 +574,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             const bool src0 = src && l == 0;
             const bool xby = do_x && do_y && lone_fused_level(p, n, l);
             const double* ystate = p->state;  // where the causal y sweep leaves its state for the anticausal one
-            if (do_x && mover && !zt.flags && (nbx <= 340 || (src0 && nbx <= 1024))) {
+            if (do_x && mover && !zt.flags && !gin.flags && (nbx <= 340 || (src0 && nbx <= 1024))) {
                 {
                     StageTimer t(p, s, src0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD, l);
                     if (src0)
@@ -557,7 +595,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
                     if (src && l == 0)
                         k_vv_x_fwd<PX, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
                     else
-                        k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, ZeroTiles{}, nullptr, bd);
+                        k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd);
                 }
                 if (!xby) {
                     StageTimer t(p, s, STITCH_K_VV_X_BWD, l);
@@ -736,6 +774,7 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
         const Level& a = p->lv[l];
         const Level& nx = p->lv[l + 1];
         StageTimer tm(p, s, l == 0 ? STITCH_K_COLLAPSE_L0 : STITCH_K_COLLAPSE, l);
+        const ZeroTiles gz = g_flags_call(p, n, l), gzn = g_flags_call(p, n, l + 1);  // G column flags of this level and of the one it expands
         // four columns per work-item on the column range whose taps follow the regular pattern (Level::c4_xa, c4_xb), one
         // column per work-item on the rest, in ONE launch (k_collapse4); levels without such a range run k_collapse
         int xa = 0, xb = 0;
@@ -755,6 +794,7 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
             CollapseArgs<OUT, true> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, outs,
                                       a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, src ? 1 : 0, crows_of(p, 0, n), xa, xb, u8_words,
                                       std::max(0, p->tune.c4_lock), p->tune.c4_swz < 0 ? 1 : p->tune.c4_swz};
+            A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
             const int strips = (a.h + A.crows - 1) / A.crows;
             const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n);
             const bool gen = a.c4_gen && p->collapse4;
@@ -773,6 +813,8 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
             eo.p[0] = a.e;
             CollapseArgs<float, false> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, eo,
                                          a.pitch, a.ps, nullptr, NoPairArgs{}, 0, crows_of(p, l, n), xa, xb, 1, std::max(0, p->tune.c4_lock), p->tune.c4_swz < 0 ? 1 : p->tune.c4_swz};
+            A.gz = gz.flags, A.gnc = gz.NC, A.zo = (unsigned)(7 * (size_t)p->cap * a.ps);
+            A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
             const int strips = (a.h + A.crows - 1) / A.crows;
             const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n);
             if (xb > xa && a.c4_gen && p->collapse4)
@@ -1773,6 +1815,8 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     const size_t wfc_off = wf_alloc ? take(sizeof(unsigned) * (WF_CTRL_WORDS + WF_STICKY_WORDS)) : 0;
     const size_t zi_off = take((size_t)B * ((v0.h + TS - 1) / TS) * ((v0.w + TS - 1) / TS));
     const size_t zt_off = wf_levels ? take((size_t)7 * B * ((v0.h + TS - 1) / TS) * ((v0.w + TS - 1) / TS)) : 0;
+    size_t gz_off[2] = {0, 0};  // G column flags of levels 1 and 2
+    for (int i = 0; i < 2; ++i) gz_off[i] = wf_levels && i + 1 < L ? take((size_t)7 * B * ((lw[i + 1] + TS - 1) / TS)) : 0;
     int recompute = 0;  // opt-in: level 0 re-run from the frames measured 3 % slower, the plane levels within noise
     if (tn.recompute >= 0) recompute = wf_levels > 0 ? std::min(2, tn.recompute) : 0;
     const size_t ck_off = recompute ? take(sizeof(double) * 3 * NC0 * 7 * B * (size_t)(v0.h + 64)) : 0;
@@ -1827,6 +1871,7 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     if (wf_levels) {
         p->zt = reinterpret_cast<uint8_t*>(base + zt_off);
         p->zi = reinterpret_cast<uint8_t*>(base + zi_off);
+        for (int i = 0; i < 2; ++i) p->gz[i] = i + 1 < L ? reinterpret_cast<uint8_t*>(base + gz_off[i]) : nullptr;
         p->recompute = recompute;
         if (recompute) p->ckpt = reinterpret_cast<double*>(base + ck_off);
         if (tn.xbyf_wgs >= 0) p->wf_max_wgs = std::max(1, tn.xbyf_wgs);
@@ -2069,6 +2114,22 @@ int stitch_plan_handoff_counts(stitch_plan* p, uint64_t out[3]) {
     out[0] = out[1] = out[2] = 0;
     // the 64-bit words behind the sticky count (Wavefront::sticky): like it, no launch sequence clears them
     if (p->wf_ctrl) HIPCHK(hipMemcpy(out, p->wf_ctrl + WF_CTRL_WORDS + 2, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return STITCH_OK;
+}
+
+int stitch_plan_g_flag_counts(stitch_plan* p, uint64_t out[2]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    for (int i = 0; i < 2; ++i) {
+        out[i] = 0;
+        if (!p->gz_last[i] || !p->gz[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
+        std::vector<uint8_t> h((size_t)7 * p->last_n * ((p->lv[i + 1].w + TS - 1) / TS));
+        HIPCHK(hipMemcpy(h.data(), p->gz[i], h.size(), hipMemcpyDeviceToHost));
+        for (uint8_t f : h) out[i] += f != 0;
+    }
     return STITCH_OK;
 }
 
