@@ -128,7 +128,11 @@ struct ZeroTiles {
 // G column flags: the same idea for the pyramid planes G_1 and G_2 of a batch, one byte per (plane, 64-column tile column), written
 // by the decimating sweep that produces the level (k_vv_y_bwd_dec) on every call.  A set byte means: every sample of the tile column,
 // in all rows, is +0.0f by bit pattern, BOTH neighbouring tile columns are +0.0f throughout as well (the plane's edge counts as
-// one), and the column was NOT stored -- the memory holds whatever an earlier call left.  Carried as a ZeroTiles with one "band":
+// one), and the column was NOT stored -- the memory holds whatever an earlier call left.  One exception: the producer's workgroup of
+// tile column t reads the tile columns 2t and 2t + 1 of the level above, and where 2t + 1 lies past that level's last tile column (an
+// odd count of them) it neither takes its all-zero path nor passes for a zero neighbour: t counts as zero, for itself and as a neighbour,
+// only if 2t + 1 < ceil(w_{l-1} / 64).  Below such a level the last two tile columns are therefore never flagged, whatever they hold:
+// they are stored and read like data (tests/g_flags_ref.py states the rule on the host).  Carried as a ZeroTiles with one "band":
 // index(plane, 0, tile) = plane * NC + tile.  Readers (k_vv_x_fwd, the collapse kernels) take zeros instead of loading; a 16-byte
 // load of the collapse that straddles two tile columns is zero when either column is flagged: a flagged column's neighbours are zero,
 // and an unflagged DATA column never has a flagged neighbour.

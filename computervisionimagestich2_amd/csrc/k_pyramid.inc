@@ -242,8 +242,12 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
     unsigned gzb = 0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
+#if !(STITCH_G_IGNORE_COARSER & 2)  // (the two macros: see collapse_cols4)
         if (g_span_flag(A.gzn, A.gncn, pr * 7 + q, ix, ix2)) gzb |= 1u << q;
+#endif
+#if !(STITCH_G_IGNORE_OWN & 2)
         if (!DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + q, x, x)) gzb |= 0x100u << q;
+#endif
     }
     const size_t zn = (size_t)A.zon - (size_t)pr * 7 * sps, zg = (size_t)A.zo - (size_t)pr * 7 * ps;  // the zeros, from gn / g
     // x pass of one source row for the nine planes that are expanded: a0..a2, b0..b2 of G_{l+1}, then E_{l+1}
@@ -510,12 +514,19 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
     // G column flags, looked up once per work-item: its four columns lie in one tile column of this level, their taps s0 .. s0+3 in
     // one or two of level l+1 (g_cols).  A flagged plane is read from the zeros behind the level's last plane instead, every row from
     // the same 16 bytes; the loads themselves stay unconditional.
-#ifdef STITCH_G_IGNORE_COARSER  // (defined only to prove that the stale-data test sees a collapse that ignores the coarser level's flags)
+    // (STITCH_G_IGNORE_COARSER / STITCH_G_IGNORE_OWN: defined only in hand-check libraries, to prove that the stale-data tests see a
+    // collapse that ignores the coarser level's flags / the level's own.  A mask of the code that ignores them: 1 (what -DNAME alone
+    // gives) collapse_cols4, 2 collapse_cols1, 4 k_collapse_px, 7 all three; see HISTORY.md)
+#if STITCH_G_IGNORE_COARSER & 1
     const bool za = false, zb = false;
 #else
     const bool za = g_span_flag(A.gzn, A.gncn, pr * 7 + c, s0, s0 + 3), zb = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, s0, s0 + 3);
 #endif
+#if STITCH_G_IGNORE_OWN & 1
+    const bool zga = false, zgb = false;
+#else
     const bool zga = !DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + c, x0, x0), zgb = !DENSE && g_span_flag(A.gz, A.gnc, pr * 7 + 3 + c, x0, x0);
+#endif
     const unsigned zsa = (unsigned)((size_t)A.zon - ((size_t)pr * 7 + c) * sps), zsb = (unsigned)((size_t)A.zon - ((size_t)pr * 7 + 3 + c) * sps);
     const size_t zg = (size_t)A.zo - (size_t)pr * 7 * ps;
     double axs[4];
@@ -761,8 +772,16 @@ __global__ __launch_bounds__(256) void k_collapse_px(CollapseArgs<float, false> 
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         // G column flags: a flagged sample is +0 and is not loaded (an interpolation between zeros is +0: the weights are in [0, 1])
+#if STITCH_G_IGNORE_COARSER & 4  // (the two macros: see collapse_cols4)
+        const bool za = false, zb = false;
+#else
         const bool za = g_span_flag(A.gzn, A.gncn, pr * 7 + c, ix, ix2), zb = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, ix, ix2);
+#endif
+#if STITCH_G_IGNORE_OWN & 4
+        const bool zga = false, zgb = false;
+#else
         const bool zga = g_span_flag(A.gz, A.gnc, pr * 7 + c, x, x), zgb = g_span_flag(A.gz, A.gnc, pr * 7 + 3 + c, x, x);
+#endif
         const float ea = za ? 0.f : expand_at(gn + c * A.sps, ep), eb = zb ? 0.f : expand_at(gn + (3 + c) * A.sps, ep), ee = expand_at(en + c * A.sps, ep);
         const float la = (zga ? 0.f : g[i + c * A.ps]) - ea;
         const float lb = (zgb ? 0.f : g[i + (3 + c) * A.ps]) - eb;

@@ -816,7 +816,9 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
         // G column flags of the level being produced (even, whole-width launches only: a workgroup's 64 output columns are then ONE
         // tile column, blockIdx.x): meanwhile the consumer wavefront asks the same question of the two neighbouring workgroups -- their
         // input tiles flagged in every band, their y state and Triggs value +0 -- since the zeros are left unstored only where both
-        // neighbours are zero as well (see g_cols; the plane's edge counts as a zero neighbour, a fill plane never qualifies).
+        // neighbours are zero as well (see g_cols; the plane's edge counts as a zero neighbour, a fill plane never qualifies, and neither
+        // does a workgroup whose second input tile lies past the level's last one: not here, tN + 1 < zt.NC, and not for itself, since
+        // zm is 0 on those dead lanes).
         const bool gz_on = !ODD && !XCH && gz.flags != nullptr;  // workgroup-uniform
         __shared__ int s_nbz;
         if (gz_on && wave == 1) {

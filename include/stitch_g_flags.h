@@ -12,7 +12,9 @@ extern "C" {
 /* Tile columns (64 columns, all rows of one plane) of the pyramid levels 1 (out[0]) and 2 (out[1]) that the plan's LAST call
  * recorded as all +0 instead of storing them, summed over the call's pairs and planes (waits for that call).  0 for a level
  * whose flags the call did not use: an odd width of the level above, a lone pair's kernels, the band path, a library built
- * with STITCH_NO_G_FLAGS. */
+ * with STITCH_NO_G_FLAGS.  A tile column is recorded only if both neighbouring tile columns are all +0 as well (the plane's edge
+ * counts as one), and tile column t of level l only if 2t + 1 < ceil(w_{l-1} / 64): where the level above has an odd count of
+ * tile columns, the last two tile columns of level l are never recorded, whatever they hold. */
 int stitch_plan_g_flag_counts(stitch_plan *plan, uint64_t out[2]);
 #ifdef __cplusplus
 }

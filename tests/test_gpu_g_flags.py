@@ -5,54 +5,9 @@ count the rule gives on the oracle's own planes."""
 import numpy as np
 import pytest
 
+from g_flags_ref import BATCHES, FORMS, OPTS, cases, flagged_columns
+
 pytestmark = pytest.mark.gpu
-
-TS = 64
-# the pyramid's depth from the SHORTER side: under the root rule canvases this flat have no valid pyramid, and the oracle refuses them
-OPTS = dict(sigma=2.0, blur_kind=0, level_rule=1, seam_rule=0)
-WARP = [1.0, 0.002, 1e-6, 0.0, -0.001, 1.0, 5e-7, 1.5]
-
-
-def shift(x0, P=None):
-    """Canvas -> frame map of a frame whose left edge lies at canvas column x0 (P: a slightly projective map instead of the shift)."""
-    P = list(P) if P else [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0]
-    P[3] = -float(x0)
-    return P
-
-
-def cases(cw):
-    """name -> (frame width, map, mosaic width, mosaic ox, seam branch).  A narrow image at one edge of the canvas: its three planes
-    are +0 over the rest of every level -- further in than the blur's tails reach -- while the other image covers nearly everything."""
-    return {
-        "frame_right": (64, shift(cw - 64, WARP), cw - 34, 0, 1),
-        "frame_left": (64, shift(0), cw - 40, -40, 0),
-        "mosaic_left": (cw - 40, shift(40), 60, 0, 1),
-        "mosaic_right": (cw - 40, shift(0), 60, -(cw - 60), 0),
-    }
-
-
-# the second batch has every zero region where the first had data: a tile column stored by call 1 is flagged -- and stale -- in call 2
-BATCHES = [("frame_right", "mosaic_left"), ("frame_left", "mosaic_right")]
-# the two ways level 2 reaches the sweep that reads the flags: as a third fused level (with flags of the blur scratch), and unfused
-# behind two fused levels as in a large batch (a batch this small would otherwise take the three-wavefront x sweep, which has no flags)
-FORMS = {"fused3": {"STITCH_WAVEFRONT": "3"}, "fused2": {"STITCH_WAVEFRONT": "2", "STITCH_MOVER": "0"}}
-
-
-def flagged_columns(oracle, a, b, levels=2):
-    """[count at level 1, count at level 2] under the rule, from the oracle's planes: a 64-column tile column of one of the six image
-    planes counts when it is +0 by bit pattern in every row and so are both neighbouring tile columns (the plane's edge counts as
-    a zero neighbour).  A level produced from an odd width has no flags."""
-    g = np.concatenate([a, b]).astype(np.float32)
-    _, lw, lh = oracle.pyramid_levels(g.shape[2], g.shape[1], OPTS["level_rule"])
-    counts = []
-    for lv in range(1, levels + 1):
-        even = (g.shape[2] & 1) == 0
-        g = oracle.decimate(oracle.blur(g), lw[lv], lh[lv])
-        nc = (g.shape[2] + TS - 1) // TS
-        zero = np.array([[not g[q, :, t * TS:(t + 1) * TS].view(np.uint32).any() for t in range(nc)] for q in range(6)])
-        pad = np.pad(zero, ((0, 0), (1, 1)), constant_values=True)
-        counts.append(int((pad[:, :-2] & pad[:, 1:-1] & pad[:, 2:]).sum()) if even else 0)
-    return counts
 
 
 @pytest.fixture(scope="module")
