@@ -202,6 +202,8 @@ def lib():
         L.stitch_plan_handoff_counts.restype, L.stitch_plan_handoff_counts.argtypes = i32, [vp, vp]  # include/stitch_handoff.h
         if hasattr(L, "stitch_plan_g_flag_counts"):  # include/stitch_g_flags.h (an A/B build of an earlier tree, STITCH_LIB, lacks it)
             L.stitch_plan_g_flag_counts.restype, L.stitch_plan_g_flag_counts.argtypes = i32, [vp, vp]
+        if hasattr(L, "stitch_plan_mask_row_counts"):  # include/stitch_mask_rows.h (likewise)
+            L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         _lib = L
     return _lib
 
@@ -1231,6 +1233,13 @@ class Plan(_Handle):
         them (stitch_plan_g_flag_counts)."""
         out = (C.c_uint64 * 2)()
         _chk(lib().stitch_plan_g_flag_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def mask_row_counts(self):
+        """-> (level 1, level 2): (tile column, band) entries of the mask plane that the plan's last call recorded as repeats of the
+        plane's row 0 instead of storing them (stitch_plan_mask_row_counts)."""
+        out = (C.c_uint64 * 2)()
+        _chk(lib().stitch_plan_mask_row_counts(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_handoff_spin_limit(self, polls):

@@ -141,6 +141,21 @@ __device__ __forceinline__ bool g_col_flag(const uint8_t* __restrict__ flags, in
     return flags[(size_t)plane * nc + min(col >> 6, nc - 1)] != 0;
 }
 
+// Row-repeat flags of the MASK plane (slot 6 of a pair) of G_1 and G_2: one byte per (pair, 64-column tile column, 64-row band), written
+// by the same producer on every call.  The blend's mask is a vertical step, and below a level of even height and width its blurred and
+// decimated rows still repeat, bit for bit, down to the few rows at the bottom where the anticausal y sweep leaves its Triggs boundary.
+// A set byte of band b >= 1 means: every existing row of that tile equals row 0 of the plane in its 64 columns, by bit pattern, and the
+// tile was NOT stored -- the memory holds whatever an earlier call left.  Band 0 is always stored and never flagged.  No neighbour rule:
+// the mask plane is read only at its own level, by the x sweep in whole tiles and by the collapse in aligned 16-byte loads.  A column of
+// zeros is the case where row 0 is +0.  Carried as a ZeroTiles over PAIRS: index(pair, band, tile).  Readers take row 0 instead:
+// k_vv_x_fwd (and skips a band whose tiles are all flagged), k_vv_xbyf (such a band is a constant band, as below the first band of the
+// implicit level-0 mask), the collapse kernels (address select).  mask_rows_call (stitch_hip.hip) decides.
+__host__ __device__ inline ZeroTiles mask_rows(uint8_t* flags, int w, int h) { return ZeroTiles{flags, h, (h + 63) / 64, (w + 63) / 64}; }
+// the mask sample at (x, y) of pair pr is taken from row 0
+__device__ __forceinline__ bool mask_row_flag(const uint8_t* __restrict__ flags, int nc, int nr, int pr, int x, int y) {
+    return flags != nullptr && flags[((size_t)pr * nc + min(x >> 6, nc - 1)) * nr + (y >> 6)] != 0;
+}
+
 constexpr int SI_ROWS = 8;  // rows per workgroup of k_src_index (a one-row workgroup is launch-bound: 393k workgroups per batch)
 template <typename PX>
 __global__ __launch_bounds__(256) void k_src_index(PairArgs<PX> pa, float* __restrict__ g0_all, int cw, int ch, int pitch, size_t ps,

@@ -37,6 +37,7 @@ struct Wavefront {
     unsigned epoch;
     unsigned spin_limit;      // polls before a wait gives up (STITCH_XBYF_SPIN_LIMIT; tests force the bail-out path with 0)
     ZeroTiles zt;             // zero-tile flags of T at this level (see ZeroTiles)
+    ZeroTiles mr;             // a level >= 1: row-repeat flags of the mask plane of G at this level (mask_rows), or none
     // read by the BANDED instance only (stitch_band: a row band of a pair split over several GPUs)
     int ph, y0;               // rows per plane in memory and the first swept row of a plane: the band sweeps rows y0 .. y0+h-1
     const double* resume;     // a band below the first: the y state the band above left, [3][planes][pitch] (as k_vv_y_fwd)
@@ -189,8 +190,21 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
         float* base = data + ((size_t)p * ph + y0 + r0) * pitch;
         // level-0 implicit mask plane below its first band: every row equals the x-blurred row that band 0 passes down
         // with the y state, so there is nothing to fetch and no x sweep to run (k_vv_x_fwd skipped these rows too)
-        const bool const_rows = wf.mask_l0 && (p % 7 == 6) && R > 0;
-        const bool pass_row = wf.mask_l0 && (p % 7 == 6);
+        // A level >= 1 with row-repeat flags of its mask plane (mask_rows): the plane passes its x-blurred row 0 down in the same way,
+        // and a band below the first whose tiles are ALL flagged repeats row 0 of G_l in every row -- the same constant band, with nothing
+        // stored behind it (k_vv_x_fwd returned at once).  Any other band of the plane is fetched and swept like a plane of samples; it
+        // receives and forwards the fifth granule.
+        const bool rows_l = MODE == 0 && !BANDED && wf.mr.flags != nullptr;  // wave-uniform
+        const bool pass_row = (wf.mask_l0 || rows_l) && (p % 7 == 6);
+        bool const_rows = wf.mask_l0 && (p % 7 == 6) && R > 0;
+#if !(STITCH_MASK_ROWS_IGNORE & 2)  // (hand-check libraries only: a sweep that fetches the unstored bands)
+        if (rows_l && pass_row && R > 0) {
+            bool all = true;
+            for (int t0 = 0; t0 < wf.NC; t0 += WAVE) all = all && __all(t0 + lane >= wf.NC || wf.mr.flags[wf.mr.index(p / 7, R, min(t0 + lane, wf.NC - 1))] != 0);
+            const_rows = all;
+        }
+#endif
+        const bool fill_plane = !BANDED && pass_row && (wf.mask_l0 == 2 || rows_l);  // flags of T mean "repeats row 0" on this plane
         stamp(0);  // claim
 
         // x state of this band's rows: where the causal x sweep left it, through the Triggs boundary (CImg.h:34911-34922)
@@ -276,7 +290,7 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
         // 0 of the plane, which band 0 always stores) although the double state may cycle in its last bit -- so the equality is
         // tested, tile by tile, on the outputs themselves.  The flag of such a tile then means "every sample equals row 0 of its
         // column"; +0 everywhere is the case rowv = +0.  k_vv_y_bwd_dec substitutes the row-0 value.
-        const bool fill_rows = !BANDED && const_rows && wf.mask_l0 == 2;
+        const bool fill_rows = fill_plane && const_rows;
         unsigned recorded = 0;
         if (!const_rows) {
             next_zero = fetch_tile(wf.NC - 1);
@@ -474,8 +488,9 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
             bool out_zero = false;
             if (wf.zt.flags) {  // the y sweep ran over every column of the tile; columns >= w hold whatever the fetch left: not counted
                 out_zero = __ballot(lane < ncols && ynz != 0) == 0;
-                // band 0 of a plane whose flags mean "repeats row 0" is always stored: it holds that row
-                if (!BANDED && pass_row && R == 0 && wf.mask_l0 == 2) out_zero = false;
+                // a band of samples of a plane whose flags mean "repeats row 0" is always stored: band 0 holds that row, and an all-(+0)
+                // tile of a swept band of a level >= 1 would be read back as row 0
+                if (fill_plane && !const_rows) out_zero = false;
                 if (lane == 0) wf.zt.flags[wf.zt.index(p, R, C)] = out_zero ? 1 : 0;
                 if (fill_rows && out_zero) ++recorded;
             }

@@ -212,14 +212,29 @@ struct CollapseArgs {
     int gnc, gncn;
     unsigned zo, zon;
 };
+// Row-repeat flags of the level's mask plane (mask_rows), [pairs][nc tile columns][nr bands]: an argument of the MR instances of the
+// collapse kernels only (levels 1 and 2 of a call with the flags on), so that every other instance is compiled as it was.  The mask
+// sample of a flagged tile is loaded from row 0 of the same columns: an address select, the load stays unconditional.  The flag is
+// looked up where a strip starts and where it enters a new 64-row band, and kept from row to row in between.
+struct MaskRowsArg {
+    const uint8_t* flags;
+    int nc, nr;
+};
+__device__ __forceinline__ bool collapse_mask_row(const MaskRowsArg& mr, int pr, int x, int y) {
+#if STITCH_MASK_ROWS_IGNORE & 4  // (hand-check libraries only: a collapse that reads the unstored tiles)
+    return false;
+#else
+    return mask_row_flag(mr.flags, mr.nc, mr.nr, pr, x, y);
+#endif
+}
 // the samples at columns x and x2 (x <= x2 <= x + 3) of a plane are both taken as zeros: either tile column is flagged
 __device__ __forceinline__ bool g_span_flag(const uint8_t* __restrict__ flags, int nc, int plane, int x, int x2) {
     return flags != nullptr && (g_col_flag(flags, nc, plane, x) || g_col_flag(flags, nc, plane, x2));
 }
 
 // one column x, rows [y0, y1) of pair pr
-template <typename OUT, bool DENSE>
-__device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A, int x, int y0, int y1, int pr) {
+template <typename OUT, bool DENSE, bool MR = false>
+__device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A, int x, int y0, int y1, int pr, MaskRowsArg mr = MaskRowsArg{}) {
     const int w = A.w, pitch = A.pitch, sw = A.sw, sh = A.sh, spitch = A.spitch, opitch = A.opitch;
     const size_t ps = A.ps, sps = A.sps, ops = A.ops;
     const ExpandTab& tb = A.tb;
@@ -265,6 +280,7 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
     float X1[9], X2[9];
     int cur1 = -1, cur2 = -1;
     const float m_step = seam_l0 ? mask_step(seam_l0[pr], x) : 0.f;  // level 0: the mask is the step itself
+    bool mrow = false;  // MR: row-repeat flag of the mask tile this row lies in
     for (int y = y0; y < y1; ++y) {
         const int iy = tb.iy[y], iy2 = iy < sh - 1 ? iy + 1 : iy;
         const double ay = tb.ay[y];
@@ -285,7 +301,9 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
             cur2 = iy2;
         }
         const size_t o = (size_t)y * pitch + x;
-        const float m = seam_l0 ? m_step : g[o + 6 * ps];
+        if constexpr (MR)
+            if (y == y0 || (y & 63) == 0) mrow = collapse_mask_row(mr, pr, x, y);
+        const float m = seam_l0 ? m_step : g[(MR && mrow ? (size_t)x : o) + 6 * ps];
         float ga[3], gb[3];
         if (!DENSE && gzb >= 0x100u) {  // some plane of this level is flagged at x: its samples come from the zeros
 #pragma unroll
@@ -318,11 +336,11 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
 }
 
 // one column per work-item over the whole level (xa == xb) -- levels too small or too irregular for k_collapse4
-template <typename OUT, bool DENSE>
-__global__ __launch_bounds__(256) void k_collapse(CollapseArgs<OUT, DENSE> A) {
+template <typename OUT, bool DENSE, bool MR = false>
+__global__ __launch_bounds__(256) void k_collapse(CollapseArgs<OUT, DENSE> A, MaskRowsArg mr = MaskRowsArg{}) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y0 = blockIdx.y * A.crows, pr = blockIdx.z;
     if (x >= (DENSE ? A.w : A.pitch)) return;
-    collapse_cols1<OUT, DENSE>(A, x, y0, min(y0 + A.crows, A.h), pr);
+    collapse_cols1<OUT, DENSE, MR>(A, x, y0, min(y0 + A.crows, A.h), pr, mr);
 }
 
 // ---- the same collapse, four columns and ONE channel per work-item ------------------------------------------------
@@ -484,8 +502,8 @@ struct SrcRow4Of<OUT, true, AD> {
 // sample over the row, so the fixed pattern holds for well under half of the columns (1 792 of 4 421), and with it every column
 // group but the last few of a row qualifies.  About 30 more selects per source row; even widths keep the fixed pattern.
 typedef __attribute__((address_space(3))) f4 lds_f4;
-template <typename OUT, bool DENSE, bool AD, bool GEN>
-__device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A, int c, int x0, int y0, int y1, int pr, float* sh) {
+template <typename OUT, bool DENSE, bool AD, bool GEN, bool MR = false>
+__device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A, int c, int x0, int y0, int y1, int pr, float* sh, MaskRowsArg mr = MaskRowsArg{}) {
     const int pitch = A.pitch, sh_ = A.sh, spitch = A.spitch, opitch = A.opitch;
     const size_t ps = A.ps, sps = A.sps, ops = A.ops;
     const ExpandTab& tb = A.tb;
@@ -575,8 +593,12 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
     }
     const typename SrcRow4Of<OUT, DENSE, AD>::type src(A.pa, pr, c, x0, A.w);
     // the level's own samples of one row, as raw bits: two planes (or the gathers of a source-fused level 0) + the mask
+    bool mrow = false;  // MR: row-repeat flag of the mask tile a row lies in (the four columns lie in one tile column)
     auto row_issue = [&](int y, float ga[4], float gb[4], f4& vm) {
         const unsigned o = (unsigned)y * (unsigned)pitch + (unsigned)x0;
+        if constexpr (MR)
+            if (y == y0 || (y & 63) == 0) mrow = collapse_mask_row(mr, pr, x0, y);
+        const unsigned om = MR && mrow ? (unsigned)x0 : o;
         if (use_src)
 #if STITCH_C4_ABLATE == 2  // the index plane is not read (every lane gathers element 0 .. 3)
             src.issue(u4{0u, 4u, 8u, 12u}, y, ga, gb);
@@ -596,14 +618,14 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
             for (int j = 0; j < 4; ++j) ga[j] = va[j], gb[j] = vb[j];
         }
         if (share) {
-            if (c == 0) vm = *reinterpret_cast<const f4*>(g + o + 6 * ps);
+            if (c == 0) vm = *reinterpret_cast<const f4*>(g + om + 6 * ps);
         } else
 #if STITCH_C4_ABLATE == 11  // only channel 0 reads the mask plane
         if (!seam_l0) vm = c == 0 ? *reinterpret_cast<const f4*>(g + o + 6 * ps) : f4{0.5f, 0.5f, 0.5f, 0.5f};
 #elif STITCH_C4_ABLATE == 12  // nobody reads the mask plane
         if (!seam_l0) vm = f4{0.5f, 0.5f, 0.5f, (float)y};
 #else
-        if (!seam_l0) vm = *reinterpret_cast<const f4*>(g + o + 6 * ps);
+        if (!seam_l0) vm = *reinterpret_cast<const f4*>(g + om + 6 * ps);
 #endif
     };
     float ga[4], gb[4];
@@ -701,8 +723,8 @@ constexpr int C4_SUB = 8, C4_THREADS = 3 * WAVE;
 // four-column blocks per strip in the launch: with a block order, strips of eight blocks and more are padded to a multiple of 8
 // (the extra workgroups return at once) so that every block of a strip is renumbered; narrower levels are left as they are
 __host__ __device__ inline int c4_padded_blocks(int nb4, int swizzle) { return swizzle && nb4 >= 8 ? (nb4 + 7) & ~7 : nb4; }
-template <typename OUT, bool DENSE, bool AD = false, bool GEN = false>
-__global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(CollapseArgs<OUT, DENSE> A, int nb4, int ncb) {
+template <typename OUT, bool DENSE, bool AD = false, bool GEN = false, bool MR = false>
+__global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(CollapseArgs<OUT, DENSE> A, int nb4, int ncb, MaskRowsArg mr = MaskRowsArg{}) {
     const int pr = blockIdx.z;
     __shared__ __attribute__((aligned(16))) float c4_sh[2 * WAVE * 4];
     const int nb4p = c4_padded_blocks(nb4, A.swizzle);
@@ -735,7 +757,7 @@ __global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(Colla
         }
         const int y0 = strip * A.crows, y1 = min(y0 + A.crows, A.h);
         const int x0 = A.xa + (blk * WAVE + (threadIdx.x & 63)) * 4;
-        if (blk < nb4 && x0 < A.xb) collapse_cols4<OUT, DENSE, AD, GEN>(A, c, x0, y0, y1, pr, c4_sh);
+        if (blk < nb4 && x0 < A.xb) collapse_cols4<OUT, DENSE, AD, GEN, MR>(A, c, x0, y0, y1, pr, c4_sh, mr);
     } else {
         const int y0 = blockIdx.y * A.crows, y1 = min(y0 + A.crows, A.h);
         const int r = blockIdx.x - nb4p, cb = r % ncb, sub = r / ncb, rows = (A.crows + C4_SUB - 1) / C4_SUB;
@@ -745,7 +767,7 @@ __global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(Colla
 #if STITCH_C4_ABLATE == 9 || STITCH_C4_ABLATE == 10  // the one-column-per-work-item part does nothing
         if (A.h < 0)
 #endif
-        if (x < (DENSE ? A.w : A.pitch) && ya < yb) collapse_cols1<OUT, DENSE>(A, x, ya, yb, pr);
+        if (x < (DENSE ? A.w : A.pitch) && ya < yb) collapse_cols1<OUT, DENSE, MR>(A, x, ya, yb, pr, mr);
     }
 }
 
@@ -753,7 +775,8 @@ __global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(Colla
 // work of k_collapse (no re-use of x-interpolated source rows), but a work-item's chain is two rounds of loads instead of a
 // strip's worth of dependent table look-ups -- for the middle levels of a LONE pair (too small for k_collapse4, too large for
 // k_coarse), where a launch's time is that chain: 15 -> 7 us per level.  Same expand_at / blend_ref arithmetic.
-__global__ __launch_bounds__(256) void k_collapse_px(CollapseArgs<float, false> A) {
+template <bool MR = false>
+__global__ __launch_bounds__(256) void k_collapse_px(CollapseArgs<float, false> A, MaskRowsArg mr = MaskRowsArg{}) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, pr = blockIdx.z;
     if (x >= A.pitch) return;
     const float* g = A.g_all + (size_t)pr * 7 * A.ps;
@@ -768,7 +791,7 @@ __global__ __launch_bounds__(256) void k_collapse_px(CollapseArgs<float, false> 
     }
     const ExpandPos ep = expand_pos(A.tb, x, y, A.sw, A.sh, A.spitch);
     const int ix = A.tb.ix[x], ix2 = ix < A.sw - 1 ? ix + 1 : ix;  // the two x taps (expand_pos)
-    const float m = g[i + 6 * A.ps];
+    const float m = g[(MR && collapse_mask_row(mr, pr, x, y) ? (size_t)x : i) + 6 * A.ps];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         // G column flags: a flagged sample is +0 and is not loaded (an interpolation between zeros is +0: the weights are in [0, 1])

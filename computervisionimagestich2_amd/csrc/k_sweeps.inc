@@ -126,7 +126,7 @@ template <typename PX, bool SRC, bool CKPT = false>
 __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, float* __restrict__ out, int w, int pitch,
                                                   long lines, VVK k, double* __restrict__ state, MaskL0 mk,
                                                   typename CollapseSrc<PX, SRC>::type pa, ZeroTiles zt, ZeroTiles zi,
-                                                  double* __restrict__ ckpt, Bands bd) {
+                                                  double* __restrict__ ckpt, Bands bd, ZeroTiles mr = ZeroTiles{}) {
     __shared__ __attribute__((aligned(16))) float tile[TS * TP];
     const int lane = threadIdx.x;
     long blk = blockIdx.x;
@@ -150,6 +150,21 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
     float* ob = out + (size_t)line0 * pitch;
     const int ntiles = (w + TS - 1) / TS;
     const bool live = lane < nrows && line < lines;
+    // Row-repeat flags of this level's mask plane (mask_rows; per-plane bands): a flagged tile of a band below the first was not stored
+    // and its 64 rows are taken from row 0 of the plane -- an address select, the loads stay unconditional.  At a fused level (T flags:
+    // k_vv_xbyf knows the flags too) a band whose tiles are ALL flagged has nothing to do here, like the level-0 step below its first band.
+#if STITCH_MASK_ROWS_IGNORE & 1  // (hand-check libraries only: proves that the stale-data tests see a sweep that ignores the flags)
+    const bool mr_on = false;
+#else
+    const bool mr_on = !SRC && !CKPT && mr.flags != nullptr && plane % 7 == 6 && band_y0 > 0;  // wave-uniform
+#endif
+    const float* row0 = in + (size_t)plane * bd.h * pitch;
+    auto tile_row0 = [&](int t) -> bool { return mr_on && mr.flags[mr.index(plane / 7, band_y0 / TS, t)] != 0; };
+    if (mr_on && zt.flags) {
+        bool all = true;
+        for (int t0 = 0; t0 < ntiles; t0 += WAVE) all = all && __all(t0 + lane >= ntiles || mr.flags[mr.index(plane / 7, band_y0 / TS, min(t0 + lane, ntiles - 1))] != 0);
+        if (all) return;
+    }
     bool gen_mask = false;  // wave-uniform: this block's 64 lines are rows of a level-0 mask plane
     SeamDev sd;
     int src_q = 0, src_y0 = 0, src_pr = 0;  // wave-uniform: plane, first row and pair of this block (use_src)
@@ -199,6 +214,7 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
                 : gen_frame  ? (double)src_px<PX>(rs, true, reinterpret_cast<const unsigned*>(idx_rows)[(size_t)lane * pitch + (w - 1)])
                 : gen_mosaic ? (double)src_px<PX>(rs, false, mosaic_offset<PX>(mosaic_row<PX>(ms, src_y0 + lane), mosaic_col<PX>(ms, w - 1, w)))
                 : tile_outside(ntiles - 1) ? 0.0
+                : tile_row0(ntiles - 1)    ? (double)row0[w - 1]
                              : (double)in[(size_t)line * pitch + (w - 1)];
     double v1 = 0, v2 = 0, v3 = 0;
     f4 pre[16];
@@ -220,8 +236,10 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
             }                                                                  \
         } else if (tile_outside(T)) {                                          \
             _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) pre[i_] = f4{0.f, 0.f, 0.f, 0.f}; \
-        } else                                                                 \
-            tile_load(ib, pitch, (T) * TS, lane, pre);                         \
+        } else {                                                               \
+            const bool r0_ = tile_row0(T);                                     \
+            tile_load(r0_ ? row0 : ib, r0_ ? 0 : pitch, (T) * TS, lane, pre);  \
+        }                                                                      \
     } while (0)
     if constexpr (SRC) {
         if (gen_frame)
@@ -700,12 +718,15 @@ __global__ __launch_bounds__(64) void k_vv_y_bwd(float* __restrict__ data, int h
 // fill_l0 (a plan's fused level 0 with the implicit mask; k_vv_xbyf, Wavefront::mask_l0 == 2): on the planes y % 7 == 6 a flagged tile was
 // not all +0 but a repetition of the plane's row 0, which is always stored: the row a flagged lane re-reads IS that row, and the lane keeps
 // what it read instead of taking zeros (no register holds the fill values: the ROWZ instances sit at 127 of 128 VGPRs for four wavefronts).
+// The same holds for the mask plane of a fused level >= 1 that has row-repeat flags (mask_rows, k_compose.inc).
+// mr (even widths and heights, whole-width launches with T flags): row-repeat flags of the mask plane of the level being PRODUCED, which
+// the consumer wavefront of the mask planes' workgroups writes while it stores that plane lazily (see the consumer loop).
 template <bool ROWZ = false, int NST = YST, bool ZT = true, bool ODD = false, bool XCH = false>
 __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ data, int w, int h, int pitch, size_t ps,
                                                       VVK k, const double* __restrict__ state, float* __restrict__ dst,
                                                       int w2, int h2, int dpitch, size_t dps, ZeroTiles zt,
                                                       const double* __restrict__ resume, double* __restrict__ state_out, int wh, int wh2,
-                                                      int x_base = 0, int fill_l0 = 0, ZeroTiles gz = ZeroTiles{}) {
+                                                      int x_base = 0, int fill_l0 = 0, ZeroTiles gz = ZeroTiles{}, ZeroTiles mr = ZeroTiles{}) {
     static_assert(!(XCH && ODD), "column chunks: even widths");
     // wh, wh2: the heights the decimation's overlap weights are taken from (CImg.h:29557-29575 weights by the LEVEL's
     // heights): h, h2 for a whole level; for a row band of a split pair the level's, not the band's (the quotient is the same
@@ -928,67 +949,107 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
             }
         }
     } else {
-        for (int j0 = 0; j0 <= nchunks; j0 += NST) {
+        // Row-repeat flags of the mask plane of the level being produced (mask_rows; even widths and heights, whole-width launches: a
+        // workgroup's 64 output columns are ONE tile column).  The sweep walks bottom-up and cannot know row 0 in advance, so the consumer
+        // stores lazily: it keeps the value of the current run of equal rows per lane and the run's top (first met) row; an output row
+        // that equals the run in every live lane is not stored; a row that differs first stores the rows the run skipped, then starts a
+        // new run.  Behind row 0 the last run is rows 0 .. run_top: band 0's rows are stored, a band the run covers whole is flagged,
+        // a band it covers in part is stored as far as the run goes, and every byte is written.  Rows that never repeat are each
+        // stored once, as without the flags.  Only the mask planes' workgroups take this form of the loop (workgroup-uniform).
+#ifdef STITCH_NO_MASK_ROWS
+        const bool mr_on = false;
+#else
+        const bool mr_on = ZT && !ODD && !XCH && mr.flags != nullptr && blockIdx.y % 7 == 6 && !h_odd;
+#endif
+        float runv = 0.f;
+        int run_top = -1;
+        auto consume = [&](auto MR) {
+            for (int j0 = 0; j0 <= nchunks; j0 += NST) {
 #pragma unroll
-            for (int st = 0; st < NST; ++st) {
-                const int j = j0 + st;
-                if (j >= 1 && j - 1 < nchunks) {
-                    // The rows of a chunk are independent until the y step, and a row is one dependent chain (LDS read, two
-                    // multiply-adds, an IEEE divide): all YCH chains are laid side by side, free of branches, so that they overlap --
-                    // row after row the consumer was the slower wavefront of the two (264 cycles per row against the producer's
-                    // 173).  Rows past the image (last chunk) are computed from whatever the ring holds and never stored.
-                    const int rc0 = (j - 1) * YCH;
-                    float E[YCH + 2];  // x-decimated rows: E[0], E[1] = the two rows before this chunk, E[2 + u] = row rc0 + u
-                    E[0] = Xp2;
-                    E[1] = Xp1;
+                for (int st = 0; st < NST; ++st) {
+                    const int j = j0 + st;
+                    if (j >= 1 && j - 1 < nchunks) {
+                        // The rows of a chunk are independent until the y step, and a row is one dependent chain (LDS read, two
+                        // multiply-adds, an IEEE divide): all YCH chains are laid side by side, free of branches, so that they overlap --
+                        // row after row the consumer was the slower wavefront of the two (264 cycles per row against the producer's
+                        // 173).  Rows past the image (last chunk) are computed from whatever the ring holds and never stored.
+                        const int rc0 = (j - 1) * YCH;
+                        float E[YCH + 2];  // x-decimated rows: E[0], E[1] = the two rows before this chunk, E[2 + u] = row rc0 + u
+                        E[0] = Xp2;
+                        E[1] = Xp1;
 #pragma unroll
-                    for (int u = 0; u < YCH; ++u) {
-                        const f2 v = *reinterpret_cast<const f2*>(&ring[(st + 1) & 1][u][2 * lane]);
-                        float X = 0.f;
-                        if constexpr (ODD) {
-                            const float v2 = ring[(st + 1) & 1][u][lane < WAVE - 1 ? 2 * lane + 2 : 2 * lane];  // the next lane's first column
-                            X += v.x * od0;
-                            X += v.y * fsx;
-                            X += v2 * od2;
+                        for (int u = 0; u < YCH; ++u) {
+                            const f2 v = *reinterpret_cast<const f2*>(&ring[(st + 1) & 1][u][2 * lane]);
+                            float X = 0.f;
+                            if constexpr (ODD) {
+                                const float v2 = ring[(st + 1) & 1][u][lane < WAVE - 1 ? 2 * lane + 2 : 2 * lane];  // the next lane's first column
+                                X += v.x * od0;
+                                X += v.y * fsx;
+                                X += v2 * od2;
+                            } else {
+                                X += v.x * fsx;
+                                X += v.y * fsx;
+                            }
+                            X /= fw;
+                            E[2 + u] = X;
+                            if (u == YCH / 2 - 1) __builtin_amdgcn_sched_barrier(0);  // two groups of four: eight divides side by side need 140 VGPRs
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        // row y = 2t completes output row t; y = h-1-rc0-u and rc0 is a multiple of YCH (even): for an even height the
+                        // odd u, for an odd height the even u
+                        if (h_odd) {
+#pragma unroll
+                            for (int u = 0; u < YCH; u += 2) {
+                                const int y = h - 1 - rc0 - u, t = y >> 1;
+                                float a2 = 0.f;
+                                a2 += E[2 + u] * (float)(unsigned)(h2 - t);
+                                a2 += E[1 + u] * fsy;
+                                a2 += E[u] * (float)(unsigned)(t + 1);
+                                a2 /= fh;
+                                if (y >= 0 && t < h2 && dst_live) st_out(t, a2);
+                            }
                         } else {
-                            X += v.x * fsx;
-                            X += v.y * fsx;
-                        }
-                        X /= fw;
-                        E[2 + u] = X;
-                        if (u == YCH / 2 - 1) __builtin_amdgcn_sched_barrier(0);  // two groups of four: eight divides side by side need 140 VGPRs
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    // row y = 2t completes output row t; y = h-1-rc0-u and rc0 is a multiple of YCH (even): for an even height the
-                    // odd u, for an odd height the even u
-                    if (h_odd) {
 #pragma unroll
-                        for (int u = 0; u < YCH; u += 2) {
-                            const int y = h - 1 - rc0 - u, t = y >> 1;
-                            float a2 = 0.f;
-                            a2 += E[2 + u] * (float)(unsigned)(h2 - t);
-                            a2 += E[1 + u] * fsy;
-                            a2 += E[u] * (float)(unsigned)(t + 1);
-                            a2 /= fh;
-                            if (y >= 0 && t < h2 && dst_live) st_out(t, a2);
+                            for (int u = 1; u < YCH; u += 2) {
+                                const int y = h - 1 - rc0 - u, t = y >> 1;
+                                float a2 = 0.f;
+                                a2 += E[2 + u] * fsy;
+                                a2 += E[1 + u] * fsy;
+                                a2 /= fh;
+                                if constexpr (decltype(MR)::value) {
+                                    if (y >= 0 && t < h2) {  // (workgroup-uniform)
+                                        if (run_top < 0 || !__all(!dst_live || __float_as_uint(a2) == __float_as_uint(runv))) {
+                                            if (dst_live)
+                                                for (int tt = t + 1; tt <= run_top; ++tt) st_out(tt, runv);  // the run that ends here
+                                            runv = a2;
+                                            run_top = t;
+                                        }
+                                    }
+                                } else if (y >= 0 && t < h2 && dst_live)
+                                    st_out(t, a2);
+                            }
                         }
-                    } else {
-#pragma unroll
-                        for (int u = 1; u < YCH; u += 2) {
-                            const int y = h - 1 - rc0 - u, t = y >> 1;
-                            float a2 = 0.f;
-                            a2 += E[2 + u] * fsy;
-                            a2 += E[1 + u] * fsy;
-                            a2 /= fh;
-                            if (y >= 0 && t < h2 && dst_live) st_out(t, a2);
-                        }
+                        Xp2 = E[YCH];
+                        Xp1 = E[YCH + 1];
                     }
-                    Xp2 = E[YCH];
-                    Xp1 = E[YCH + 1];
+                    __syncthreads();
                 }
-                __syncthreads();
             }
-        }
+        };
+        if (mr_on) {
+            consume(std::true_type{});
+            if (dst_live)
+                for (int tt = 0; tt <= min(run_top, TS - 1); ++tt) st_out(tt, runv);
+            for (int b = 1; b < mr.NR; ++b) {
+                const int lo = b * TS, hi = min(lo + TS, h2) - 1;
+                const bool whole = hi <= run_top;
+                if (!whole && dst_live)
+                    for (int tt = lo; tt <= run_top; ++tt) st_out(tt, runv);
+                if (lane == 0 && (int)blockIdx.x < mr.NC) mr.flags[mr.index(blockIdx.y / 7, b, blockIdx.x)] = whole ? 1 : 0;
+            }
+            if (lane == 0 && (int)blockIdx.x < mr.NC) mr.flags[mr.index(blockIdx.y / 7, 0, blockIdx.x)] = 0;
+        } else
+            consume(std::false_type{});
     }
     if (state_out && wave == 0 && col_live) y2_store(state_out, (size_t)gridDim.y * sp, ystate_index(blockIdx.y, sp, sx), s);
 }

@@ -21,6 +21,7 @@
 #include "stitch.h"
 #include "stitch_g_flags.h"
 #include "stitch_handoff.h"
+#include "stitch_mask_rows.h"
 #include "stitch_panorama.h"
 #include "stitch_rig.h"
 #include "stitch_exposure.h"
@@ -313,6 +314,8 @@ struct stitch_plan {
     bool zero_tiles = false;
     uint8_t* gz[2] = {nullptr, nullptr};  // G column flags of levels 1 and 2, [7*cap][tile columns] (g_cols; g_flags_call decides per call)
     bool gz_last[2] = {false, false};     // the last call used them (stitch_plan_g_flag_counts)
+    uint8_t* mr[2] = {nullptr, nullptr};  // row-repeat flags of the mask plane of levels 1 and 2, [cap][tile columns][bands] (mask_rows; mask_rows_call decides per call)
+    bool mr_last[2] = {false, false};     // the last call used them (stitch_plan_mask_row_counts)
     const float* zero_page = nullptr;  // 4 KB of zeros in the arena (k_vv_xby_m's loader reads a flagged tile from here)
     int wf_max_wgs = 2304;  // persistent workgroups of the fused sweep (STITCH_XBYF_WGS)
     unsigned wf_spin_limit = 1u << 23;  // polls before a hand-off wait gives up, about 20 s (STITCH_XBYF_SPIN_LIMIT); 2^20 (2-3 s) was reached once in a warm-up
@@ -432,6 +435,31 @@ ZeroTiles g_flags_call(const stitch_plan* p, int n, int l) {
 #endif
 }
 
+// Row-repeat flags of the mask plane of level l (1 or 2) in a call with n pairs, or none (see mask_rows, k_compose.inc): the ONE place that
+// decides.  On only where the G column flags of the level are on (the same producer launch, the same readers, none of k_vv_x_m, STITCH_RECOMPUTE,
+// the band path, the XCH / ODD / BANDED instances, the levels from coarse_from on), and
+//   producer        k_vv_y_bwd_dec below a level l-1 of even width AND even height (below an odd height the decimation's overlap weights
+//                   change from row to row and the rows do not repeat), on a plane whose T flags mean "repeats row 0": level 0 with the
+//                   implicit mask recorded in the flags (Wavefront::mask_l0 == 2), level 1 fused with these flags of its own;
+//   x sweep of l    k_vv_x_fwd<PX, false>: a flagged tile from row 0; at a fused level a band flagged throughout is skipped;
+//   fused sweep     k_vv_xbyf MODE 0 (Wavefront::mr): such a band is a constant band, its T tiles recorded as repeats of row 0;
+//   y sweep of l    k_vv_y_bwd_dec with fill_l0: a flagged lane re-reads row 0 of T and keeps it;
+//   collapse of l   k_collapse4 / k_collapse / k_collapse_px (their MR instances, MaskRowsArg): the mask sample from row 0.
+// An unfused level 2 (a large batch) only redirects: k_vv_x_bwd, k_vv_y_fwd1 and its k_vv_y_bwd_dec work on T, which is stored in full.
+// STITCH_NO_MASK_ROWS (compile time, A/B libraries): never.  STITCH_NO_ZERO_TILES=1 turns them off with the other flags.
+ZeroTiles mask_rows_call(const stitch_plan* p, int n, int l) {
+#ifdef STITCH_NO_MASK_ROWS
+    return ZeroTiles{};
+#else
+    if (l < 1 || l > 2 || !p->mr[l - 1] || !g_flags_call(p, n, l).flags) return ZeroTiles{};
+    const Level& a = p->lv[l - 1];
+    if ((a.w & 1) != 0 || (a.h & 1) != 0) return ZeroTiles{};
+    if (l == 1 && !p->mask_opt) return ZeroTiles{};
+    if (l == 2 && (!mask_rows_call(p, n, 1).flags || p->lv[1].h < 2)) return ZeroTiles{};
+    return mask_rows(p->mr[l - 1], p->lv[l].w, p->lv[l].h);
+#endif
+}
+
 // One pair in flight: the anticausal x and the causal y sweep of level l as ONE launch of five-wavefront bands (k_vv_xby_m) where the
 // separate launches are bound by their bytes -- from STITCH_XBYM_MPIX megapixels per plane (default 20: 6144 x 4096).  Below that a level's time is
 // its chain of rows and columns either way, and the fused form adds a hand-off per 64-row band.  STITCH_XBYM=0: never; =1: the first
@@ -451,6 +479,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
     if (p->wf_levels > 0 || any_lone_fused) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
     const int l_end = p->coarse_from > 0 ? p->coarse_from : p->L - 1;  // levels [0, l_end) are reduced level by level
     for (int i = 0; i < 2; ++i) p->gz_last[i] = g_flags_call(p, n, i + 1).flags != nullptr;
+    for (int i = 0; i < 2; ++i) p->mr_last[i] = mask_rows_call(p, n, i + 1).flags != nullptr;
     for (int l = 0; l < l_end; ++l) {
         const Level& a = p->lv[l];
         const Level& b = p->lv[l + 1];
@@ -490,6 +519,13 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
         const ZeroTiles gin = g_flags_call(p, n, l), gout = g_flags_call(p, n, l + 1);
         if (gout.flags && !(wavefront && zt.flags && (a.w & 1) == 0)) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their producer", l + 1);
         if (gin.flags && !do_x) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their reader", l);
+        // row-repeat flags of the mask plane (mask_rows_call): of this level for its readers, of the next for the sweep that produces them
+        const ZeroTiles min_ = mask_rows_call(p, n, l), mout = mask_rows_call(p, n, l + 1);
+        const bool fill_mask = zt.flags && (l == 0 ? mk.enabled != 0 : min_.flags != nullptr);  // T flags of the mask plane mean "repeats row 0"
+        if (mout.flags && !(wavefront && fill_mask && gout.flags && (a.w & 1) == 0 && (a.h & 1) == 0))
+            return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d without their producer", l + 1);
+        if (min_.flags && !(gin.flags && do_x && (wavefront || !zt.flags)))
+            return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d without their reader", l);
         Bands bd{};
         if (mk.enabled || (src && l == 0) || zt.flags || gin.flags) bd = Bands{NR, a.h};
         const int nbx = bd.nr ? np * bd.nr : (int)((lines + TS - 1) / TS);
@@ -507,8 +543,9 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
                 } else if (rcmp)
                     k_vv_x_fwd<PX, false, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, ZeroTiles{}, p->ckpt, bd);
                 else
-                    k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd);
+                    k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd, min_);
             }
+            if (min_.flags && (rcmp || (src && l == 0) || (p->wf_dbg && l == 0))) return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d in front of a sweep that does not know them", l);
             Wavefront wf{};
             wf.yg = p->wf_yg;
             wf.counter = p->wf_ctrl + (size_t)l * 16;
@@ -525,6 +562,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             wf.epoch = 1;
             wf.mask_l0 = mk.enabled ? (zt.flags ? 2 : 1) : 0;  // 2: the mask blur below the first band is recorded in the flags, not stored
             wf.zt = zt;
+            if (fill_mask && l > 0) wf.mr = min_;
             wf.early_read = p->wf_early_read;
             const long ntiles = (long)wf.NP * wf.NR;  // one persistent wavefront per row band
             // the x-sweep state lives in state[0 .. 4*lines); the y state the kernel leaves goes behind it
@@ -551,12 +589,13 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
             }
             StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
             dim3 g((a.pitch + YCOLS - 1) / YCOLS, np);
-            const int fill_l0 = wf.mask_l0 == 2;  // flagged tiles of the mask planes repeat the plane's row 0 (k_vv_xbyf)
+            const int fill_l0 = wf.mask_l0 == 2 || wf.mr.flags;  // flagged tiles of the mask planes repeat the plane's row 0 (k_vv_xbyf)
+            if (fill_l0 != (fill_mask ? 1 : 0)) return fail(STITCH_ERR_ARG, "reduce: the mask plane's T flags of level %d are read in another sense than they are written", l);
             if ((a.w & 1) == 0 && !p->no_fuse) {
                 if (rowz)
-                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout);
+                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
                 else
-                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout);
+                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
                 decimated = true;
             } else if (odd_dec) {  // odd width: three-tap x decimation, workgroups overlap by two columns
                 const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
@@ -595,7 +634,7 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
                     if (src && l == 0)
                         k_vv_x_fwd<PX, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
                     else
-                        k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd);
+                        k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd, min_);
                 }
                 if (!xby) {
                     StageTimer t(p, s, STITCH_K_VV_X_BWD, l);
@@ -775,6 +814,9 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
         const Level& nx = p->lv[l + 1];
         StageTimer tm(p, s, l == 0 ? STITCH_K_COLLAPSE_L0 : STITCH_K_COLLAPSE, l);
         const ZeroTiles gz = g_flags_call(p, n, l), gzn = g_flags_call(p, n, l + 1);  // G column flags of this level and of the one it expands
+        const ZeroTiles mrz = mask_rows_call(p, n, l);  // row-repeat flags of this level's mask plane
+        if ((mrz.flags != nullptr) != (l >= 1 && l <= 2 && p->mr_last[l - 1]))
+            return fail(STITCH_ERR_ARG, "collapse: mask row flags of level %d decided otherwise than in the reduce", l);
         // four columns per work-item on the column range whose taps follow the regular pattern (Level::c4_xa, c4_xb), one
         // column per work-item on the rest, in ONE launch (k_collapse4); levels without such a range run k_collapse
         int xa = 0, xb = 0;
@@ -815,13 +857,24 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
                                          a.pitch, a.ps, nullptr, NoPairArgs{}, 0, crows_of(p, l, n), xa, xb, 1, std::max(0, p->tune.c4_lock), p->tune.c4_swz < 0 ? 1 : p->tune.c4_swz};
             A.gz = gz.flags, A.gnc = gz.NC, A.zo = (unsigned)(7 * (size_t)p->cap * a.ps);
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
+            const MaskRowsArg mra{mrz.flags, mrz.NC, mrz.NR};
+            const bool px = (long)n * a.pitch * a.h <= 4096L * 64 * 2 && p->tune.collapse_px != 0;  // a launch that leaves most SIMDs with at most a wavefront or two
             const int strips = (a.h + A.crows - 1) / A.crows;
             const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n);
-            if (xb > xa && a.c4_gen && p->collapse4)
+            if (mrz.flags) {  // the instances that take the mask sample of a flagged tile from row 0
+                if (xb > xa && a.c4_gen && p->collapse4)
+                    k_collapse4<float, false, false, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
+                else if (xb > xa)
+                    k_collapse4<float, false, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
+                else if (px)
+                    k_collapse_px<true><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A, mra);
+                else
+                    k_collapse<float, false, true><<<grid_xy(cols, strips, n), 256, 0, s>>>(A, mra);
+            } else if (xb > xa && a.c4_gen && p->collapse4)
                 k_collapse4<float, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
             else if (xb > xa)
                 k_collapse4<float, false><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if ((long)n * a.pitch * a.h <= 4096L * 64 * 2 && p->tune.collapse_px != 0)  // a launch that leaves most SIMDs with at most a wavefront or two
+            else if (px)
                 k_collapse_px<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A);
             else
                 k_collapse<float, false><<<grid_xy(cols, strips, n), 256, 0, s>>>(A);
@@ -1817,6 +1870,8 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     const size_t zt_off = wf_levels ? take((size_t)7 * B * ((v0.h + TS - 1) / TS) * ((v0.w + TS - 1) / TS)) : 0;
     size_t gz_off[2] = {0, 0};  // G column flags of levels 1 and 2
     for (int i = 0; i < 2; ++i) gz_off[i] = wf_levels && i + 1 < L ? take((size_t)7 * B * ((lw[i + 1] + TS - 1) / TS)) : 0;
+    size_t mr_off[2] = {0, 0};  // row-repeat flags of the mask plane of levels 1 and 2
+    for (int i = 0; i < 2; ++i) mr_off[i] = wf_levels && i + 1 < L ? take((size_t)B * ((lw[i + 1] + TS - 1) / TS) * ((lh[i + 1] + TS - 1) / TS)) : 0;
     int recompute = 0;  // opt-in: level 0 re-run from the frames measured 3 % slower, the plane levels within noise
     if (tn.recompute >= 0) recompute = wf_levels > 0 ? std::min(2, tn.recompute) : 0;
     const size_t ck_off = recompute ? take(sizeof(double) * 3 * NC0 * 7 * B * (size_t)(v0.h + 64)) : 0;
@@ -1872,6 +1927,7 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
         p->zt = reinterpret_cast<uint8_t*>(base + zt_off);
         p->zi = reinterpret_cast<uint8_t*>(base + zi_off);
         for (int i = 0; i < 2; ++i) p->gz[i] = i + 1 < L ? reinterpret_cast<uint8_t*>(base + gz_off[i]) : nullptr;
+        for (int i = 0; i < 2; ++i) p->mr[i] = i + 1 < L ? reinterpret_cast<uint8_t*>(base + mr_off[i]) : nullptr;
         p->recompute = recompute;
         if (recompute) p->ckpt = reinterpret_cast<double*>(base + ck_off);
         if (tn.xbyf_wgs >= 0) p->wf_max_wgs = std::max(1, tn.xbyf_wgs);
@@ -2128,6 +2184,23 @@ int stitch_plan_g_flag_counts(stitch_plan* p, uint64_t out[2]) {
         if (!p->gz_last[i] || !p->gz[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
         std::vector<uint8_t> h((size_t)7 * p->last_n * ((p->lv[i + 1].w + TS - 1) / TS));
         HIPCHK(hipMemcpy(h.data(), p->gz[i], h.size(), hipMemcpyDeviceToHost));
+        for (uint8_t f : h) out[i] += f != 0;
+    }
+    return STITCH_OK;
+}
+
+int stitch_plan_mask_row_counts(stitch_plan* p, uint64_t out[2]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    for (int i = 0; i < 2; ++i) {
+        out[i] = 0;
+        if (!p->mr_last[i] || !p->mr[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
+        const ZeroTiles m = mask_rows(p->mr[i], p->lv[i + 1].w, p->lv[i + 1].h);
+        std::vector<uint8_t> h((size_t)p->last_n * m.NC * m.NR);
+        HIPCHK(hipMemcpy(h.data(), p->mr[i], h.size(), hipMemcpyDeviceToHost));
         for (uint8_t f : h) out[i] += f != 0;
     }
     return STITCH_OK;
