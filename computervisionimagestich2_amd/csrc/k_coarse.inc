@@ -16,7 +16,6 @@
 //   collapse  k_collapse                (expand_at + blend_ref per output sample)
 // Van Vliet blur only (the Deriche variant keeps the per-level launches).
 constexpr int CO_THREADS = 512;
-constexpr int CO_MAXL = 16;
 struct CoarseLevel {
     float* g;  // 7 planes per pair [a0 a1 a2 b0 b1 b2 m], pitched; pair stride 7 * ps
     float* e;  // 3 planes per pair (collapse chain); pair stride 3 * ps
@@ -138,7 +137,6 @@ __device__ __forceinline__ void coarse_y_cols(float* p, int h, int pitch, const 
         stream_rows<false>(p, pitch, h - 2, h - 1, [&](int y, f2 xv) { *reinterpret_cast<f2*>(p + (size_t)y * pitch) = y2_step_bwd(s, k, xv); });
 }
 
-constexpr int CO_MAXSIDE = 512;  // the host never hands k_coarse a level with w/2 + h/2 above this (tap tables in LDS)
 __global__ __launch_bounds__(CO_THREADS) void k_coarse(CoarseArgs A) {
     __shared__ int tap_s0[CO_MAXSIDE], tap_n[CO_MAXSIDE];
     __shared__ float tap_d[3 * CO_MAXSIDE];
@@ -272,7 +270,6 @@ __global__ __launch_bounds__(CO_THREADS) void k_coarse(CoarseArgs A) {
 // levels above read: E of the first coarse level.  Rows are pitched to an odd number of floats, so that 64 lines (x passes, lane =
 // line) and 64 columns (everything else, lane = column) both spread over the banks.  The arithmetic and its order per sample are
 // k_coarse's; the host takes this form when the levels fit (coarse_lds_floats).
-constexpr int CO_TABN = 192;  // entries of the expand tables of all coarse levels together
 struct CoarseLds {
     int g[CO_MAXL], e[CO_MAXL];  // float offsets of a level's 7 planes G / 3 planes E in the dynamic LDS array
     int t;                       // blur scratch, shaped like the level in work

@@ -149,7 +149,7 @@ __device__ __forceinline__ bool g_col_flag(const uint8_t* __restrict__ flags, in
 // the mask plane is read only at its own level, by the x sweep in whole tiles and by the collapse in aligned 16-byte loads.  A column of
 // zeros is the case where row 0 is +0.  Carried as a ZeroTiles over PAIRS: index(pair, band, tile).  Readers take row 0 instead:
 // k_vv_x_fwd (and skips a band whose tiles are all flagged), k_vv_xbyf (such a band is a constant band, as below the first band of the
-// implicit level-0 mask), the collapse kernels (address select).  mask_rows_call (stitch_hip.hip) decides.
+// implicit level-0 mask), the collapse kernels (address select).  call_form (stitch_call_form.h) decides.
 __host__ __device__ inline ZeroTiles mask_rows(uint8_t* flags, int w, int h) { return ZeroTiles{flags, h, (h + 63) / 64, (w + 63) / 64}; }
 // the mask sample at (x, y) of pair pr is taken from row 0
 __device__ __forceinline__ bool mask_row_flag(const uint8_t* __restrict__ flags, int nc, int nr, int pr, int x, int y) {

@@ -24,7 +24,7 @@
 #ifndef STITCH_XY_WGS
 #define STITCH_XY_WGS 512  // persistent workgroups of a launch: two per CU with four buffers
 #endif
-constexpr int XY_BUFS = STITCH_XY_BUFS, XY_IN = 2, XY_THREADS = 5 * WAVE, XY_MAXNC = 1024, XY_WGS = STITCH_XY_WGS;
+constexpr int XY_BUFS = STITCH_XY_BUFS, XY_IN = 2, XY_THREADS = 5 * WAVE, XY_WGS = STITCH_XY_WGS;
 struct XYState {  // one tile's y state in LDS: three doubles, iplus (last band) and the passed-down mask row per column
     double u[4][WAVE];
     unsigned extra[WAVE];

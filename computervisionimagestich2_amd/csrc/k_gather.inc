@@ -4,7 +4,6 @@
 // ImageProcess.cpp:218-224 + :680-681.  Level-0 planes of pair b: [a0 a1 a2 b0 b1 b2 mask], pitched, plane
 // stride ps, pairs stacked (7*ps apart).  The zero canvases of the reference are implicit: an out-of-range pixel
 // is written as 0.  A launch covers every pair of the batch (blockIdx.z = pair).
-constexpr int MAXB = 16;  // pairs per plan / launch
 template <typename PX>
 struct PairArgs {
     const PX* frame[MAXB];

@@ -141,10 +141,6 @@ struct OutPtrs {
 // and consecutive output rows share their source rows (iy advances by at most one per output row when
 // up-sampling), so the x-interpolated values of the two current source rows are kept in registers and only a newly
 // entered source row is interpolated: the double-precision work per pixel halves, the values are the same floats.
-#ifndef STITCH_CROWS
-#define STITCH_CROWS 8
-#endif
-constexpr int CROWS = STITCH_CROWS;
 // G_0 of a source-fused plan: evaluated from the pair's frames; otherwise read from the level's planes.
 template <typename OUT>
 __device__ __forceinline__ void level_ab(const PairArgs<OUT>& pa, int pr, int use_src, const float* g, size_t o, size_t ps, int x, int y,

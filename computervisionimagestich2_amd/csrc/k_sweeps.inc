@@ -9,7 +9,6 @@
 // ds_read_b128 of "my row" are bank-conflict free.  The next tile is prefetched into registers while the
 // current one runs its 64 recurrence steps.  The forward kernel leaves (v1,v2,v3,iplus) of every line in
 // `state`; the backward kernel starts from the Triggs boundary values computed from them.
-constexpr int TS = 64;  // tile edge
 constexpr int TP = 68;  // padded LDS row (floats)
 
 __device__ __forceinline__ void tile_load(const float* __restrict__ base, int pitch, int c0, int lane, f4 pre[16]) {
@@ -457,7 +456,7 @@ __device__ __forceinline__ Taps make_taps(int t, int n_src, int n_dst) {
 // HBM round trip, so rows are fetched far ahead of their use: YST stages of YCH rows rotate through registers
 // (YCH*(YST-1) = 24 rows in flight per wavefront while one chunk computes).  In place.
 // grid = (ceil(pitch/128), planes); pitch is a multiple of 64, a last half-empty block is masked off.
-constexpr int YCH = 8, YST = 4, YCOLS = 2 * WAVE;
+constexpr int YST = 4;
 
 // Calls f(y, value) for rows y_begin, y_begin +/- 1, ... (count rows), loading each row's value long before.
 typedef float f2 __attribute__((ext_vector_type(2)));

@@ -605,10 +605,11 @@ int stitch_band_top(stitch_band* b, const float* d_g7, void* stream) {
         HIPCHK(hipMemcpy2DAsync(a.g + (size_t)q * a.ps, sizeof(float) * a.pitch, b->gtop + (size_t)q * n, sizeof(float) * a.w, sizeof(float) * a.w, a.h,
                                 hipMemcpyDeviceToDevice, s));
     const PairArgs<float> none{};
-    if ((rc = run_reduce<float>(p, 1, s, none, false, ZeroTiles{}))) return rc;
+    const CallForm c = p->last_form = call_form(*p, 1, false, false);
+    if ((rc = run_reduce<float>(p, c, s, none, ZeroTiles{}))) return rc;
     OutPtrs<float> outs{};
     outs.p[0] = b->etop;
-    if ((rc = run_collapse<float>(p, 1, outs, s, none, false))) return rc;
+    if ((rc = run_collapse<float>(p, c, outs, s, none))) return rc;
     p->last_stream = s, p->pending = true, p->last_n = 1;
     b->last_stream = s, b->pending = true;
     return STITCH_OK;

@@ -74,10 +74,6 @@ int need_device() {
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-// Row pitch of a level's planes in floats: the width rounded up to 64, plus -- for rows of 16 KB and more -- `pad` floats
-// (STITCH_PITCH_PAD, rounded up to 64) so that the 64 rows of a tile do not start a power-of-two-ish number of bytes apart.
-inline int level_pitch(int w, int pad) { return round_up(w, 64) + (pad > 0 && w >= 4096 ? round_up(pad, 64) : 0); }
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 constexpr double kPI = 3.14159265358979323846;  // cimg::PI
 
@@ -145,141 +141,16 @@ DRK make_drk(float sigma) {
     return k;
 }
 
-// CImg.h:29625-29637: idx/alpha of the linear up-sampling walk
-void expand_table(int n_src, int n_dst, std::vector<int32_t>& idx, std::vector<double>& alpha) {
-    idx.resize(n_dst);
-    alpha.resize(n_dst);
-    if (n_src == 1) {
-        for (int x = 0; x < n_dst; ++x) idx[x] = 0, alpha[x] = 0;
-        return;
-    }
-    const double fx = n_dst > 1 ? (n_src - 1.0) / (n_dst - 1) : 0;
-    double curr = 0;
-    for (int x = 0; x < n_dst; ++x) {
-        idx[x] = (int32_t)(unsigned int)curr;
-        alpha[x] = curr - (unsigned int)curr;
-        const double nxt = curr + fx;
-        curr = (n_src - 1.0) < nxt ? (n_src - 1.0) : nxt;
-    }
-}
-
-// The longest run of 256-column blocks in which every group of four columns x0.. has the resize taps s, s+1, s+1, s+2 with
-// s+3 inside the source row (see k_collapse4); [*xa, *xb) empty when there is none or the source level is a single row/column.
-void regular_range(const std::vector<int32_t>& idx, int w, int sw, int sh, int* xa, int* xb) {
-    *xa = *xb = 0;
-    int best_a = 0, best_b = 0, run_a = -1;
-    const int nblk = w / 256;
-    for (int b = 0; b <= nblk; ++b) {
-        bool reg = b < nblk && sw >= 2 && sh >= 2;
-        for (int x0 = b * 256; reg && x0 < (b + 1) * 256; x0 += 4) {
-            const int s_ = idx[x0];
-            reg = idx[x0 + 1] == s_ + 1 && idx[x0 + 2] == s_ + 1 && idx[x0 + 3] == s_ + 2 && s_ + 3 <= sw - 1;
-        }
-        if (reg && run_a < 0) run_a = b;
-        if (!reg && run_a >= 0) {
-            if (b - run_a > best_b - best_a) best_a = run_a, best_b = b;
-            run_a = -1;
-        }
-    }
-    if (best_b > best_a) *xa = best_a * 256, *xb = best_b * 256;
-}
-
-// The columns [0, *xb) (a multiple of 256) in which every group of four columns x0.. has its taps inside ONE 16-byte load at
-// ix[x0]: ix[x0 + 3] + 1 <= ix[x0] + 3 (always true for a step below 1/2; see k_collapse4, GEN).  The window may reach past the
-// source row's last sample: the last group of an even width has the taps s, s+1, s+1, s+1 or s, s+1, s+1, s+2 with the row ending
-// at s + 2, so element 3 of its window is the first sample of the next row (of the next plane, of whatever follows the planes in
-// the arena) -- loaded, selected by no tap: a column whose first tap IS the row's last sample takes that sample twice, as the
-// reference does (CImg.h:29648), whatever the window holds behind it.
-void general_range(const std::vector<int32_t>& idx, int w, int sw, int sh, int* xb) {
-    *xb = 0;
-    if (sw < 4 || sh < 2) return;
-    int x0 = 0;
-    for (; x0 + 3 < w; x0 += 4) {
-        const int s_ = idx[x0];
-        if (!(idx[x0 + 1] >= s_ && idx[x0 + 2] >= idx[x0 + 1] && idx[x0 + 3] >= idx[x0 + 2] && idx[x0 + 3] - s_ <= 2 && s_ >= 0 && s_ + 1 <= sw - 1)) break;
-    }
-    *xb = x0 / 256 * 256;
-}
-
+// pyramid_sizes (stitch_call_form.h) with the reasons spelled out
 int pyramid_levels(int w, int h, int level_rule, int* lw, int* lh) {
-    if (w <= 0 || h <= 0) return fail(STITCH_ERR_ARG, "pyramid: non-positive size %dx%d", w, h);
-    const int len = level_rule ? (w < h ? w : h) : (w >= h ? w : h);
-    int levels = 0;
-    while ((len >> (levels + 1)) > 0) ++levels;  // floor(log2(len)), ImageProcess.cpp:675-676
-    if (levels < 1 || levels > 32) return fail(STITCH_ERR_PYRAMID, "pyramid: %dx%d gives %d levels", w, h, levels);
-    int cw = w, ch = h;
-    for (int i = 0; i < levels; ++i) {
-        if (cw <= 0 || ch <= 0)
-            return fail(STITCH_ERR_PYRAMID, "pyramid: level %d of %dx%d has a zero dimension (the reference degenerates here)",
-                        i, w, h);
-        if (lw) lw[i] = cw;
-        if (lh) lh[i] = ch;
-        cw /= 2;  // ImageProcess.cpp:706-707
-        ch /= 2;
-    }
+    const int levels = pyramid_sizes(w, h, level_rule, lw, lh);
+    if (levels == 0) return fail(STITCH_ERR_ARG, "pyramid: non-positive size %dx%d", w, h);
+    if (levels == -1) return fail(STITCH_ERR_PYRAMID, "pyramid: %dx%d gives 0 levels", w, h);  // (an int's side cannot give more than 32)
+    if (levels < 0)
+        return fail(STITCH_ERR_PYRAMID, "pyramid: level %d of %dx%d has a zero dimension (the reference degenerates here)", -levels - 2, w, h);
     return levels;
 }
 
-// Tuning / A-B switches of a plan (listed in include/stitch.h; none changes a result bit): ONE snapshot of the environment,
-// taken when a plan is created and again whenever a host-pointer entry point looks for an idle plan in the cache.  The
-// snapshot is part of the cache key (PlanKey), so a caller who flips a switch between two calls gets a workspace built for
-// the new setting, never a stale one.  All fields are ints (no padding: compared with memcmp); -1 = not set.
-struct Tuning {
-    int wavefront, no_fuse, no_src_fuse, no_zero_tiles, crows_l0, crows_ln, collapse4, xbyf_wgs, xbyf_spin_limit, xbyf_early, y2,
-        recompute, stamp, gate64, coarse, single_fast, odd_dec, c4_gen, collapse_px, y1s, c4_lock, c4_swz, mover, src_lone, dec7, xbym, xbym_mpix, coarse_lds, pitch_pad, crows_wgs;
-    static int env_int(const char* name) {
-        const char* e = std::getenv(name);
-        return e ? std::max(0, atoi(e)) : -1;
-    }
-    static Tuning from_env() {
-        Tuning t{};
-        t.wavefront = env_int("STITCH_WAVEFRONT");
-        t.no_fuse = env_int("STITCH_NO_FUSE") > 0;
-        t.no_src_fuse = env_int("STITCH_NO_SRC_FUSE") > 0;
-        t.no_zero_tiles = env_int("STITCH_NO_ZERO_TILES") > 0;
-        t.crows_l0 = env_int("STITCH_CROWS_L0");
-        t.crows_ln = env_int("STITCH_CROWS_LN");
-        t.collapse4 = env_int("STITCH_COLLAPSE4");
-        t.xbyf_wgs = env_int("STITCH_XBYF_WGS");
-        t.xbyf_spin_limit = env_int("STITCH_XBYF_SPIN_LIMIT");
-        t.xbyf_early = env_int("STITCH_XBYF_EARLY");
-        t.y2 = env_int("STITCH_Y2") > 0;
-        t.recompute = env_int("STITCH_RECOMPUTE");
-        t.stamp = env_int("STITCH_WAVEFRONT_STAMP") > 0;
-        t.gate64 = env_int("STITCH_GATE64") > 0;
-        t.coarse = env_int("STITCH_COARSE");
-        t.single_fast = env_int("STITCH_SINGLE_FAST");
-        t.odd_dec = env_int("STITCH_ODD_DEC");
-        t.c4_gen = env_int("STITCH_C4_GEN");
-        t.collapse_px = env_int("STITCH_COLLAPSE_PX");
-        t.y1s = env_int("STITCH_Y1S");
-        t.c4_lock = env_int("STITCH_C4_LOCKSTEP");
-        t.c4_swz = env_int("STITCH_C4_SWIZZLE");
-        t.mover = env_int("STITCH_MOVER");
-        t.src_lone = env_int("STITCH_SRC_LONE_MPIX");
-        t.dec7 = env_int("STITCH_DEC7");
-        t.xbym = env_int("STITCH_XBYM");
-        t.xbym_mpix = env_int("STITCH_XBYM_MPIX");
-        t.coarse_lds = env_int("STITCH_COARSE_LDS");
-        t.pitch_pad = env_int("STITCH_PITCH_PAD");
-        t.crows_wgs = env_int("STITCH_CROWS_WGS");
-        return t;
-    }
-    bool operator==(const Tuning& o) const { return std::memcmp(this, &o, sizeof o) == 0; }
-};
-
-struct Level {
-    int w, h, pitch;
-    size_t ps;       // plane stride in floats = pitch*h
-    float* g;        // 7 planes [a0 a1 a2 b0 b1 b2 m] + 64 slack rows
-    float* e;        // 3 planes (collapse chain), levels >= 1
-    int32_t *ix, *iy;  // expand tables level+1 -> level (levels < L-1)
-    double *ax, *ay;
-    int c4_xa, c4_xb;  // columns [c4_xa, c4_xb) of this level go to k_collapse4 (multiples of 256; empty when equal)
-    int c4_gen;        // != 0: [0, c4_xb) with per-lane tap offsets (k_collapse4 GEN) -- chosen where it covers more than the fixed pattern
-};
-
-constexpr int CO_LDS_BYTES = 144 * 1024;  // dynamic LDS k_coarse_lds may take (160 KB per CU, 15 KB of tables beside it)
 constexpr int WF_CTRL_WORDS = 4 * 16 + 16;  // band-queue heads of up to 4 levels (64 bytes apart) + the abort word
 constexpr int WF_STICKY_WORDS = 16;         // behind them, outside what a launch sequence clears: the plan's count of timed-out waits and,
                                             // from word 2, its three 64-bit hand-off counts (stitch_plan_handoff_counts)
@@ -291,42 +162,30 @@ struct ProfRec {
 
 }  // namespace
 
-struct stitch_plan {
+// A plan: its shape (stitch_call_form.h: sizes, switches, which forms it was built for) and the device memory carved for it.
+struct stitch_plan : PlanShape {
     int device = 0;
-    int cw = 0, ch = 0, L = 0;
-    int cap = 1;     // pairs per launch sequence this workspace can hold (planes of pair b follow pair b-1)
-    int last_n = 0;  // pairs of the last call
-    stitch_blend_opts opts{};
-    Tuning tune{};  // the environment's switches as they were when the plan was created
-    Level lv[32]{};
+    int last_n = 0;         // pairs of the last call
+    CallForm last_form{};   // the form of the last call (which flag arrays it wrote: stitch_plan_g_flag_counts, stitch_plan_mask_row_counts)
     void* arena = nullptr;
     size_t arena_bytes = 0;
     float* T = nullptr;   // blur scratch, 7 planes of level 0 + slack
     float* T2 = nullptr;  // Deriche temporaries (blur_kind 1 only)
     double* state = nullptr;
-    // fused anticausal-x + causal-y wavefront sweep (k_vv_xbyf) for the first `wf_levels` levels
-    int wf_levels = 0;
     u64* wf_yg = nullptr;
     size_t wf_yg_bytes = 0;
     unsigned* wf_ctrl = nullptr;   // per level one band-queue head (16 words apart), then the abort flag
     uint8_t* zi = nullptr;         // [cap][tiles][bands] of level 0: "every pixel of the tile lies outside the frame" (k_src_index)
     uint8_t* zt = nullptr;         // zero-tile flags of T, [7*cap][bands][tiles] of level 0 (ZeroTiles); reused level by level
-    bool zero_tiles = false;
-    uint8_t* gz[2] = {nullptr, nullptr};  // G column flags of levels 1 and 2, [7*cap][tile columns] (g_cols; g_flags_call decides per call)
-    bool gz_last[2] = {false, false};     // the last call used them (stitch_plan_g_flag_counts)
-    uint8_t* mr[2] = {nullptr, nullptr};  // row-repeat flags of the mask plane of levels 1 and 2, [cap][tile columns][bands] (mask_rows; mask_rows_call decides per call)
-    bool mr_last[2] = {false, false};     // the last call used them (stitch_plan_mask_row_counts)
+    uint8_t* gz[2] = {nullptr, nullptr};  // G column flags of levels 1 and 2, [7*cap][tile columns] (g_cols)
+    uint8_t* mr[2] = {nullptr, nullptr};  // row-repeat flags of the mask plane of levels 1 and 2, [cap][tile columns][bands] (mask_rows)
     const float* zero_page = nullptr;  // 4 KB of zeros in the arena (k_vv_xby_m's loader reads a flagged tile from here)
     int wf_max_wgs = 2304;  // persistent workgroups of the fused sweep (STITCH_XBYF_WGS)
     unsigned wf_spin_limit = 1u << 23;  // polls before a hand-off wait gives up, about 20 s (STITCH_XBYF_SPIN_LIMIT); 2^20 (2-3 s) was reached once in a warm-up
     int wf_early_read = 1;  // STITCH_XBYF_EARLY=0: poll for the hand-off only when it is needed
-    // The causal x sweep of a wavefront level keeps only its state in front of every tile and the fused sweep re-runs it
-    // tile by tile (k_vv_x_fwd<.., CKPT>, k_vv_xbyf MODE 1/2): the x-swept level is neither written nor read back.
-    // STITCH_RECOMPUTE=0 keeps the two-pass form.
-    int recompute = 0;  // 0 off, 1 every wavefront level, 2 the wavefront levels >= 1 only
-    double* ckpt = nullptr;  // [3][tiles of level 0][lines of level 0]
+    double* ckpt = nullptr;  // STITCH_RECOMPUTE: [3][tiles of level 0][lines of level 0]
     unsigned long long* d7_dbg = nullptr;  // STITCH_D7_STAMP=<level>: k_vv_y_bwd_dec7's per-chunk stamps of one workgroup at that level (diagnostics)
-    int d7_dbg_level = -1, d7_dbg_chunks = 0;
+    int d7_dbg_chunks = 0;
     unsigned long long* xy_dbg = nullptr;  // STITCH_XBYM_STAMP=1: k_vv_xby_m's per-tile stamps of one band of the last level-0 launch (diagnostics)
     int xy_dbg_nc = 0;
     unsigned long long* wf_dbg = nullptr;  // STITCH_WAVEFRONT_STAMP=1: [wf_max_wgs][8] segment cycle sums (diagnostics)
@@ -335,30 +194,53 @@ struct stitch_plan {
     unsigned* h_wf_abort = nullptr;
     unsigned wf_abort_seen = 0;  // count already acknowledged by stitch_plan_clear_fault
     float* side = nullptr;  // [cap][pitch0] x-blurred level-0 mask rows (implicit level-0 mask)
-    bool mask_opt = false;  // level-0 mask handled implicitly (Van Vliet, level-0 height a multiple of 64)
-    // rows per work-item strip of the collapse (a strip re-uses its x-interpolated source rows from output row to output
-    // row, and its rows are one serial chain of load latencies): 32 at the large levels (fewer re-reads of level l+1), h/32
-    // but at least 4 at the small ones, whose launches are nothing but that chain.  STITCH_CROWS_L0 / STITCH_CROWS_LN override.
-    int crows_ln = 0;  // 0 = per level, crows_of()
-    int crows_l0 = 4 * CROWS;
-    bool collapse4 = true;  // four columns per work-item in the collapse where possible (STITCH_COLLAPSE4=0: always k_collapse)
     unsigned long long* co_dbg = nullptr;  // STITCH_COARSE_STAMP=1: k_coarse's phase stamps of the last launch (diagnostics)
-    int coarse_from = 0;  // > 0: levels coarse_from .. L-1 run in ONE launch (k_coarse: REDUCE to the top, top blend, collapse back up)
-    bool src_fuse = false;  // pairs: level-0 planes evaluated from the frames by their consumers, k_compose never runs
     SeamDev* d_seam = nullptr;
     SeamDev* h_seam = nullptr;  // pinned
     hipStream_t last_stream = nullptr;
     bool pending = false;
     VVK vvk{};
     DRK drk{};
-    bool blur_skip = false;
-    bool no_fuse = false;  // STITCH_NO_FUSE=1: keep blur and decimation as separate kernels (A/B and tests)
-    bool planes_in = false;  // level 0 (a, b AND the mask plane) is handed in by the caller (the coarse levels of a band-split pair): no seam scan, no implicit mask
     bool profiling = false;
     int prof_only = -1;  // >= 0: record events only around launches of this kernel id
     std::vector<ProfRec> recs;
     std::vector<hipEvent_t> free_events;
 };
+
+Tuning sk::Tuning::from_env() {
+    Tuning t{};
+    t.wavefront = env_int("STITCH_WAVEFRONT");
+    t.no_fuse = env_int("STITCH_NO_FUSE") > 0;
+    t.no_src_fuse = env_int("STITCH_NO_SRC_FUSE") > 0;
+    t.no_zero_tiles = env_int("STITCH_NO_ZERO_TILES") > 0;
+    t.crows_l0 = env_int("STITCH_CROWS_L0");
+    t.crows_ln = env_int("STITCH_CROWS_LN");
+    t.collapse4 = env_int("STITCH_COLLAPSE4");
+    t.xbyf_wgs = env_int("STITCH_XBYF_WGS");
+    t.xbyf_spin_limit = env_int("STITCH_XBYF_SPIN_LIMIT");
+    t.xbyf_early = env_int("STITCH_XBYF_EARLY");
+    t.y2 = env_int("STITCH_Y2") > 0;
+    t.recompute = env_int("STITCH_RECOMPUTE");
+    t.stamp = env_int("STITCH_WAVEFRONT_STAMP") > 0;
+    t.gate64 = env_int("STITCH_GATE64") > 0;
+    t.coarse = env_int("STITCH_COARSE");
+    t.single_fast = env_int("STITCH_SINGLE_FAST");
+    t.odd_dec = env_int("STITCH_ODD_DEC");
+    t.c4_gen = env_int("STITCH_C4_GEN");
+    t.collapse_px = env_int("STITCH_COLLAPSE_PX");
+    t.y1s = env_int("STITCH_Y1S");
+    t.c4_lock = env_int("STITCH_C4_LOCKSTEP");
+    t.c4_swz = env_int("STITCH_C4_SWIZZLE");
+    t.mover = env_int("STITCH_MOVER");
+    t.src_lone = env_int("STITCH_SRC_LONE_MPIX");
+    t.dec7 = env_int("STITCH_DEC7");
+    t.xbym = env_int("STITCH_XBYM");
+    t.xbym_mpix = env_int("STITCH_XBYM_MPIX");
+    t.coarse_lds = env_int("STITCH_COARSE_LDS");
+    t.pitch_pad = env_int("STITCH_PITCH_PAD");
+    t.crows_wgs = env_int("STITCH_CROWS_WGS");
+    return t;
+}
 
 namespace {
 
@@ -398,348 +280,170 @@ int launch_check(const char* what) {
     return STITCH_OK;
 }
 
-// The fused anticausal-x + causal-y sweep of a call with n pairs (see run_reduce): a per-CALL choice, like src_fused_call.
-// (Until round 4 one pair of >= 800 bands -- config 5 -- took the batch's sweep too; the five-wavefront form with zero-tile flags is 2.6 %
-// faster there, 22.3 against 22.9 ms per pair.  STITCH_XBYM=0 brings the old choice back.)
-bool fused_sweep_call(const stitch_plan* p, int n) {
-    return p->tune.wavefront >= 0 || p->tune.single_fast > 0 || n >= 2 || (p->tune.xbym == 0 && 7L * ((p->lv[0].h + TS - 1) / TS) >= 800);
+// The hand-off record of a fused sweep of level l (k_vv_xbyf, k_vv_xby_m), behind the clear of its granules: every polled word is
+// cleared in front of the launch (never told apart by a per-launch argument: a captured graph replays frozen arguments, and stale
+// tags from the previous replay would match at once)
+Wavefront wavefront_of(stitch_plan* p, int l, int np, const LevelForm& f, const ZeroTiles& zt, hipStream_t s) {
+    Wavefront wf{};
+    wf.yg = p->wf_yg;
+    wf.counter = p->wf_ctrl + (size_t)l * 16;
+    wf.abort = p->wf_ctrl + WF_CTRL_WORDS - 16;
+    wf.sticky = p->wf_ctrl + WF_CTRL_WORDS;
+    wf.spin_limit = p->wf_spin_limit;
+    wf.NR = f.NR;
+    wf.NC = f.NC;
+    wf.NP = np;
+    wf.epoch = 1;
+    wf.zt = zt;
+    wf.early_read = p->wf_early_read;
+    const size_t gran_words = (size_t)wf.NP * wf.NC * WF_GRAN * WAVE;
+    k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(p->wf_yg, gran_words);
+    return wf;
 }
 
-// G column flags of level l (1 or 2) in a call with n pairs, or none (see g_cols, k_compose.inc): the ONE place that decides.  They are on
-// only where the level's producer AND every kernel that reads G_l later in the same call know them:
-//   producer        k_vv_y_bwd_dec with T flags behind the fused sweep of level l-1, even width (the ODD instance advances by 63 columns);
-//   x sweep of l    k_vv_x_fwd (not its CKPT form nor k_vv_xbyf MODE 1, which fetch G_l again: no flags under STITCH_RECOMPUTE; not
-//                   k_vv_x_m, which a small batch takes; not the copy of a width of 1);
-//   collapse        k_collapse4 / k_collapse / k_collapse_px of levels l-1 and l, all three (CollapseArgs::gz, gzn);
-//   not             k_coarse and k_blend_top (levels from coarse_from on, the top level), the band path and the coarse levels of a split
-//                   pair (planes_in), the lone-pair sweeps (they never run in a call that takes the fused sweep), k_decimate (its level
-//                   has no T flags, so no producer).
-// The collapse reads a flagged column from the level's slack rows, at a 32-bit offset from its plane: levels beyond that are left alone.
-// STITCH_NO_G_FLAGS (compile time, A/B libraries): never.
-ZeroTiles g_flags_call(const stitch_plan* p, int n, int l) {
-#ifdef STITCH_NO_G_FLAGS
-    return ZeroTiles{};
-#else
-    if (l < 1 || l > 2 || !p->gz[l - 1] || !p->zero_tiles || p->planes_in || p->no_fuse || p->opts.blur_kind != 0 || p->blur_skip ||
-        p->recompute != 0 || p->wf_dbg || !fused_sweep_call(p, n))
-        return ZeroTiles{};
-    if (l >= (p->coarse_from > 0 ? p->coarse_from : p->L - 1)) return ZeroTiles{};
-    const Level& a = p->lv[l - 1];
-    const Level& b = p->lv[l];
-    if (l - 1 >= p->wf_levels || a.w < 2 || a.h < 2 || (a.w & 1) != 0 || (a.h + TS - 1) / TS > 256 || (p->tune.gate64 && a.h % TS)) return ZeroTiles{};
-    if (b.w < 2) return ZeroTiles{};
-    const bool fused_l = l < p->wf_levels && b.h > 1;
-    if (!fused_l && p->tune.mover != 0 && 7L * n * ((b.h + TS - 1) / TS) <= 340) return ZeroTiles{};
-    if (7ull * p->cap * b.ps + 64ull * b.pitch >= (1ull << 32)) return ZeroTiles{};  // (in samples)
-    return g_cols(p->gz[l - 1], b.w);
-#endif
+// The fused anticausal-y sweep + decimation of level a into level b: k_vv_y_bwd_dec<rowz, YST, dec_zt, dec_odd> of the record
+// (the odd instance: three-tap x decimation, workgroups overlap by two columns)
+void launch_y_bwd_dec(const stitch_plan* p, const LevelForm& f, int np, hipStream_t s, const Level& a, const Level& b, const double* ystate, const ZeroTiles& zt,
+                      int fill_l0, const ZeroTiles& gout, const ZeroTiles& mout) {
+    const dim3 g = f.dec_odd ? dim3((b.w + WAVE - 2) / (WAVE - 1), np) : dim3((a.pitch + YCOLS - 1) / YCOLS, np);
+    auto go = [&](auto R, auto Z, auto O) {
+        k_vv_y_bwd_dec<decltype(R)::value, YST, decltype(Z)::value, decltype(O)::value>
+            <<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
+    };
+    const std::true_type y{};
+    const std::false_type no{};
+    if (!f.dec_zt)
+        f.dec_odd ? go(no, no, y) : go(no, no, no);
+    else if (f.rowz)
+        f.dec_odd ? go(y, y, y) : go(y, y, no);
+    else
+        f.dec_odd ? go(no, y, y) : go(no, y, no);
 }
 
-// Row-repeat flags of the mask plane of level l (1 or 2) in a call with n pairs, or none (see mask_rows, k_compose.inc): the ONE place that
-// decides.  On only where the G column flags of the level are on (the same producer launch, the same readers, none of k_vv_x_m, STITCH_RECOMPUTE,
-// the band path, the XCH / ODD / BANDED instances, the levels from coarse_from on), and
-//   producer        k_vv_y_bwd_dec below a level l-1 of even width AND even height (below an odd height the decimation's overlap weights
-//                   change from row to row and the rows do not repeat), on a plane whose T flags mean "repeats row 0": level 0 with the
-//                   implicit mask recorded in the flags (Wavefront::mask_l0 == 2), level 1 fused with these flags of its own;
-//   x sweep of l    k_vv_x_fwd<PX, false>: a flagged tile from row 0; at a fused level a band flagged throughout is skipped;
-//   fused sweep     k_vv_xbyf MODE 0 (Wavefront::mr): such a band is a constant band, its T tiles recorded as repeats of row 0;
-//   y sweep of l    k_vv_y_bwd_dec with fill_l0: a flagged lane re-reads row 0 of T and keeps it;
-//   collapse of l   k_collapse4 / k_collapse / k_collapse_px (their MR instances, MaskRowsArg): the mask sample from row 0.
-// An unfused level 2 (a large batch) only redirects: k_vv_x_bwd, k_vv_y_fwd1 and its k_vv_y_bwd_dec work on T, which is stored in full.
-// STITCH_NO_MASK_ROWS (compile time, A/B libraries): never.  STITCH_NO_ZERO_TILES=1 turns them off with the other flags.
-ZeroTiles mask_rows_call(const stitch_plan* p, int n, int l) {
-#ifdef STITCH_NO_MASK_ROWS
-    return ZeroTiles{};
-#else
-    if (l < 1 || l > 2 || !p->mr[l - 1] || !g_flags_call(p, n, l).flags) return ZeroTiles{};
-    const Level& a = p->lv[l - 1];
-    if ((a.w & 1) != 0 || (a.h & 1) != 0) return ZeroTiles{};
-    if (l == 1 && !p->mask_opt) return ZeroTiles{};
-    if (l == 2 && (!mask_rows_call(p, n, 1).flags || p->lv[1].h < 2)) return ZeroTiles{};
-    return mask_rows(p->mr[l - 1], p->lv[l].w, p->lv[l].h);
-#endif
-}
-
-// One pair in flight: the anticausal x and the causal y sweep of level l as ONE launch of five-wavefront bands (k_vv_xby_m) where the
-// separate launches are bound by their bytes -- from STITCH_XBYM_MPIX megapixels per plane (default 20: 6144 x 4096).  Below that a level's time is
-// its chain of rows and columns either way, and the fused form adds a hand-off per 64-row band.  STITCH_XBYM=0: never; =1: the first
-// four levels of every lone pair, whatever their size (tests).
-bool lone_fused_level(const stitch_plan* p, int n, int l) {
-    const Level& a = p->lv[l];
-    const long mpix = p->tune.xbym > 0 ? 0 : p->tune.xbym_mpix >= 0 ? p->tune.xbym_mpix : 20;
-    return n == 1 && p->wf_ctrl && l < 4 && p->opts.blur_kind == 0 && !p->blur_skip && p->tune.mover != 0 && p->tune.xbym != 0 && a.w > 1 && a.h > 1 &&
-           (long)a.w * a.h >= mpix * 1000000L && (a.h + TS - 1) / TS < 4095 && !fused_sweep_call(p, n);
-}
-
-// REDUCE for every level (ImageProcess.cpp:705-715): blur(G_l) into T, decimate T into G_{l+1}.
+// REDUCE for every level (ImageProcess.cpp:705-715): blur(G_l) into T, decimate T into G_{l+1}.  Which kernels: the call's form
+// (stitch_call_form.h); here are their arguments.
 template <typename PX>
-int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const ZeroTiles& zi) {
-    const int np = 7 * n;  // planes in flight: every launch covers all pairs of the batch
-    const bool any_lone_fused = lone_fused_level(p, n, 0);  // levels shrink: level 0 qualifies whenever any level does
-    if (p->wf_levels > 0 || any_lone_fused) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
-    const int l_end = p->coarse_from > 0 ? p->coarse_from : p->L - 1;  // levels [0, l_end) are reduced level by level
-    for (int i = 0; i < 2; ++i) p->gz_last[i] = g_flags_call(p, n, i + 1).flags != nullptr;
-    for (int i = 0; i < 2; ++i) p->mr_last[i] = mask_rows_call(p, n, i + 1).flags != nullptr;
-    for (int l = 0; l < l_end; ++l) {
+int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<PX>& pa, const ZeroTiles& zi) {
+    const int n = c.n, np = 7 * n;  // planes in flight: every launch covers all pairs of the batch
+    if (c.wf_ctrl) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
+    for (int l = 0; l < c.l_end; ++l) {
+        const LevelForm& f = c.lv[l];
         const Level& a = p->lv[l];
         const Level& b = p->lv[l + 1];
         const long lines = (long)np * a.h;
-        const bool do_x = a.w > 1 && !p->blur_skip, do_y = a.h > 1 && !p->blur_skip;
-        bool decimated = false;
         MaskL0 mk{};
-        if (l == 0 && p->mask_opt) {
-            mk.seam = p->d_seam;
-            mk.side = p->side;
-            mk.h = a.h;
-            mk.enabled = 1;
-        }
-        // The band pipeline pays where a launch has many bands in flight to hide its fill (see stitch_plan_create_batched): decided
-        // per CALL -- a batched plan asked for one pair runs the separate sweeps, which are faster for a lone pair (3.0 against
-        // 3.4 ms at 6144 x 4096) -- unless STITCH_WAVEFRONT or STITCH_SINGLE_FAST pins the form.
-        const bool wavefront = p->opts.blur_kind == 0 && do_x && do_y && l < p->wf_levels && fused_sweep_call(p, n);
-        // odd widths decimate inside the anticausal sweep too (three overlaps per output column); a width of 1 has no next level column
-        const bool odd_dec = (a.w & 1) != 0 && a.w >= 3 && !p->no_fuse && p->tune.odd_dec != 0;
-        // zero-tile flags: only where all three users run (causal x sweep, fused sweep, fused anticausal-y + decimation)
-        const int NR = (a.h + TS - 1) / TS;  // 64-row bands per plane, the last one possibly partial
-        ZeroTiles zt{};
-        // (the five-wavefront sweep of ONE pair carries the flags too where its x sweeps are the one-wavefront kernels anyway -- more bands
-        // than the chain + loader + storer form takes: a pair of config 5's size)
-        const int nbx_bands = np * NR;
-        const bool xby_zt = !wavefront && p->zt && do_x && do_y && lone_fused_level(p, n, l) && (a.w + TS - 1) / TS <= XY_MAXNC &&
-                            !(p->tune.mover != 0 && (nbx_bands <= 340 || (src && l == 0 && nbx_bands <= 1024)));
-        if ((wavefront || xby_zt) && p->zero_tiles && NR <= 256 && ((a.w & 1) == 0 || odd_dec) && !p->no_fuse && !(p->tune.gate64 && (a.h % TS || (a.w & 1)))) {
-            zt.flags = p->zt;
-            zt.h = a.h;
-            zt.NR = NR;
-            zt.NC = (a.w + TS - 1) / TS;
-        }
-        // blocks of the x sweeps: per-plane bands wherever a block's treatment depends on its plane (implicit mask, source-fused
-        // level 0, zero-tile flags), 64 stacked lines otherwise (fewer blocks when planes are shorter than 64 rows)
-        // G column flags (g_flags_call): of this level's planes for the causal x sweep, of the next level's for the sweep that produces them
-        const ZeroTiles gin = g_flags_call(p, n, l), gout = g_flags_call(p, n, l + 1);
-        if (gout.flags && !(wavefront && zt.flags && (a.w & 1) == 0)) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their producer", l + 1);
-        if (gin.flags && !do_x) return fail(STITCH_ERR_ARG, "reduce: G column flags of level %d without their reader", l);
-        // row-repeat flags of the mask plane (mask_rows_call): of this level for its readers, of the next for the sweep that produces them
-        const ZeroTiles min_ = mask_rows_call(p, n, l), mout = mask_rows_call(p, n, l + 1);
-        const bool fill_mask = zt.flags && (l == 0 ? mk.enabled != 0 : min_.flags != nullptr);  // T flags of the mask plane mean "repeats row 0"
-        if (mout.flags && !(wavefront && fill_mask && gout.flags && (a.w & 1) == 0 && (a.h & 1) == 0))
-            return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d without their producer", l + 1);
-        if (min_.flags && !(gin.flags && do_x && (wavefront || !zt.flags)))
-            return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d without their reader", l);
-        Bands bd{};
-        if (mk.enabled || (src && l == 0) || zt.flags || gin.flags) bd = Bands{NR, a.h};
-        const int nbx = bd.nr ? np * bd.nr : (int)((lines + TS - 1) / TS);
-        const bool rowz = zt.flags && (a.h % YCH) != 0;  // fused anticausal-y + decimation: a chunk of rows may straddle bands
-        if (wavefront) {
-            const int nb = nbx;
-            const bool rcmp = (p->recompute == 1 || (p->recompute == 2 && l >= 1)) && !(p->wf_dbg && l == 0);
-            {
-                StageTimer t(p, s, src && l == 0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD, l);
-                if (src && l == 0) {
-                    if (rcmp)
-                        k_vv_x_fwd<PX, true, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, p->ckpt, bd);
-                    else
-                        k_vv_x_fwd<PX, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
-                } else if (rcmp)
-                    k_vv_x_fwd<PX, false, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, ZeroTiles{}, p->ckpt, bd);
-                else
-                    k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd, min_);
-            }
-            if (min_.flags && (rcmp || (src && l == 0) || (p->wf_dbg && l == 0))) return fail(STITCH_ERR_ARG, "reduce: mask row flags of level %d in front of a sweep that does not know them", l);
-            Wavefront wf{};
-            wf.yg = p->wf_yg;
-            wf.counter = p->wf_ctrl + (size_t)l * 16;
-            wf.abort = p->wf_ctrl + WF_CTRL_WORDS - 16;
-            wf.sticky = p->wf_ctrl + WF_CTRL_WORDS;
-            wf.spin_limit = p->wf_spin_limit;
-            wf.NR = NR;
-            wf.NC = (a.w + TS - 1) / TS;
-            wf.NP = np;
-            // every polled word is cleared in front of the launch (never told apart by a per-launch argument: a captured
-            // graph replays frozen arguments, and stale tags from the previous replay would match at once)
-            const size_t gran_words = (size_t)wf.NP * wf.NC * WF_GRAN * WAVE;
-            k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(p->wf_yg, gran_words);
-            wf.epoch = 1;
-            wf.mask_l0 = mk.enabled ? (zt.flags ? 2 : 1) : 0;  // 2: the mask blur below the first band is recorded in the flags, not stored
-            wf.zt = zt;
-            if (fill_mask && l > 0) wf.mr = min_;
-            wf.early_read = p->wf_early_read;
-            const long ntiles = (long)wf.NP * wf.NR;  // one persistent wavefront per row band
-            // the x-sweep state lives in state[0 .. 4*lines); the y state the kernel leaves goes behind it
-            double* state_y = p->state + 4 * (size_t)p->cap * 7 * (a.h + 64);
-            {
-                StageTimer t(p, s, STITCH_K_VV_XBYF, l);
-                const int wg = (int)std::min<long>(ntiles, p->wf_max_wgs);  // at most 9 workgroups per CU by LDS
-                Recompute rcv{};
-                if (rcmp) {
-                    rcv.in = a.g;
-                    rcv.ckpt = p->ckpt;
-                    rcv.seam = p->d_seam;
-                    if (src && l == 0) rcv.zi = zi;
-                }
-                if (p->wf_dbg && l == 0) {  // diagnostic build: per-segment cycle sums of the level-0 launch
-                    wf.dbg = p->wf_dbg;
-                    k_vv_xbyf<true><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
-                } else if (rcmp && src && l == 0)
-                    k_vv_xbyf<false, PX, 2><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, pa);
-                else if (rcmp)
-                    k_vv_xbyf<false, float, 1><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
-                else
-                    k_vv_xbyf<false><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
-            }
-            StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
-            dim3 g((a.pitch + YCOLS - 1) / YCOLS, np);
-            const int fill_l0 = wf.mask_l0 == 2 || wf.mr.flags;  // flagged tiles of the mask planes repeat the plane's row 0 (k_vv_xbyf)
-            if (fill_l0 != (fill_mask ? 1 : 0)) return fail(STITCH_ERR_ARG, "reduce: the mask plane's T flags of level %d are read in another sense than they are written", l);
-            if ((a.w & 1) == 0 && !p->no_fuse) {
-                if (rowz)
-                    k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
-                else
-                    k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
-                decimated = true;
-            } else if (odd_dec) {  // odd width: three-tap x decimation, workgroups overlap by two columns
-                const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
-                if (rowz)
-                    k_vv_y_bwd_dec<true, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
-                else
-                    k_vv_y_bwd_dec<false, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, state_y, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0);
-                decimated = true;
-            } else
-                k_vv_y_bwd<<<g, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, state_y, nullptr, nullptr);
-        } else if (p->opts.blur_kind == 0) {
-            // few enough blocks for a workgroup of three wavefronts each (chain, loader, storer: k_sweeps1.inc) to find SIMDs of its own:
-            // the recurrence alone on one wavefront, the tiles' traffic -- and, at a source-fused level 0, the gathers -- on the others
-            const bool mover = p->tune.mover != 0;
-            const bool src0 = src && l == 0;
-            const bool xby = do_x && do_y && lone_fused_level(p, n, l);
-            const double* ystate = p->state;  // where the causal y sweep leaves its state for the anticausal one
-            if (do_x && mover && !zt.flags && !gin.flags && (nbx <= 340 || (src0 && nbx <= 1024))) {
-                {
-                    StageTimer t(p, s, src0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD, l);
-                    if (src0)
-                        k_vv_x_m<true, PX, true><<<nbx, 192, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, pa);
-                    else
-                        k_vv_x_m<true><<<nbx, 192, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, NoPairArgs{});
-                }
-                StageTimer t(p, s, STITCH_K_VV_X_BWD, l);
-                if (xby) {
-                } else if (nbx <= 340)
-                    k_vv_x_m<false><<<nbx, 192, 0, s>>>(p->T, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, NoPairArgs{});
-                else
-                    k_vv_x_bwd<<<nbx, 64, 0, s>>>(p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd);
-            } else if (do_x) {
-                const int nb = nbx;
-                {
-                    StageTimer t(p, s, src && l == 0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD, l);
-                    if (src && l == 0)
-                        k_vv_x_fwd<PX, true><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
-                    else
-                        k_vv_x_fwd<PX, false><<<nb, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd, min_);
-                }
-                if (!xby) {
-                    StageTimer t(p, s, STITCH_K_VV_X_BWD, l);
-                    k_vv_x_bwd<<<nb, 64, 0, s>>>(p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd);
-                }
-            } else
-                HIPCHK(hipMemcpyAsync(p->T, a.g, sizeof(float) * a.ps * np, hipMemcpyDeviceToDevice, s));
-            if (xby) {
-                Wavefront wf{};
-                wf.yg = p->wf_yg;
-                wf.counter = p->wf_ctrl + (size_t)l * 16;
-                wf.abort = p->wf_ctrl + WF_CTRL_WORDS - 16;
-                wf.sticky = p->wf_ctrl + WF_CTRL_WORDS;
-                wf.spin_limit = p->wf_spin_limit;
-                wf.NR = NR;
-                wf.NC = (a.w + TS - 1) / TS;
-                wf.NP = np;
-                wf.epoch = 1;
-                wf.mask_l0 = mk.enabled;
-                wf.zt = zt;
-                if (p->xy_dbg && l == 0) wf.dbg = p->xy_dbg, p->xy_dbg_nc = wf.NC;
-                // every polled word is cleared in front of the launch (see the batch form above)
-                const size_t gran_words = (size_t)wf.NP * wf.NC * WF_GRAN * WAVE;
-                k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(p->wf_yg, gran_words);
-                // the x state lives in state[0 .. 4 * lines); the y state the kernel leaves goes behind it
-                double* state_y = p->state + 4 * (size_t)p->cap * 7 * (a.h + 64);
-                ystate = state_y;
-                StageTimer t(p, s, STITCH_K_VV_XBYF, l);
-                // two workgroups per CU by LDS: every band of a lone 6144 x 4096 pair (448) is resident at once
-                k_vv_xby_m<<<(int)std::min<long>((long)wf.NP * wf.NR, XY_WGS), XY_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, p->zero_page);
-            }
-            if (do_y) {
-                dim3 g((a.pitch + YCOLS - 1) / YCOLS, np);
-                // fewer than 1.5 wavefronts per SIMD: the launch's time is one wavefront's chain of rows, i.e. its instructions per
-                // row (k_sweeps1.inc): one column per work-item, rows through scalar offsets, the decimation on three consumer wavefronts
-                const bool lone = (long)g.x * g.y < 1536 && !p->tune.y2, small_plane = a.ps * sizeof(float) < 0x7fffffffULL;
-                const bool ymover = mover && lone && (long)(a.pitch / WAVE) * np <= 340;  // chain + mover, 64 columns per workgroup
-                if (!xby) {
-                    StageTimer t(p, s, STITCH_K_VV_Y_FWD, l);
-                    if (ymover)
-                        k_vv_y_m<true><<<dim3(a.pitch / WAVE, np), 192, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk);
-                    else if (lone && small_plane && p->tune.y1s != 0 && (p->tune.y1s >= 2 || a.ps * np * sizeof(float) * 2 < (1000u << 20)))
-                        // (56 rows in flight; a sweep that moves more than ~1 GB is bound by bytes and streams better on flat addresses:
-                        // 4421 x 2315 level 0 129 -> 98 us, 6144 x 4096 level 0 266 -> 271)
-                        k_vv_y_fwd1s<8><<<dim3(a.pitch / WAVE, np), 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
-                    else if (lone)
-                        k_vv_y_fwd1<<<dim3(a.pitch / WAVE, np), 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
-                    else
-                        k_vv_y_fwd<<<g, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
-                }
-                StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
-                // loader + two chains + four consumers, free-running (k_vv_y_bwd_dec7) where the launch leaves SIMDs idle; the two-wavefront
-                // kernel otherwise
-                const bool dec7 = lone && small_plane && p->tune.dec7 != 0 && !zt.flags;
-                if (zt.flags && ((a.w & 1) == 0 || odd_dec) && !p->no_fuse) {  // (zero-tile flags from k_vv_xby_m: the kernels that read them)
-                    if ((a.w & 1) == 0) {
-                        if (rowz)
-                            k_vv_y_bwd_dec<true><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
-                        else
-                            k_vv_y_bwd_dec<false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
-                    } else {
-                        const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
-                        if (rowz)
-                            k_vv_y_bwd_dec<true, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
-                        else
-                            k_vv_y_bwd_dec<false, YST, true, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h);
-                    }
-                    decimated = true;
-                } else if ((a.w & 1) == 0 && !p->no_fuse) {  // even width: decimation fused into the anticausal pass
-                    if (dec7) {
-                        unsigned long long* dbg = p->d7_dbg && l == p->d7_dbg_level ? p->d7_dbg : nullptr;
-                        if (dbg) p->d7_dbg_chunks = (a.h + YCH - 1) / YCH;
-                        k_vv_y_bwd_dec7<false><<<g, D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, dbg, dbg ? Tuning::env_int("STITCH_D7_STAMP_MODE") : 0);
-                    }
-                    else
-                        k_vv_y_bwd_dec<false, YST, false><<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, ZeroTiles{}, nullptr, nullptr, a.h, b.h);
-                    decimated = true;
-                } else if (odd_dec) {
-                    const dim3 go((b.w + WAVE - 2) / (WAVE - 1), np);
-                    if (dec7)
-                        k_vv_y_bwd_dec7<true><<<go, D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps);
-                    else
-                        k_vv_y_bwd_dec<false, YST, false, true><<<go, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, ZeroTiles{}, nullptr, nullptr, a.h, b.h);
-                    decimated = true;
-                } else
-                    k_vv_y_bwd<<<g, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, ystate, nullptr, nullptr);
-            }
-        } else {
+        if (f.mask_l0) mk = MaskL0{p->d_seam, p->side, a.h, 1};
+        const ZeroTiles none{};
+        const ZeroTiles zt = f.zt ? ZeroTiles{p->zt, a.h, f.NR, f.NC} : none;
+        // G column flags and row-repeat flags of the mask plane: of this level for its readers, of the next for the sweep that produces them
+        const ZeroTiles gin = f.g_in ? g_cols(p->gz[l - 1], a.w) : none, gout = f.g_out ? g_cols(p->gz[l], b.w) : none;
+        const ZeroTiles min_ = f.mr_in ? mask_rows(p->mr[l - 1], a.w, a.h) : none, mout = f.mr_out ? mask_rows(p->mr[l], b.w, b.h) : none;
+        const Bands bd = f.per_plane ? Bands{f.NR, a.h} : Bands{};
+        const int xstage = f.src0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD;
+        // the x-sweep state lives in state[0 .. 4*lines); the y state a fused sweep leaves goes behind it
+        double* state_y = p->state + 4 * (size_t)p->cap * 7 * (a.h + 64);
+        const double* ystate = f.sweep == SW_BATCH || f.xby ? state_y : p->state;  // where the causal y sweep leaves its state for the anticausal one
+        const dim3 gy((a.pitch + YCOLS - 1) / YCOLS, np), gy1(a.pitch / WAVE, np);
+
+        if (f.x_fwd == XF_COPY)
             HIPCHK(hipMemcpyAsync(p->T, a.g, sizeof(float) * a.ps * np, hipMemcpyDeviceToDevice, s));
-            if (do_x) {
-                StageTimer t(p, s, src && l == 0 ? STITCH_K_VV_X_FWD_SRC : STITCH_K_VV_X_FWD, l);
+        else {
+            StageTimer t(p, s, xstage, l);
+            if (f.x_fwd == XF_M) {
+                if (f.src0)
+                    k_vv_x_m<true, PX, true><<<f.nbx, 192, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, pa);
+                else
+                    k_vv_x_m<true><<<f.nbx, 192, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, NoPairArgs{});
+            } else if (f.src0) {
+                if (f.rcmp)
+                    k_vv_x_fwd<PX, true, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, p->ckpt, bd);
+                else
+                    k_vv_x_fwd<PX, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
+            } else if (f.rcmp)
+                k_vv_x_fwd<PX, false, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, none, p->ckpt, bd);
+            else
+                k_vv_x_fwd<PX, false><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, gin, nullptr, bd, min_);
+        }
+        if (f.x_bwd != XB_NONE || f.x_fwd == XF_M) {  // (the stage is timed behind k_vv_x_m even where the fused sweep takes its work)
+            StageTimer t(p, s, STITCH_K_VV_X_BWD, l);
+            if (f.x_bwd == XB_M)
+                k_vv_x_m<false><<<f.nbx, 192, 0, s>>>(p->T, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd, NoPairArgs{});
+            else if (f.x_bwd == XB_BWD)
+                k_vv_x_bwd<<<f.nbx, 64, 0, s>>>(p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, bd);
+        }
+        int fill_l0 = 0;
+        if (f.sweep == SW_BATCH) {
+            Wavefront wf = wavefront_of(p, l, np, f, zt, s);
+            wf.mask_l0 = f.mask_l0 ? (f.zt ? 2 : 1) : 0;  // 2: the mask blur below the first band is recorded in the flags, not stored
+            if (f.fill_mask && l > 0) wf.mr = min_;
+            fill_l0 = f.fill_mask;  // flagged tiles of the mask planes repeat the plane's row 0
+            StageTimer t(p, s, STITCH_K_VV_XBYF, l);
+            const int wg = (int)std::min<long>((long)wf.NP * wf.NR, p->wf_max_wgs);  // one persistent wavefront per row band; at most 9 workgroups per CU by LDS
+            Recompute rcv{};
+            if (f.rcmp) {
+                rcv.in = a.g;
+                rcv.ckpt = p->ckpt;
+                rcv.seam = p->d_seam;
+                if (f.src0) rcv.zi = zi;
+            }
+            if (f.stamp) {  // diagnostic build: per-segment cycle sums of the level-0 launch
+                wf.dbg = p->wf_dbg;
+                k_vv_xbyf<true><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
+            } else if (f.rcmp && f.src0)
+                k_vv_xbyf<false, PX, 2><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, pa);
+            else if (f.rcmp)
+                k_vv_xbyf<false, float, 1><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
+            else
+                k_vv_xbyf<false><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
+        } else if (f.xby) {
+            Wavefront wf = wavefront_of(p, l, np, f, zt, s);
+            wf.mask_l0 = f.mask_l0;
+            if (p->xy_dbg && l == 0) wf.dbg = p->xy_dbg, p->xy_dbg_nc = wf.NC;
+            StageTimer t(p, s, STITCH_K_VV_XBYF, l);
+            // two workgroups per CU by LDS: every band of a lone 6144 x 4096 pair (448) is resident at once
+            k_vv_xby_m<<<(int)std::min<long>((long)wf.NP * wf.NR, XY_WGS), XY_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, p->zero_page);
+        } else if (f.sweep == SW_DERICHE) {
+            if (f.do_x) {
+                StageTimer t(p, s, xstage, l);
                 k_deriche<<<(int)((lines + 63) / 64), 64, 0, s>>>(p->T, p->T2, a.w, 1, a.pitch, a.h, a.ps, lines, p->drk);
             }
-            if (do_y) {
+            if (f.do_y) {
                 StageTimer t(p, s, STITCH_K_VV_Y_FWD, l);
                 const long cols = (long)np * a.w;
                 k_deriche<<<(int)((cols + 63) / 64), 64, 0, s>>>(p->T, p->T2, a.h, a.pitch, 1, a.w, a.ps, cols, p->drk);
             }
         }
-        if (!decimated) {
+        if (f.y_fwd != YF_NONE) {
+            StageTimer t(p, s, STITCH_K_VV_Y_FWD, l);
+            if (f.y_fwd == YF_M)
+                k_vv_y_m<true><<<gy1, 192, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk);
+            else if (f.y_fwd == YF_FWD1S)
+                k_vv_y_fwd1s<8><<<gy1, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
+            else if (f.y_fwd == YF_FWD1)
+                k_vv_y_fwd1<<<gy1, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
+            else
+                k_vv_y_fwd<<<gy, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, p->state, mk, nullptr);
+        }
+        if (f.y_bwd != YB_NONE) {
+            StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
+            if (f.y_bwd == YB_DEC)
+                launch_y_bwd_dec(p, f, np, s, a, b, ystate, zt, fill_l0, gout, mout);
+            else if (f.y_bwd == YB_BWD)
+                k_vv_y_bwd<<<gy, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, ystate, nullptr, nullptr);
+            else if (f.dec_odd)
+                k_vv_y_bwd_dec7<true><<<dim3((b.w + WAVE - 2) / (WAVE - 1), np), D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps);
+            else {
+                unsigned long long* dbg = p->d7_dbg && l == p->stamp_d7_level ? p->d7_dbg : nullptr;
+                if (dbg) p->d7_dbg_chunks = (a.h + YCH - 1) / YCH;
+                k_vv_y_bwd_dec7<false><<<gy, D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, dbg, dbg ? Tuning::env_int("STITCH_D7_STAMP_MODE") : 0);
+            }
+        }
+        if (f.decimate) {
             StageTimer t(p, s, STITCH_K_DECIMATE, l);
             k_decimate<<<grid_xy(b.pitch, b.h, np), 256, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, b.g, b.w, b.h, b.pitch, b.ps, 0, 0);
         }
     }
-    if (p->coarse_from > 0) {  // every remaining level in one launch, one workgroup per pair; leaves E of level coarse_from
+    if (c.coarse) {  // every remaining level in one launch, one workgroup per pair; leaves E of level coarse_from
         StageTimer t(p, s, STITCH_K_COARSE, p->coarse_from);
         CoarseArgs ca{};
         ca.n = p->L - p->coarse_from;
@@ -750,79 +454,42 @@ int run_reduce(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, boo
         ca.T = p->T;
         ca.k = p->vvk;
         ca.dbg = p->co_dbg;
-        // every level in LDS where they fit (k_coarse_lds): G of all levels, the blur scratch, the collapse chain; rows pitched odd
-        CoarseLds lo{};
-        int fl = 0, tabs_w = 0, tabs_h = 0;
-        for (int i = 0; i < ca.n; ++i) {
-            lo.p[i] = ca.lv[i].w | 1;
-            lo.g[i] = fl;
-            fl += 7 * ca.lv[i].h * lo.p[i];
-            lo.e[i] = fl;
-            fl += 3 * ca.lv[i].h * lo.p[i];
-            if (i + 1 < ca.n) tabs_w += ca.lv[i].w, tabs_h += ca.lv[i].h;
-        }
-        lo.t = fl;
-        fl += 7 * ca.lv[0].h * lo.p[0];
-        const size_t lds_bytes = sizeof(float) * (size_t)fl;
-        if (p->tune.coarse_lds != 0 && !p->co_dbg && lds_bytes <= CO_LDS_BYTES && tabs_w <= CO_TABN && tabs_h <= CO_TABN) {
+        if (c.coarse_lds) {
+            CoarseLds lo{};
+            bool fits;
+            const size_t lds_bytes = sizeof(float) * coarse_lds_layout(*p, lo.p, lo.g, lo.e, &lo.t, &fits);
             static std::once_flag once;  // more than 64 KB of dynamic LDS is opt-in per function
             std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_coarse_lds), hipFuncAttributeMaxDynamicSharedMemorySize, CO_LDS_BYTES); });
             k_coarse_lds<<<n, CO_THREADS, lds_bytes, s>>>(ca, lo);
         } else
             k_coarse<<<n, CO_THREADS, 0, s>>>(ca);
     }
-    if (p->wf_levels > 0 || any_lone_fused) HIPCHK(hipMemcpyAsync(p->h_wf_abort, p->wf_ctrl + WF_CTRL_WORDS, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (c.wf_ctrl) HIPCHK(hipMemcpyAsync(p->h_wf_abort, p->wf_ctrl + WF_CTRL_WORDS, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     return launch_check("reduce");
 }
 
-// Rows per strip of the collapse of level l in a call with n pairs.  A strip is one serial chain of rows per work-item (load -> arithmetic ->
-// store, one row after the other) and re-uses the x-interpolated source rows best when it is long: 32 rows wherever the launch has
-// workgroups enough to hide that chain behind each other -- every batch.  A launch with few workgroups lives on the chains alone: the
-// strip of a ONE-pair call is halved until the launch has STITCH_CROWS_WGS workgroups (default 8192; 0 = round 3's rule: by the level's height alone) or
-// is 4 rows high (one pair in flight, 6144 x 4096: level 0 32 -> 8 rows, levels >= 1 32 -> 4: 2.41 -> 2.33 ms; 4421 x 2315 1.30 -> 1.25;
-// the rows two strips share are read once more per halving, which a lone pair does not notice).  STITCH_CROWS_L0 / _LN pin the height.
-int crows_of(const stitch_plan* p, int l, int n) {
-    const Level& a = p->lv[l];
-    int c;
-    if (l == 0) {
-        if (p->tune.crows_l0 >= 0) return p->crows_l0;
-        c = a.h >= 2048 ? p->crows_l0 : a.h >= 1024 ? 16 : 8;
-    } else {
-        if (p->crows_ln > 0) return p->crows_ln;
-        c = std::max(4, std::min(4 * CROWS, a.h / 32));
-    }
-    const long want = p->tune.crows_wgs >= 0 ? p->tune.crows_wgs : 8192;
-    const long blocks = std::max(1, (a.c4_xb - a.c4_xa) / 256);
-    // (one pair per call only: a batch has other workgroups to run meanwhile, and with four 4-pair sequences in flight shorter strips
-    // measured 5 % slower, scripts/experiments/r4_run36.sh)
-    while (n == 1 && c > 4 && blocks * ((a.h + c - 1) / c) < want) c /= 2;
-    return c;
-}
-
 template <typename OUT>
-int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s, const PairArgs<OUT>& pa, bool src) {
-    const int L = p->L;
-    if (p->coarse_from == 0) {
+int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hipStream_t s, const PairArgs<OUT>& pa) {
+    const int L = p->L, n = c.n;
+    if (!c.coarse) {
         const Level& t = p->lv[L - 1];
         StageTimer tm(p, s, STITCH_K_COLLAPSE_TOP, L - 1);
         k_blend_top<<<grid_xy(t.pitch, t.h, n), 256, 0, s>>>(t.g, t.pitch, t.h, t.ps, t.e);
         if (L == 1) k_emit_top<OUT><<<grid_xy(t.w, t.h, n), 256, 0, s>>>(t.e, t.w, t.h, t.pitch, t.ps, outs);  // writes out_u8 too
     }
     // with k_coarse the chain arrives collapsed down to level coarse_from
-    for (int l = (p->coarse_from > 0 ? p->coarse_from - 1 : L - 2); l >= 0; --l) {
+    for (int l = c.l_end - 1; l >= 0; --l) {
+        const LevelForm& f = c.lv[l];
         const Level& a = p->lv[l];
         const Level& nx = p->lv[l + 1];
         StageTimer tm(p, s, l == 0 ? STITCH_K_COLLAPSE_L0 : STITCH_K_COLLAPSE, l);
-        const ZeroTiles gz = g_flags_call(p, n, l), gzn = g_flags_call(p, n, l + 1);  // G column flags of this level and of the one it expands
-        const ZeroTiles mrz = mask_rows_call(p, n, l);  // row-repeat flags of this level's mask plane
-        if ((mrz.flags != nullptr) != (l >= 1 && l <= 2 && p->mr_last[l - 1]))
-            return fail(STITCH_ERR_ARG, "collapse: mask row flags of level %d decided otherwise than in the reduce", l);
-        // four columns per work-item on the column range whose taps follow the regular pattern (Level::c4_xa, c4_xb), one
-        // column per work-item on the rest, in ONE launch (k_collapse4); levels without such a range run k_collapse
-        int xa = 0, xb = 0;
-        if (p->collapse4) xa = a.c4_xa, xb = a.c4_xb;
+        // G column flags of this level and of the one it expands, row-repeat flags of this level's mask plane
+        const ZeroTiles none{};
+        const ZeroTiles gz = f.g_in ? g_cols(p->gz[l - 1], a.w) : none, gzn = f.g_out ? g_cols(p->gz[l], nx.w) : none;
+        const ZeroTiles mrz = f.c_mr ? mask_rows(p->mr[l - 1], a.w, a.h) : none;
+        int xa = f.xa, xb = f.xb;
         int u8_words = 1;  // level 0: unsigned char rows start on 32-bit boundaries
-        if (l == 0) {
+        if (l == 0) {      // what the caller's addresses take away from the record
             u8_words = (a.w % 4) == 0;
             for (int i = 0; i < n; ++i) {
                 if (sizeof(OUT) == 1) u8_words = u8_words && (reinterpret_cast<uintptr_t>(outs.p[i]) % 4) == 0;
@@ -832,19 +499,19 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
         }
         const int cols = l == 0 ? a.w : a.pitch, rest = cols - (xb - xa);
         const int nb4 = ((xb - xa) / 4 + WAVE - 1) / WAVE, ncb = (rest + C4_THREADS - 1) / C4_THREADS;
+        const int strips = (a.h + f.crows - 1) / f.crows;
+        const dim3 g4(c4_padded_blocks(nb4, c.c4_swizzle) + ncb * C4_SUB, strips, n);
         if (l == 0) {  // level 0: the mask is the seam's step function itself (never read from memory)
             CollapseArgs<OUT, true> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, outs,
-                                      a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, src ? 1 : 0, crows_of(p, 0, n), xa, xb, u8_words,
-                                      std::max(0, p->tune.c4_lock), p->tune.c4_swz < 0 ? 1 : p->tune.c4_swz};
+                                      a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, c.src ? 1 : 0, f.crows, xa, xb, u8_words,
+                                      c.c4_lock, c.c4_swizzle};
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
-            const int strips = (a.h + A.crows - 1) / A.crows;
-            const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n);
-            const bool gen = a.c4_gen && p->collapse4;
-            if (xb > xa && src && pa.a_dense && gen)
+            const bool dense = c.src && c.a_dense;
+            if (xb > xa && dense && f.gen)
                 k_collapse4<OUT, true, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa && src && pa.a_dense)
+            else if (xb > xa && dense)
                 k_collapse4<OUT, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa && gen)
+            else if (xb > xa && f.gen)
                 k_collapse4<OUT, true, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
             else if (xb > xa)
                 k_collapse4<OUT, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
@@ -854,27 +521,24 @@ int run_collapse(stitch_plan* p, int n, const OutPtrs<OUT>& outs, hipStream_t s,
             OutPtrs<float> eo{};
             eo.p[0] = a.e;
             CollapseArgs<float, false> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, eo,
-                                         a.pitch, a.ps, nullptr, NoPairArgs{}, 0, crows_of(p, l, n), xa, xb, 1, std::max(0, p->tune.c4_lock), p->tune.c4_swz < 0 ? 1 : p->tune.c4_swz};
+                                         a.pitch, a.ps, nullptr, NoPairArgs{}, 0, f.crows, xa, xb, 1, c.c4_lock, c.c4_swizzle};
             A.gz = gz.flags, A.gnc = gz.NC, A.zo = (unsigned)(7 * (size_t)p->cap * a.ps);
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
             const MaskRowsArg mra{mrz.flags, mrz.NC, mrz.NR};
-            const bool px = (long)n * a.pitch * a.h <= 4096L * 64 * 2 && p->tune.collapse_px != 0;  // a launch that leaves most SIMDs with at most a wavefront or two
-            const int strips = (a.h + A.crows - 1) / A.crows;
-            const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n);
-            if (mrz.flags) {  // the instances that take the mask sample of a flagged tile from row 0
-                if (xb > xa && a.c4_gen && p->collapse4)
+            if (f.c_mr) {  // the instances that take the mask sample of a flagged tile from row 0
+                if (xb > xa && f.gen)
                     k_collapse4<float, false, false, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
                 else if (xb > xa)
                     k_collapse4<float, false, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
-                else if (px)
+                else if (f.px)
                     k_collapse_px<true><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A, mra);
                 else
                     k_collapse<float, false, true><<<grid_xy(cols, strips, n), 256, 0, s>>>(A, mra);
-            } else if (xb > xa && a.c4_gen && p->collapse4)
+            } else if (xb > xa && f.gen)
                 k_collapse4<float, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
             else if (xb > xa)
                 k_collapse4<float, false><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (px)
+            else if (f.px)
                 k_collapse_px<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A);
             else
                 k_collapse<float, false><<<grid_xy(cols, strips, n), 256, 0, s>>>(A);
@@ -913,34 +577,13 @@ int check_plan_call(stitch_plan* p, const void* a, const void* b, const void* ou
     return STITCH_OK;
 }
 
-// Source fusion trades bytes for instructions: the consumers of level 0 gather their samples (64 four-byte gathers per lane and
-// tile in the causal x sweep) instead of streaming planes.  A launch sequence over several pairs is bound by the bytes it moves
-// and gains (12 % at config 2); ONE pair in flight is bound by the length of its recurrence chains, its sweeps have a SIMD to
-// themselves, and the gathers land on the critical path: measured at 4421 x 2315 / 1081 x 527, materialised S1 2.14 / 0.81 ms,
-// source-fused 2.27 / 0.84 ms per pair.  So the form is chosen per CALL: source-fused for launch sequences with enough canvas
-// in them, materialised (k_compose / k_load_canvases; the implicit mask stays) otherwise.  STITCH_SINGLE_FAST=1 pins the fused
-// forms everywhere (A/B runs, tests).
-// Measured per launch sequence of n pairs, 1 and 4 sequences in flight (scripts/experiments/exp_srcfuse_n.py, ms per pair, fused /
-// materialised): 1081 x 527: n = 2 0.255 / 0.239, n = 8 0.053 / 0.047 (4 in flight), n = 16 0.040 / 0.046; 4421 x 2315: n = 2
-// 0.597 / 0.858 (4 in flight), n = 8 0.500 / 0.588.  The fused form pays from about 8 MPix of canvas per launch sequence.
-// (A lone pair that is large enough to fill the chip by itself -- 7 planes x 64-row bands >= 800, the fused sweep's own criterion:
-// config 5's 24576 x 16384 -- is a throughput case too: 23.5 ms source-fused against 25.9 ms materialised.)
-bool src_fused_call(const stitch_plan* p, int n) {
-    if (p->tune.single_fast > 0) return true;
-    if (7L * ((p->lv[0].h + TS - 1) / TS) >= 800) return true;
-    // (round 4) one pair too: with the gathers on a loader wavefront (k_vv_x_m<.., SRC>) they are off the recurrence's issue stream,
-    // and level 0 of a canvas this size is bound by bytes even alone.  STITCH_SRC_LONE_MPIX moves the threshold (0 = never).
-    const long long lone_px = p->tune.src_lone >= 0 ? 1000000LL * p->tune.src_lone : 8000000LL;
-    if (n == 1) return p->tune.mover != 0 && lone_px > 0 && (long long)p->lv[0].w * p->lv[0].h >= lone_px && p->opts.blur_kind == 0;
-    return (long long)n * p->lv[0].w * p->lv[0].h >= 8000000LL;
-}
-
 // The launch sequence of n pairs (or of one dense-canvas blend, pa.a_dense): S1, seam scan, REDUCE, collapse.
 // given: the pairs' seams as their four integers (stitch_dev_pairs_seamed_*), or nullptr for the scan.
 template <typename PX>
 int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, int n, hipStream_t s, bool src, const SeamInts* given = nullptr) {
     const Level& a = p->lv[0];
     int rc;
+    const CallForm c = call_form(*p, n, src, pa.a_dense != 0);  // every kernel choice of REDUCE and the collapse, before the first launch
     // source-fused: level 0 is a function of the inputs, evaluated by its three consumers (a warped frame through an index
     // plane, dense images as pure shifts)
     ZeroTiles zi{};
@@ -963,8 +606,9 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
             k_compose<PX><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, 0);
     }
     if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given))) return rc;
-    if ((rc = run_reduce<PX>(p, n, s, pa, src, zi))) return rc;
-    if ((rc = run_collapse<PX>(p, n, outs, s, pa, src))) return rc;
+    p->last_form = c;
+    if ((rc = run_reduce<PX>(p, c, s, pa, zi))) return rc;
+    if ((rc = run_collapse<PX>(p, c, outs, s, pa))) return rc;
     p->last_stream = s;
     p->pending = true;
     p->last_n = n;
@@ -995,7 +639,7 @@ int dev_blend(stitch_plan* p, const PX* d_a, const PX* d_b, PX* d_out, void* str
     const size_t bytes = sizeof(PX) * (size_t)3 * p->cw * p->ch;
     // source-fused: a and b are read again by the causal x sweep and by the level-0 collapse WHILE d_out is written, so an output
     // that overlaps an input takes the materialised form (k_load_canvases copies both canvases before anything is written)
-    const bool src = p->src_fuse && src_fused_call(p, 1) && (unsigned long long)p->cw * p->ch * sizeof(PX) < 0xfffffff0ULL &&  // 32-bit byte offsets into a channel plane
+    const bool src = source_fused_call(*p, 1) && (unsigned long long)p->cw * p->ch * sizeof(PX) < 0xfffffff0ULL &&  // 32-bit byte offsets into a channel plane
                      !ranges_overlap(d_out, bytes, d_a, bytes) && !ranges_overlap(d_out, bytes, d_b, bytes);
     return run_pairs<PX>(p, pa, outs, 1, as_stream(stream), src);
 }
@@ -1042,7 +686,7 @@ int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, co
         pa.offx[i] = d[i].offx;
         pa.offy[i] = d[i].offy;
     }
-    bool src = p->src_fuse && src_fused_call(p, n);
+    bool src = source_fused_call(*p, n);
     for (int i = 0; i < n; ++i)  // 32-bit element indices and byte offsets into one channel plane
         src = src && (unsigned long long)d[i].fw * d[i].fh * sizeof(PX) < 0xfffffff0ULL && (unsigned long long)d[i].mw * d[i].mh * sizeof(PX) < 0xfffffff0ULL;
     // source-fused: the frames are read again while the mosaics are written (see dev_blend): no output of the call may overlap an input of it
@@ -1789,6 +1433,7 @@ int stitch_plan_create(int cw, int ch, const stitch_blend_opts* opts, stitch_pla
     return stitch_plan_create_batched(cw, ch, opts, 1, plan_out);
 }
 
+// Fill the shape (plan_shape, stitch_call_form.h), carve one arena for it, upload the resize tables.
 int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, stitch_plan** plan_out) {
     if (!plan_out) return fail(STITCH_ERR_ARG, "plan_create: null plan_out");
     if (max_pairs < 1 || max_pairs > MAXB) return fail(STITCH_ERR_ARG, "plan_create: max_pairs must be 1..%d", MAXB);
@@ -1801,23 +1446,19 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     if (o.blur_kind < 0 || o.blur_kind > 1 || o.level_rule < 0 || o.level_rule > 1 || o.seam_rule < 0 || o.seam_rule > 1 ||
         !(o.sigma >= 0))
         return fail(STITCH_ERR_ARG, "plan_create: bad blend options");
-    int lw[32], lh[32];
-    const int L = pyramid_levels(cw, ch, o.level_rule, lw, lh);
+    const int L = pyramid_levels(cw, ch, o.level_rule, nullptr, nullptr);
     if (L < 0) return L;
 
     stitch_plan* p = new stitch_plan();
-    p->cw = cw;
-    p->ch = ch;
-    p->L = L;
-    p->cap = max_pairs;
+    const Tuning tn = Tuning::from_env();
+    StampRequest stamps;
+    stamps.xy = std::getenv("STITCH_XBYM_STAMP") != nullptr;
+    stamps.co = std::getenv("STITCH_COARSE_STAMP") != nullptr;
+    if (std::getenv("STITCH_D7_STAMP")) stamps.d7_level = atoi(std::getenv("STITCH_D7_STAMP"));
+    plan_shape(*p, cw, ch, o, max_pairs, tn, stamps);
     const size_t B = (size_t)max_pairs;
-    p->opts = o;
     p->vvk = make_vvk(o.sigma);
     p->drk = make_drk(o.sigma);
-    const Tuning tn = Tuning::from_env();
-    p->tune = tn;
-    p->no_fuse = tn.no_fuse != 0;
-    p->blur_skip = o.blur_kind == 0 ? (o.sigma < 0.5f) : (o.sigma < 0.1f);  // CImg.h:35051 / :34800
     if (hipGetDevice(&p->device) != hipSuccess) {
         delete p;
         return fail(STITCH_ERR_HIP, "hipGetDevice failed");
@@ -1831,11 +1472,7 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     };
     size_t g_off[32], e_off[32], ix_off[32], ax_off[32], iy_off[32], ay_off[32];
     for (int l = 0; l < L; ++l) {
-        Level& v = p->lv[l];
-        v.w = lw[l];
-        v.h = lh[l];
-        v.pitch = level_pitch(v.w, tn.pitch_pad);
-        v.ps = (size_t)v.pitch * v.h;
+        const Level& v = p->lv[l];
         g_off[l] = take(sizeof(float) * (v.ps * 7 * B + (size_t)v.pitch * 64));
         e_off[l] = l >= 1 || L == 1 ? take(sizeof(float) * v.ps * 3 * B) : 0;
         if (l + 1 < L) {
@@ -1849,32 +1486,16 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     const size_t t_bytes = sizeof(float) * (v0.ps * 7 * B + (size_t)v0.pitch * 64);
     const size_t t_off = take(t_bytes);
     const size_t t2_off = o.blur_kind == 1 ? take(t_bytes) : 0;
-    // wavefront sweep: enabled with STITCH_WAVEFRONT=<levels> (Van Vliet only); granule buffers sized for level 0
-    int wf_levels = 0;
-    if (tn.wavefront >= 0)
-        wf_levels = std::min(4, tn.wavefront);
-    else if (max_pairs >= 2 || 7L * ((lh[0] + TS - 1) / TS) >= 800)
-        // auto: the band pipeline pays where a launch has many bands in flight (planes x 64-row bands of level 0: 896 for two
-        // 6144x4096 pairs, 1792 for one 24576x16384 pair) to hide its fill (bands x hand-off latency) and the levels have
-        // enough tiles to stream; a lone 6144x4096 pair (448 bands) is faster unfused
-        while (wf_levels < 2 && wf_levels < L - 1 && lw[wf_levels] >= 1024 && lh[wf_levels] >= 1024) ++wf_levels;
-    if (o.blur_kind != 0 || tn.no_fuse || o.sigma < 0.5f) wf_levels = 0;
-    wf_levels = std::min(wf_levels, L - 1);
-    while (wf_levels > 0 && (lw[wf_levels - 1] < 2 || lh[wf_levels - 1] < 2)) --wf_levels;
-    const int NC0 = (v0.w + TS - 1) / TS;
-    // (a plan without fused-sweep levels keeps them for k_vv_xby_m: one pair in flight, from STITCH_XBYM_MPIX megapixels per level)
-    const bool wf_alloc = wf_levels > 0 || (o.blur_kind == 0 && !tn.no_fuse && o.sigma >= 0.5f && L >= 2);
-    const size_t yg_off = wf_alloc ? take(sizeof(u64) * B * 7 * NC0 * WF_GRAN * WAVE) : 0;
-    const size_t wfc_off = wf_alloc ? take(sizeof(unsigned) * (WF_CTRL_WORDS + WF_STICKY_WORDS)) : 0;
-    const size_t zi_off = take((size_t)B * ((v0.h + TS - 1) / TS) * ((v0.w + TS - 1) / TS));
-    const size_t zt_off = wf_levels ? take((size_t)7 * B * ((v0.h + TS - 1) / TS) * ((v0.w + TS - 1) / TS)) : 0;
-    size_t gz_off[2] = {0, 0};  // G column flags of levels 1 and 2
-    for (int i = 0; i < 2; ++i) gz_off[i] = wf_levels && i + 1 < L ? take((size_t)7 * B * ((lw[i + 1] + TS - 1) / TS)) : 0;
-    size_t mr_off[2] = {0, 0};  // row-repeat flags of the mask plane of levels 1 and 2
-    for (int i = 0; i < 2; ++i) mr_off[i] = wf_levels && i + 1 < L ? take((size_t)B * ((lw[i + 1] + TS - 1) / TS) * ((lh[i + 1] + TS - 1) / TS)) : 0;
-    int recompute = 0;  // opt-in: level 0 re-run from the frames measured 3 % slower, the plane levels within noise
-    if (tn.recompute >= 0) recompute = wf_levels > 0 ? std::min(2, tn.recompute) : 0;
-    const size_t ck_off = recompute ? take(sizeof(double) * 3 * NC0 * 7 * B * (size_t)(v0.h + 64)) : 0;
+    const int NC0 = tiles(v0.w), NR0 = tiles(v0.h);
+    // hand-off granules, sized for level 0
+    const size_t yg_off = p->has_wf ? take(sizeof(u64) * B * 7 * NC0 * WF_GRAN * WAVE) : 0;
+    const size_t wfc_off = p->has_wf ? take(sizeof(unsigned) * (WF_CTRL_WORDS + WF_STICKY_WORDS)) : 0;
+    const size_t zi_off = take((size_t)B * NR0 * NC0);
+    const size_t zt_off = p->has_zt ? take((size_t)7 * B * NR0 * NC0) : 0;
+    size_t gz_off[2] = {0, 0}, mr_off[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) gz_off[i] = p->has_gz[i] ? take((size_t)7 * B * tiles(p->lv[i + 1].w)) : 0;
+    for (int i = 0; i < 2; ++i) mr_off[i] = p->has_mr[i] ? take((size_t)B * tiles(p->lv[i + 1].w) * tiles(p->lv[i + 1].h)) : 0;
+    const size_t ck_off = p->recompute ? take(sizeof(double) * 3 * NC0 * 7 * B * (size_t)(v0.h + 64)) : 0;
     // x-sweep state [4][lines] followed by the y state the wavefront kernel leaves [4][planes][pitch]
     const size_t state_n = 4 * 7 * B * (size_t)(v0.h + 64) + 4 * 7 * B * (size_t)std::max(v0.h + 64, v0.pitch);
     const size_t st_off = take(sizeof(double) * state_n);
@@ -1903,73 +1524,34 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     p->T2 = o.blur_kind == 1 ? reinterpret_cast<float*>(base + t2_off) : nullptr;
     p->state = reinterpret_cast<double*>(base + st_off);
     p->d_seam = reinterpret_cast<SeamDev*>(base + seam_off);
-    p->wf_levels = wf_levels;
-    if (wf_alloc) {
+    p->side = reinterpret_cast<float*>(base + side_off);
+    p->zero_page = reinterpret_cast<const float*>(base + zp_off);
+    if (p->has_wf) {
         p->wf_yg = reinterpret_cast<u64*>(base + yg_off);
         p->wf_yg_bytes = sizeof(u64) * B * 7 * NC0 * WF_GRAN * WAVE;
         p->wf_ctrl = reinterpret_cast<unsigned*>(base + wfc_off);
         if (tn.xbyf_spin_limit >= 0) p->wf_spin_limit = (unsigned)tn.xbyf_spin_limit;
     }
-    if (std::getenv("STITCH_D7_STAMP")) {
-        p->d7_dbg_level = atoi(std::getenv("STITCH_D7_STAMP"));
-        const size_t nb = sizeof(unsigned long long) * (7 * ((size_t)(v0.h + YCH - 1) / YCH + 1) + 8);
-        if (hipMalloc((void**)&p->d7_dbg, nb) != hipSuccess || hipMemset(p->d7_dbg, 0, nb) != hipSuccess) {
-            (void)hipGetLastError();
-            p->d7_dbg = nullptr;
-        }
-    }
-    if (wf_alloc && std::getenv("STITCH_XBYM_STAMP") &&
-        (hipMalloc((void**)&p->xy_dbg, sizeof(unsigned long long) * 5 * NC0) != hipSuccess || hipMemset(p->xy_dbg, 0, sizeof(unsigned long long) * 5 * NC0) != hipSuccess)) {
-        (void)hipGetLastError();
-        p->xy_dbg = nullptr;
-    }
-    if (wf_levels) {
+    if (p->has_zt) {
         p->zt = reinterpret_cast<uint8_t*>(base + zt_off);
         p->zi = reinterpret_cast<uint8_t*>(base + zi_off);
-        for (int i = 0; i < 2; ++i) p->gz[i] = i + 1 < L ? reinterpret_cast<uint8_t*>(base + gz_off[i]) : nullptr;
-        for (int i = 0; i < 2; ++i) p->mr[i] = i + 1 < L ? reinterpret_cast<uint8_t*>(base + mr_off[i]) : nullptr;
-        p->recompute = recompute;
-        if (recompute) p->ckpt = reinterpret_cast<double*>(base + ck_off);
+        for (int i = 0; i < 2; ++i) p->gz[i] = p->has_gz[i] ? reinterpret_cast<uint8_t*>(base + gz_off[i]) : nullptr;
+        for (int i = 0; i < 2; ++i) p->mr[i] = p->has_mr[i] ? reinterpret_cast<uint8_t*>(base + mr_off[i]) : nullptr;
+        if (p->recompute) p->ckpt = reinterpret_cast<double*>(base + ck_off);
         if (tn.xbyf_wgs >= 0) p->wf_max_wgs = std::max(1, tn.xbyf_wgs);
-        if (tn.xbyf_spin_limit >= 0) p->wf_spin_limit = (unsigned)tn.xbyf_spin_limit;
-        // diagnostic build: one record per persistent workgroup, sized from the workgroup count actually used
-        if (tn.stamp &&
-            (hipMalloc((void**)&p->wf_dbg, sizeof(unsigned long long) * (size_t)p->wf_max_wgs * 8) != hipSuccess ||
-             hipMemset(p->wf_dbg, 0, sizeof(unsigned long long) * (size_t)p->wf_max_wgs * 8) != hipSuccess)) {
-            (void)hipGetLastError();
-            p->wf_dbg = nullptr;
-        }
         if (tn.xbyf_early >= 0) p->wf_early_read = tn.xbyf_early != 0;
-        p->zero_tiles = !tn.no_zero_tiles;  // A/B and tests: move the zeros like any other sample
     }
-    p->side = reinterpret_cast<float*>(base + side_off);
-    p->zero_page = reinterpret_cast<const float*>(base + zp_off);
-    // implicit level-0 mask: needs both Van Vliet sweeps at level 0 (the x sweeps then run per-plane bands, Bands, at any height;
-    // STITCH_GATE64=1 restores the old restriction to heights that are multiples of 64 for A/B runs)
-    p->mask_opt = !p->no_fuse && o.blur_kind == 0 && !p->blur_skip && L >= 2 && v0.w > 1 && v0.h > 1 && !(tn.gate64 && v0.h % 64);
-    {
-        if (tn.crows_l0 >= 0) p->crows_l0 = std::max(1, tn.crows_l0);
-        if (tn.crows_ln >= 0) p->crows_ln = std::max(1, tn.crows_ln);
-        if (tn.collapse4 >= 0) p->collapse4 = tn.collapse4 != 0;
-        p->src_fuse = p->mask_opt && !tn.no_src_fuse;  // STITCH_NO_SRC_FUSE: A/B and tests, keep S1 as its own kernel (k_compose)
-    }
-    // coarse levels in one launch (k_coarse): from the first level l >= 1 whose sides are both at most STITCH_COARSE (default 40;
-    // 0 = never), when at least two levels qualify.  One workgroup -- one CU -- per pair: measured on the reference's 1081 x 527
-    // panorama, the levels from 33 x 16 down take 65 us in k_coarse against 124 us as 31 launches of their own (4.5 us of
-    // start-up each, 15 us for a collapse level), but 67 x 32 already costs more in one CU (the collapse's ~220 double-precision
-    // operations per pixel) than spread over the chip.  Van Vliet only.
-    {
-        const int thr = std::min(tn.coarse >= 0 ? tn.coarse : 40, CO_MAXSIDE);
-        int lc = 1;
-        while (lc < L && std::max(lw[lc], lh[lc]) > thr) ++lc;
-        if (thr > 0 && o.blur_kind == 0 && !p->blur_skip && lc <= L - 2 && L - lc <= CO_MAXL) p->coarse_from = lc;
-        if (p->coarse_from && std::getenv("STITCH_COARSE_STAMP") &&
-            (hipMalloc((void**)&p->co_dbg, sizeof(unsigned long long) * CO_MAXL * 8) != hipSuccess ||
-             hipMemset(p->co_dbg, 0, sizeof(unsigned long long) * CO_MAXL * 8) != hipSuccess)) {
-            (void)hipGetLastError();
-            p->co_dbg = nullptr;
-        }
-    }
+    // the diagnostic stamp buffers the shape asks for; one that cannot be had is struck from the shape
+    auto stamp_buffer = [](unsigned long long** d, size_t words) {
+        if (hipMalloc((void**)d, sizeof(unsigned long long) * words) == hipSuccess && hipMemset(*d, 0, sizeof(unsigned long long) * words) == hipSuccess) return true;
+        (void)hipGetLastError();
+        *d = nullptr;
+        return false;
+    };
+    if (std::getenv("STITCH_D7_STAMP")) stamp_buffer(&p->d7_dbg, 7 * ((size_t)(v0.h + YCH - 1) / YCH + 1) + 8);
+    if (p->stamp_xy) p->stamp_xy = stamp_buffer(&p->xy_dbg, (size_t)5 * NC0);
+    if (p->stamp_wf) p->stamp_wf = stamp_buffer(&p->wf_dbg, (size_t)p->wf_max_wgs * 8);  // one record per persistent workgroup, sized from the workgroup count actually used
+    if (p->stamp_co) p->stamp_co = stamp_buffer(&p->co_dbg, (size_t)CO_MAXL * 8);
     // the slack rows and pitch padding are read by partial tiles: give them defined (zero) contents once
     if (hipMemset(p->arena, 0, off) != hipSuccess || hipHostMalloc((void**)&p->h_seam, sizeof(SeamDev) * B) != hipSuccess) {
         stitch_plan_destroy(p);
@@ -1983,18 +1565,10 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
         Level& v = p->lv[l];
         std::vector<int32_t> idx;
         std::vector<double> al;
-        expand_table(lw[l + 1], v.w, idx, al);
-        regular_range(idx, v.w, lw[l + 1], lh[l + 1], &v.c4_xa, &v.c4_xb);
-        {
-            int gxb = 0;
-            general_range(idx, v.w, lw[l + 1], lh[l + 1], &gxb);
-            // STITCH_C4_GEN: 0 never, 1 where it gains two blocks or more, 2 / unset wherever it gains a block
-            v.c4_gen = tn.c4_gen != 0 && gxb >= (v.c4_xb - v.c4_xa) + (tn.c4_gen == 1 ? 512 : 256);
-            if (v.c4_gen) v.c4_xa = 0, v.c4_xb = gxb;
-        }
+        expand_table(p->lv[l + 1].w, v.w, idx, al);
         (void)hipMemcpy(v.ix, idx.data(), sizeof(int32_t) * v.w, hipMemcpyHostToDevice);
         (void)hipMemcpy(v.ax, al.data(), sizeof(double) * v.w, hipMemcpyHostToDevice);
-        expand_table(lh[l + 1], v.h, idx, al);
+        expand_table(p->lv[l + 1].h, v.h, idx, al);
         (void)hipMemcpy(v.iy, idx.data(), sizeof(int32_t) * v.h, hipMemcpyHostToDevice);
         if (hipMemcpy(v.ay, al.data(), sizeof(double) * v.h, hipMemcpyHostToDevice) != hipSuccess) {
             stitch_plan_destroy(p);
@@ -2002,7 +1576,7 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
         }
     }
     std::memset(p->h_seam, 0, sizeof(SeamDev) * B);
-    if (wf_alloc) {
+    if (p->has_wf) {
         if (hipHostMalloc((void**)&p->h_wf_abort, sizeof(unsigned)) != hipSuccess) {
             stitch_plan_destroy(p);
             return fail(STITCH_ERR_HIP, "plan_create: pinned allocation failed");
@@ -2032,7 +1606,7 @@ void stitch_plan_destroy(stitch_plan* p) {
             static const char* nm[7] = {"loader", "chain 0", "chain 1", "cons 0", "cons 1", "cons 2", "cons 3"};
             const unsigned long long t0 = h[0];
             std::fprintf(stderr, "[k_vv_y_bwd_dec7 stamps, level %d, %d chunks, middle workgroup of plane 0: ticks since the loader's first chunk, every %d-th chunk; then ticks per chunk over the middle half]\n",
-                         p->d7_dbg_level, nc, std::max(1, nc / 16));
+                         p->stamp_d7_level, nc, std::max(1, nc / 16));
             for (int wv = 0; wv < 7; ++wv) {
                 std::fprintf(stderr, "  %-8s", nm[wv]);
                 const int c0 = wv >= 3 ? wv - 3 : 0, step = wv >= 3 ? 4 : 1;  // consumer c stamps chunks c, c+4, ...
@@ -2181,7 +1755,7 @@ int stitch_plan_g_flag_counts(stitch_plan* p, uint64_t out[2]) {
     }
     for (int i = 0; i < 2; ++i) {
         out[i] = 0;
-        if (!p->gz_last[i] || !p->gz[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
+        if (!p->last_form.lv[i].g_out || !p->gz[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
         std::vector<uint8_t> h((size_t)7 * p->last_n * ((p->lv[i + 1].w + TS - 1) / TS));
         HIPCHK(hipMemcpy(h.data(), p->gz[i], h.size(), hipMemcpyDeviceToHost));
         for (uint8_t f : h) out[i] += f != 0;
@@ -2197,7 +1771,7 @@ int stitch_plan_mask_row_counts(stitch_plan* p, uint64_t out[2]) {
     }
     for (int i = 0; i < 2; ++i) {
         out[i] = 0;
-        if (!p->mr_last[i] || !p->mr[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
+        if (!p->last_form.lv[i].mr_out || !p->mr[i] || p->last_n <= 0) continue;  // (the bytes of a call without flags are an earlier call's)
         const ZeroTiles m = mask_rows(p->mr[i], p->lv[i + 1].w, p->lv[i + 1].h);
         std::vector<uint8_t> h((size_t)p->last_n * m.NC * m.NR);
         HIPCHK(hipMemcpy(h.data(), p->mr[i], h.size(), hipMemcpyDeviceToHost));
@@ -2218,20 +1792,7 @@ int stitch_plan_clear_fault(stitch_plan* p) {
 
 int stitch_plan_capacity(const stitch_plan* p) { return p ? p->cap : 0; }
 int stitch_plan_coarse_from(const stitch_plan* p) { return p ? p->coarse_from : 0; }
-int stitch_plan_fast_paths(const stitch_plan* p) {
-    if (!p) return 0;
-    int f = 0;
-    if (p->mask_opt) f |= STITCH_FAST_IMPLICIT_MASK;
-    if (p->src_fuse) f |= STITCH_FAST_SOURCE_FUSED;
-    if (p->wf_levels > 0) f |= STITCH_FAST_FUSED_SWEEP;
-    if (p->wf_levels > 0 && p->zero_tiles && !p->no_fuse && ((p->lv[0].w & 1) == 0 || (p->lv[0].w >= 3 && p->tune.odd_dec != 0)) &&
-        (p->lv[0].h + TS - 1) / TS <= 256 && !(p->tune.gate64 && (p->lv[0].h % TS || (p->lv[0].w & 1))))
-        f |= STITCH_FAST_ZERO_TILES;
-    if (!p->no_fuse && p->opts.blur_kind == 0 && !p->blur_skip && p->L >= 2 && ((p->lv[0].w & 1) == 0 || (p->lv[0].w >= 3 && p->tune.odd_dec != 0)) && p->lv[0].h > 1)
-        f |= STITCH_FAST_FUSED_DECIMATE;
-    if (p->coarse_from > 0) f |= STITCH_FAST_COARSE_LEVELS;
-    return f;
-}
+int stitch_plan_fast_paths(const stitch_plan* p) { return p ? capability_mask(*p) : 0; }
 int stitch_plan_fused_sweep_levels(const stitch_plan* p) { return p ? p->wf_levels : 0; }
 int stitch_plan_collapse_range(const stitch_plan* p, int level, int* xa, int* xb, int* per_lane_taps) {
     if (!p || level < 0 || level + 1 >= p->L || !xa || !xb || !per_lane_taps) return fail(STITCH_ERR_ARG, "plan_collapse_range: bad argument");
@@ -2243,10 +1804,10 @@ int stitch_plan_collapse_range(const stitch_plan* p, int level, int* xa, int* xb
 }
 int stitch_plan_call_forms(const stitch_plan* p, int n_pairs) {
     if (!p || n_pairs < 1 || n_pairs > p->cap) return 0;
+    const CallForm c = call_form(*p, n_pairs, source_fused_call(*p, n_pairs), false);
     int f = 0;
-    if (p->src_fuse && src_fused_call(p, n_pairs)) f |= STITCH_FAST_SOURCE_FUSED;
-    if (p->wf_levels > 0 && p->opts.blur_kind == 0 && !p->blur_skip && fused_sweep_call(p, n_pairs)) f |= STITCH_FAST_FUSED_SWEEP;
-    if (lone_fused_level(p, n_pairs, 0)) f |= STITCH_FAST_FUSED_SWEEP;  // one pair in flight: k_vv_xby_m
+    if (c.src) f |= STITCH_FAST_SOURCE_FUSED;
+    if (c.lv[0].sweep == SW_BATCH || c.lv[0].xby) f |= STITCH_FAST_FUSED_SWEEP;  // k_vv_xbyf; one pair in flight: k_vv_xby_m
     return f;
 }
 

@@ -15,12 +15,14 @@
 #include <type_traits>
 
 #include "stitch_elem.h"
+#include "stitch_call_form.h"  // the constants kernels and host decisions share (TS, YCH, YCOLS, XY_MAXNC, CROWS, CO_*, MAXB)
 
 #pragma clang fp contract(off)
 
 namespace sk {
 
 constexpr int WAVE = 64;
+static_assert(TS == WAVE, "a tile is as wide as a wavefront");
 typedef float f4 __attribute__((ext_vector_type(4)));  // native 16-byte vector (keeps prefetch arrays in VGPRs)
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
