@@ -1,7 +1,8 @@
 // The pair path's decisions, without HIP: what a plan of a canvas size holds (PlanShape, plan_shape) and which kernels reduce and
 // collapse every level of a call with n pairs (CallForm, call_form).  Plain C++17: the library's host code (stitch_hip.hip) fills the
 // shape, carves its arena from it and launches from the record; tests/call_form_dump.cpp prints the records on a machine without a GPU.
-// Every rule of the path -- a threshold, a condition -- is written ONCE, here.
+// Every rule of the path -- a threshold, a condition -- is written ONCE, here.  The band path's decisions (one pair split into row bands
+// over ranks: BandShape, band_shape, BandForm, band_form) follow at the end of the file, under the same rule.
 //
 // REDUCE of level l (ImageProcess.cpp:705-715) is blur(G_l) into the scratch T, then decimate T into G_{l+1}.  The blur is a causal and
 // an anticausal sweep along x, then along y.  call_form decides in four steps, so that no two places have to reach the same answer:
@@ -45,6 +46,10 @@ constexpr long CHIP_BANDS = 800;            // planes x 64-row bands of level 0 
 constexpr int WF_MIN_SIDE = 1024;           // a level joins the batch's fused sweep from this width and height
 constexpr long Y_LONE_WGS = 1536;           // workgroups of a y sweep below which SIMDs idle (fewer than 1.5 wavefronts each): one column per lane
 constexpr int ZT_MAX_BANDS = 256;           // bands per plane the flag users address
+// ---- defaults of the fused sweep's hand-off (a plan's STITCH_XBYF_WGS / STITCH_XBYF_SPIN_LIMIT move them; a band takes them as they are)
+constexpr int WF_MAX_WGS = 2304;            // persistent workgroups: at most 9 per CU by LDS
+constexpr unsigned WF_SPIN_LIMIT = 1u << 23;  // polls before a hand-off wait gives up, about 20 s; 2^20 (2-3 s) was reached once in a warm-up
+constexpr int BAND_HALO = 2;                // rows of either neighbour a band holds of a level that an EXPAND reads
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int tiles(int v) { return (v + TS - 1) / TS; }
@@ -170,7 +175,9 @@ struct PlanShape {
     Level lv[32]{};
     bool blur_skip = false;  // sigma below the blur's threshold: REDUCE decimates G itself (CImg.h:35051 / :34800)
     bool no_fuse = false;    // STITCH_NO_FUSE=1: keep blur and decimation as separate kernels (A/B and tests)
-    bool planes_in = false;  // level 0 (a, b AND the mask plane) is handed in by the caller (the coarse levels of a band-split pair): no seam scan, no implicit mask
+    // level 0 (a, b AND the mask plane) is handed in by the caller (the coarse levels of a band-split pair): no seam scan, and so neither
+    // the implicit mask nor source fusion (mask_opt and src_fuse are off), no G column or mask-row flags.  An input of plan_shape.
+    bool planes_in = false;
     // fused anticausal-x + causal-y wavefront sweep (k_vv_xbyf) for the first `wf_levels` levels
     int wf_levels = 0;
     // The causal x sweep of a wavefront level keeps only its state in front of every tile and the fused sweep re-runs it
@@ -205,14 +212,17 @@ struct StampRequest {  // STITCH_WAVEFRONT_STAMP is Tuning::stamp
 // One pair whose level 0 alone fills the chip: a throughput case like a batch.
 inline bool chip_filling(int h0) { return 7L * tiles(h0) >= CHIP_BANDS; }
 
-// Fills the shape of a cw x ch plan for `cap` pairs.  Returns pyramid_sizes' answer: the level count, or <= 0 and an untouched shape.
-inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, int cap, const Tuning& tn, const StampRequest& st = StampRequest{}) {
+// Fills the shape of a cw x ch plan for `cap` pairs; planes_in: see PlanShape.  Returns pyramid_sizes' answer: the level count, or <= 0
+// and an untouched shape.  The ONE writer of a shape: nothing sets a field of it afterwards.
+inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, int cap, const Tuning& tn, const StampRequest& st = StampRequest{},
+                      bool planes_in = false) {
     int lw[32], lh[32];
     const int L = pyramid_sizes(cw, ch, o.level_rule, lw, lh);
     if (L <= 0) return L;
     s = PlanShape{};
     s.cw = cw, s.ch = ch, s.L = L, s.cap = cap, s.opts = o, s.tune = tn;
     s.no_fuse = tn.no_fuse != 0;
+    s.planes_in = planes_in;
     s.blur_skip = o.blur_kind == 0 ? (o.sigma < 0.5f) : (o.sigma < 0.1f);
     for (int l = 0; l < L; ++l) {
         Level& v = s.lv[l];
@@ -250,7 +260,7 @@ inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, 
     // (a plan without fused-sweep levels keeps the hand-off buffers for k_vv_xby_m: one pair in flight, from STITCH_XBYM_MPIX megapixels per level)
     s.has_wf = wf > 0 || (o.blur_kind == 0 && !tn.no_fuse && o.sigma >= 0.5f && L >= 2);
     s.has_zt = wf > 0;
-    for (int i = 0; i < 2; ++i) s.has_gz[i] = s.has_mr[i] = wf > 0 && i + 1 < L;
+    for (int i = 0; i < 2; ++i) s.has_gz[i] = s.has_mr[i] = wf > 0 && i + 1 < L && !planes_in;  // (reads_flags: planes handed in know no flags)
     // opt-in: level 0 re-run from the frames measured 3 % slower, the plane levels within noise
     if (tn.recompute >= 0 && wf > 0) s.recompute = std::min(2, tn.recompute);
     s.zero_tiles = wf > 0 && !tn.no_zero_tiles;
@@ -259,7 +269,7 @@ inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, 
     s.stamp_d7_level = st.d7_level;
     // implicit level-0 mask: needs both Van Vliet sweeps at level 0 (the x sweeps then run per-plane bands at any height;
     // STITCH_GATE64=1 restores the old restriction to heights that are multiples of 64 for A/B runs)
-    s.mask_opt = !s.no_fuse && o.blur_kind == 0 && !s.blur_skip && L >= 2 && lw[0] > 1 && lh[0] > 1 && !(tn.gate64 && lh[0] % 64);
+    s.mask_opt = !planes_in && !s.no_fuse && o.blur_kind == 0 && !s.blur_skip && L >= 2 && lw[0] > 1 && lh[0] > 1 && !(tn.gate64 && lh[0] % 64);
     if (tn.crows_l0 >= 0) s.crows_l0 = std::max(1, tn.crows_l0);
     if (tn.crows_ln >= 0) s.crows_ln = std::max(1, tn.crows_ln);
     if (tn.collapse4 >= 0) s.collapse4 = tn.collapse4 != 0;
@@ -568,6 +578,214 @@ inline CallForm call_form(const PlanShape& s, int n, bool src, bool a_dense) {
         f.c_mr = f.mr_in;
     }
     return c;
+}
+
+// ---- the band path: ONE pair split into row bands over ranks (stitch_band.inc) ---------------------------------------------------
+// What a band of a cw x ch canvas holds (BandShape, band_shape) and what each entry point launches at each level (BandForm, band_form).
+// The split levels l < Ls are reduced and collapsed band by band by the caller's sequence of operations (pipeline.BandStitcher.steps);
+// the levels from Ls up run through an ordinary plan whose level 0 is handed in (plan_shape with planes_in).
+struct BandLevel {
+    int w = 0, h_full = 0, rows = 0, row0 = 0, pitch = 0;
+    int halo = 0;   // halo rows either side: BAND_HALO on levels >= 1 (sources of an EXPAND) of a band with neighbours, else none
+    size_t ps = 0;  // plane stride in floats: pitch * (rows + 2 * halo)
+    int c4_xa = 0, c4_xb = 0;  // as Level's
+    int sh_eff = 0;  // the source height the collapse's `iy < sh - 1 ? iy + 1 : iy` clamps at: the LEVEL's last row only
+    // device addresses, null in a bare shape
+    float* g = nullptr;  // 7 planes (base = first halo row); origin = g + halo * pitch
+    float* e = nullptr;  // 3 planes, levels 1..Ls-1
+    int32_t *ix = nullptr, *iy = nullptr;  // resize tables level+1 -> level, rows in band-local source coordinates
+    double *ax = nullptr, *ay = nullptr;
+    int ph() const { return rows + 2 * halo; }  // rows per plane in memory
+    float* origin_g() const { return g + (size_t)halo * pitch; }
+    float* origin_e() const { return e + (size_t)halo * pitch; }
+};
+
+struct BandShape {
+    int cw = 0, ch = 0, rank = 0, nranks = 1, Ls = 0, L = 0;
+    BandLevel lv[32];  // 0..Ls (level Ls: this rank's band of the first replicated level, the decimation's output)
+    // the switches read at creation
+    bool zero_tiles = true;  // STITCH_NO_ZERO_TILES
+    bool src_l0 = true;      // level 0 source-fused (index plane + gathers, implicit mask) or, STITCH_BAND_PLANES=1, seven stored planes
+    bool plain_dec = false;  // STITCH_BAND_PLAIN=1: anticausal y sweep and decimation as two kernels (A/B)
+};
+// (the one writer of the field after band_shape: stitch_band_set_level0's value arrives here with the next compose)
+inline void band_set_src_l0(BandShape& s, bool source_fused) { s.src_l0 = source_fused; }
+
+enum BandRefusal { BAND_OK = 0, BAND_BAD_RANK, BAND_BAD_PYRAMID, BAND_BAD_SPLIT, BAND_BAD_ROWS, BAND_BAD_WIDTH, BAND_BAD_HALO };
+struct BandWhy {  // what the refusal's message names
+    int level = 0, row = 0, src_a = 0, src_b = 0;
+};
+
+// The y tables of the EXPAND of level l+1 into this band's rows of level l: the reference's tables for the whole level
+// (CImg.h:29625-29637), rows re-based to what this rank holds of level l+1 -- its band with its halo rows (source row 0 of the buffer =
+// row0_{l+1} - halo), or all rows when l+1 is the first replicated level.  Returns the first row whose taps leave what the rank holds
+// (*why names it), or -1.
+inline int band_row_table(const BandShape& s, int l, std::vector<int32_t>& iy, std::vector<double>& ay, BandWhy* why = nullptr) {
+    const BandLevel &v = s.lv[l], &nx = s.lv[l + 1];
+    std::vector<int32_t> idx;
+    std::vector<double> al;
+    expand_table(nx.h_full, v.h_full, idx, al);
+    const bool top_src = l + 1 == s.Ls;
+    const int src_base = top_src ? 0 : nx.row0 - nx.halo, src_rows = top_src ? nx.h_full : nx.ph();
+    iy.resize(v.rows);
+    ay.assign(al.begin() + v.row0, al.begin() + v.row0 + v.rows);
+    int bad = -1;
+    for (int y = 0; y < v.rows; ++y) {
+        const int gi = idx[v.row0 + y], gi2 = gi < nx.h_full - 1 ? gi + 1 : gi;
+        iy[y] = gi - src_base;
+        if (bad < 0 && (iy[y] < 0 || gi2 - src_base >= src_rows)) {
+            bad = y;
+            if (why) *why = BandWhy{l, v.row0 + y, gi, gi2};
+        }
+    }
+    return bad;
+}
+
+// Fills the shape of rank `rank` of `nranks` of a cw x ch canvas whose first `split_levels` levels are split (the root variant's pyramid:
+// level_rule 0).  Rank r owns rows [r * h_l / N, (r + 1) * h_l / N) of every split level: even row counts, so that the 2:1 decimation
+// never straddles two ranks, and at least 2 * BAND_HALO of them.  A refusal leaves *why for the message.
+inline BandRefusal band_shape(BandShape& s, int cw, int ch, int rank, int nranks, int split_levels, bool zero_tiles, bool src_l0, bool plain_dec,
+                              BandWhy* why = nullptr) {
+    BandWhy w0;
+    BandWhy& y = why ? *why : w0;
+    if (nranks < 1 || rank < 0 || rank >= nranks) return BAND_BAD_RANK;
+    int lw[32], lh[32];
+    const int L = pyramid_sizes(cw, ch, 0, lw, lh);
+    if (L <= 0) return BAND_BAD_PYRAMID;
+    const int Ls = split_levels;
+    y.level = L;
+    if (Ls < 1 || Ls > L - 1) return BAND_BAD_SPLIT;
+    for (int l = 0; l <= Ls; ++l) {
+        const int q = l < Ls ? 2 * nranks : nranks;  // split levels: even band heights (the 2:1 decimation stays inside a band)
+        y.level = l, y.row = lh[l], y.src_a = lw[l];
+        if (lh[l] % q != 0 || lh[l] / nranks < (l < Ls ? 2 * BAND_HALO : 1)) return BAND_BAD_ROWS;
+        if (lw[l] < 2) return BAND_BAD_WIDTH;
+    }
+    s = BandShape{};
+    s.cw = cw, s.ch = ch, s.rank = rank, s.nranks = nranks, s.Ls = Ls, s.L = L;
+    s.zero_tiles = zero_tiles, s.plain_dec = plain_dec;
+    band_set_src_l0(s, src_l0);
+    for (int l = 0; l <= Ls; ++l) {
+        BandLevel& v = s.lv[l];
+        v.w = lw[l], v.h_full = lh[l], v.rows = lh[l] / nranks, v.row0 = rank * v.rows, v.pitch = round_up(v.w, 64);
+        v.halo = l == 0 || nranks == 1 ? 0 : BAND_HALO;  // a band without neighbours has nobody's rows to hold
+        v.ps = (size_t)v.pitch * v.ph();
+    }
+    std::vector<int32_t> idx;
+    std::vector<double> al;
+    for (int l = 0; l < Ls; ++l) {
+        BandLevel& v = s.lv[l];
+        const BandLevel& nx = s.lv[l + 1];
+        expand_table(nx.w, v.w, idx, al);
+        regular_range(idx, v.w, nx.w, nx.h_full, &v.c4_xa, &v.c4_xb);
+        v.sh_eff = l + 1 == Ls ? nx.h_full : (rank == nranks - 1 ? nx.rows + nx.halo : (1 << 30));
+        if (band_row_table(s, l, idx, al, &y) >= 0) return BAND_BAD_HALO;
+    }
+    return BAND_OK;
+}
+
+// Zero-tile flags of T at level l of a band, as in a plan and under its conditions: every user of T is a fused form (so only behind
+// BO_XY_FWD), the two finest levels, an even width, at most ZT_MAX_BANDS bands per plane; and no halo rows (the flags know a plane of
+// `rows` rows), the fused decimation (the two-kernel form reads every tile), level 0 only as the index plane.  The same condition
+// holds for the index plane's own flags at level 0 (zi).
+inline bool band_zero_tile_level(const BandShape& s, int l) {
+    const BandLevel& a = s.lv[l];
+    return l < 2 && (l > 0 || s.src_l0) && (a.w & 1) == 0 && tiles(a.rows) <= ZT_MAX_BANDS && a.halo == 0 && s.zero_tiles && !s.plain_dec;
+}
+
+// The entry points of a band that launch (stitch.h: stitch_band_compose_*, _reduce_x, _reduce_xy_fwd, _reduce_y_fwd, _reduce_y_fwd_cols,
+// _reduce_y_bwd, _reduce_y_bwd_cols, _collapse_*)
+enum BandOp : uint8_t { BO_COMPOSE, BO_X, BO_XY_FWD, BO_Y_FWD, BO_Y_FWD_COLS, BO_Y_BWD, BO_Y_BWD_COLS, BO_COLLAPSE };
+
+// The level whose T flags are live behind `op` at `level`, given the level whose flags were live before (-1: none).  One buffer: a
+// level's flags live from the causal x sweep of its BO_XY_FWD to its anticausal y sweep; the separate x sweeps leave none.
+inline int band_zt_after(const BandShape& s, int zt_live, BandOp op, int level) {
+    if (op == BO_XY_FWD && band_zero_tile_level(s, level)) return level;
+    if ((op == BO_X || op == BO_XY_FWD) && zt_live == level) return -1;
+    return zt_live;
+}
+
+struct DecInstance {  // k_vv_y_bwd_dec<rowz, YST, zt, odd, xch>
+    bool rowz, zt, odd, xch;
+};
+
+struct BandForm {
+    bool admitted;  // the level takes the operation in this form (one plane at a time: stored planes; column chunks: the fused decimation)
+    int zt_after;   // band_zt_after
+    // BO_X, BO_XY_FWD: the x sweeps (k_vv_x_fwd, k_vv_x_bwd); BO_COMPOSE: zi alone
+    bool src0;       // level 0 from the frames through the index plane, the mask implicit (every operation: MaskL0 goes with it)
+    bool zi;         // the index plane's zero-tile flags
+    bool per_plane;  // blocks: per-plane bands (Bands{bands_nr, bands_h}), or 64 stacked lines
+    int nbx, bands_nr, bands_h;
+    bool zt;         // T flags: written by BO_XY_FWD, read by BO_Y_BWD / BO_Y_BWD_COLS
+    // BO_XY_FWD: the fused sweep (k_vv_xbyf)
+    bool banded;     // the BANDED instance: halo rows or a resume state (it carries more scalars through the tile loop, a few per cent slower)
+    int NR, NC, wgs;
+    // the y sweeps
+    int np;          // planes per launch
+    bool xch;        // a column range with the chunk's own state arrays
+    uint8_t y_bwd;   // YB_DEC, or YB_BWD with k_decimate behind it
+    DecInstance dec;
+    bool decimate;
+    // BO_COLLAPSE
+    int crows, strips, cols, xa, xb;  // [xa, xb): before the caller's addresses clamp it
+    bool top_src;    // the source level is the replicated one: all rows, dense planes
+};
+
+// What `op` launches at `level`; zt_live: the level whose T flags are live (the band's state); plane: -1 all seven, or one (BO_Y_FWD, BO_Y_BWD).
+inline BandForm band_form(const BandShape& s, BandOp op, int level, int zt_live = -1, int plane = -1) {
+    BandForm f{};
+    const BandLevel& a = s.lv[level];
+    const bool zt_on = band_zero_tile_level(s, level);
+    f.admitted = true;
+    f.zt_after = band_zt_after(s, zt_live, op, level);
+    f.src0 = level == 0 && s.src_l0;
+    f.zi = f.src0 && zt_on;
+    f.NR = tiles(a.rows);
+    f.NC = tiles(a.w);
+    f.np = plane < 0 ? 7 : 1;
+    switch (op) {
+    case BO_COMPOSE:
+        break;
+    case BO_XY_FWD:
+        f.zt = zt_on;
+        // a level without halo rows that starts at the image's first row is exactly a plan's launch: the plain instance
+        f.banded = a.halo != 0 || s.rank > 0;
+        f.wgs = (int)std::min<long>(7L * f.NR, WF_MAX_WGS);
+        [[fallthrough]];
+    case BO_X:  // halo rows are swept along x too (their contents are never used)
+        f.per_plane = f.src0 || f.zt;  // a block's treatment depends on its plane
+        f.bands_nr = tiles(a.ph()), f.bands_h = a.ph();
+        f.nbx = f.per_plane ? 7 * f.bands_nr : (int)((7L * a.ph() + TS - 1) / TS);
+        break;
+    case BO_Y_FWD:
+        f.admitted = !(f.src0 && plane >= 0);  // one plane at a time needs the stored planes
+        break;
+    case BO_Y_FWD_COLS:
+        f.xch = true;
+        break;
+    case BO_Y_BWD:
+    case BO_Y_BWD_COLS: {
+        const bool fused = (a.w & 1) == 0 && !s.plain_dec;  // (odd widths keep the stand-alone decimation here)
+        f.xch = op == BO_Y_BWD_COLS;
+        f.admitted = !f.xch || fused;  // the odd-width decimation overlaps workgroups by two columns
+        f.zt = zt_live == level && plane < 0 && zt_on;
+        f.y_bwd = fused ? YB_DEC : YB_BWD;
+        f.decimate = !fused;
+        // ZT = true whatever f.zt: the band path has one instance per (rowz, xch) and hands it an empty flag record where there are no
+        // flags (the pair path launches the ZT = false instance there)
+        f.dec = DecInstance{f.zt && (a.rows % YCH) != 0, true, false, f.xch};
+        break;
+    }
+    case BO_COLLAPSE:
+        f.crows = std::max(4, std::min(32, a.rows / 8));  // (a rule of the band's own: by the band's rows, whatever the launch's workgroups)
+        f.strips = (a.rows + f.crows - 1) / f.crows;
+        f.cols = level == 0 ? a.w : a.pitch;
+        f.xa = a.c4_xa, f.xb = a.c4_xb;
+        f.top_src = level + 1 == s.Ls;
+        break;
+    }
+    return f;
 }
 
 }  // namespace sk

@@ -180,8 +180,8 @@ struct stitch_plan : PlanShape {
     uint8_t* gz[2] = {nullptr, nullptr};  // G column flags of levels 1 and 2, [7*cap][tile columns] (g_cols)
     uint8_t* mr[2] = {nullptr, nullptr};  // row-repeat flags of the mask plane of levels 1 and 2, [cap][tile columns][bands] (mask_rows)
     const float* zero_page = nullptr;  // 4 KB of zeros in the arena (k_vv_xby_m's loader reads a flagged tile from here)
-    int wf_max_wgs = 2304;  // persistent workgroups of the fused sweep (STITCH_XBYF_WGS)
-    unsigned wf_spin_limit = 1u << 23;  // polls before a hand-off wait gives up, about 20 s (STITCH_XBYF_SPIN_LIMIT); 2^20 (2-3 s) was reached once in a warm-up
+    int wf_max_wgs = WF_MAX_WGS;  // persistent workgroups of the fused sweep (STITCH_XBYF_WGS)
+    unsigned wf_spin_limit = WF_SPIN_LIMIT;  // polls before a hand-off wait gives up (STITCH_XBYF_SPIN_LIMIT)
     int wf_early_read = 1;  // STITCH_XBYF_EARLY=0: poll for the hand-off only when it is needed
     double* ckpt = nullptr;  // STITCH_RECOMPUTE: [3][tiles of level 0][lines of level 0]
     unsigned long long* d7_dbg = nullptr;  // STITCH_D7_STAMP=<level>: k_vv_y_bwd_dec7's per-chunk stamps of one workgroup at that level (diagnostics)
@@ -280,44 +280,137 @@ int launch_check(const char* what) {
     return STITCH_OK;
 }
 
-// The hand-off record of a fused sweep of level l (k_vv_xbyf, k_vv_xby_m), behind the clear of its granules: every polled word is
-// cleared in front of the launch (never told apart by a per-launch argument: a captured graph replays frozen arguments, and stale
-// tags from the previous replay would match at once)
-Wavefront wavefront_of(stitch_plan* p, int l, int np, const LevelForm& f, const ZeroTiles& zt, hipStream_t s) {
+// The hand-off buffers and limits of a fused sweep: a plan's (level l's queue head) or a band's
+struct Handoff {
+    u64* yg;
+    unsigned *head, *abort, *sticky;
+    unsigned spin_limit;
+    int early_read;
+};
+Handoff handoff_of(const stitch_plan* p, int l) {
+    return Handoff{p->wf_yg, p->wf_ctrl + (size_t)l * 16, p->wf_ctrl + WF_CTRL_WORDS - 16, p->wf_ctrl + WF_CTRL_WORDS, p->wf_spin_limit, p->wf_early_read};
+}
+
+// The hand-off record of a fused sweep (k_vv_xbyf, k_vv_xby_m) of np planes of NR x NC tiles, behind the clear of its granules: every
+// polled word is cleared in front of the launch (never told apart by a per-launch argument: a captured graph replays frozen arguments,
+// and stale tags from the previous replay would match at once)
+Wavefront wavefront_of(const Handoff& h, int np, int NR, int NC, const ZeroTiles& zt, hipStream_t s) {
     Wavefront wf{};
-    wf.yg = p->wf_yg;
-    wf.counter = p->wf_ctrl + (size_t)l * 16;
-    wf.abort = p->wf_ctrl + WF_CTRL_WORDS - 16;
-    wf.sticky = p->wf_ctrl + WF_CTRL_WORDS;
-    wf.spin_limit = p->wf_spin_limit;
-    wf.NR = f.NR;
-    wf.NC = f.NC;
+    wf.yg = h.yg;
+    wf.counter = h.head;
+    wf.abort = h.abort;
+    wf.sticky = h.sticky;
+    wf.spin_limit = h.spin_limit;
+    wf.NR = NR;
+    wf.NC = NC;
     wf.NP = np;
     wf.epoch = 1;
     wf.zt = zt;
-    wf.early_read = p->wf_early_read;
+    wf.early_read = h.early_read;
     const size_t gran_words = (size_t)wf.NP * wf.NC * WF_GRAN * WAVE;
-    k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(p->wf_yg, gran_words);
+    k_clear_words<<<(int)std::min<size_t>((gran_words + 255) / 256, 2048), 256, 0, s>>>(h.yg, gran_words);
     return wf;
 }
 
-// The fused anticausal-y sweep + decimation of level a into level b: k_vv_y_bwd_dec<rowz, YST, dec_zt, dec_odd> of the record
-// (the odd instance: three-tap x decimation, workgroups overlap by two columns)
-void launch_y_bwd_dec(const stitch_plan* p, const LevelForm& f, int np, hipStream_t s, const Level& a, const Level& b, const double* ystate, const ZeroTiles& zt,
-                      int fill_l0, const ZeroTiles& gout, const ZeroTiles& mout) {
-    const dim3 g = f.dec_odd ? dim3((b.w + WAVE - 2) / (WAVE - 1), np) : dim3((a.pitch + YCOLS - 1) / YCOLS, np);
-    auto go = [&](auto R, auto Z, auto O) {
-        k_vv_y_bwd_dec<decltype(R)::value, YST, decltype(Z)::value, decltype(O)::value>
-            <<<g, 128, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, zt, nullptr, nullptr, a.h, b.h, 0, fill_l0, gout, mout);
+// The batch's fused anticausal-x + causal-y sweep: the diagnostic instance, the two that re-run the causal x sweep (MODE 2 from the
+// frames), the plain one, and a band's (BANDED: rows y0 .. of planes ph rows high, from a resume state)
+template <typename PX>
+void launch_xbyf(int wg, hipStream_t s, bool stamp, bool rcmp, bool src0, bool banded, float* T, int w, int h, int pitch, const VVK& k, double* state, long lines,
+                 double* state_y, const Wavefront& wf, const Recompute& rcv, const PairArgs<PX>& pa) {
+    if (stamp)
+        k_vv_xbyf<true><<<wg, 64, 0, s>>>(T, w, h, pitch, k, state, lines, state_y, wf, rcv, NoPairArgs{});
+    else if (rcmp && src0)
+        k_vv_xbyf<false, PX, 2><<<wg, 64, 0, s>>>(T, w, h, pitch, k, state, lines, state_y, wf, rcv, pa);
+    else if (rcmp)
+        k_vv_xbyf<false, float, 1><<<wg, 64, 0, s>>>(T, w, h, pitch, k, state, lines, state_y, wf, rcv, NoPairArgs{});
+    else if (banded)
+        k_vv_xbyf<false, float, 0, true><<<wg, 64, 0, s>>>(T, w, h, pitch, k, state, lines, state_y, wf, rcv, NoPairArgs{});
+    else
+        k_vv_xbyf<false><<<wg, 64, 0, s>>>(T, w, h, pitch, k, state, lines, state_y, wf, rcv, NoPairArgs{});
+}
+
+// The source and the destination of the fused anticausal-y sweep + decimation: np planes of T (h rows of a level h_full rows high) into
+// the planes of the next level
+struct DecPlanes {
+    float* p;
+    int w, h, pitch;
+    size_t ps;
+    int h_full;
+};
+// k_vv_y_bwd_dec<rowz, YST, zt, odd, xch> of the record, every instance either path has (the odd one: three-tap x decimation,
+// workgroups overlap by two columns; xch: columns from x0 with the chunk's own state arrays, `cols` of them)
+void launch_y_bwd_dec(const DecInstance& i, int np, hipStream_t s, const DecPlanes& a, const DecPlanes& b, const VVK& k, const double* ystate, const ZeroTiles& zt,
+                      const double* resume, double* state_out, int x0, int cols, int fill_l0, const ZeroTiles& gout, const ZeroTiles& mout) {
+    const dim3 g = i.odd ? dim3((b.w + WAVE - 2) / (WAVE - 1), np) : dim3((cols + YCOLS - 1) / YCOLS, np);
+    auto go = [&](auto R, auto Z, auto O, auto X) {
+        k_vv_y_bwd_dec<decltype(R)::value, YST, decltype(Z)::value, decltype(O)::value, decltype(X)::value>
+            <<<g, 128, 0, s>>>(a.p, a.w, a.h, a.pitch, a.ps, k, ystate, b.p, b.w, b.h, b.pitch, b.ps, zt, resume, state_out, a.h_full, b.h_full, x0, fill_l0, gout, mout);
     };
     const std::true_type y{};
     const std::false_type no{};
-    if (!f.dec_zt)
-        f.dec_odd ? go(no, no, y) : go(no, no, no);
-    else if (f.rowz)
-        f.dec_odd ? go(y, y, y) : go(y, y, no);
+    if (i.xch)
+        i.rowz ? go(y, y, no, y) : go(no, y, no, y);
+    else if (!i.zt)
+        i.odd ? go(no, no, y, no) : go(no, no, no, no);
+    else if (i.rowz)
+        i.odd ? go(y, y, y, no) : go(y, y, no, no);
     else
-        f.dec_odd ? go(no, y, y) : go(no, y, no);
+        i.odd ? go(no, y, y, no) : go(no, y, no, no);
+}
+
+// One level of the collapse: the clamp of [xa, xb) by the caller's addresses at level 0, the grid, the instance.  Columns [xa, xb) go
+// four per work-item (k_collapse4: dense, GEN, MR instances), the rest of `cols` one per work-item in the same launch; a level without
+// such a range runs k_collapse, or k_collapse_px where the record says so.  whole_words (a band): the range stands only where every
+// destination row is whole groups of four samples and the buffer is aligned to one; a plan's rule otherwise (u8_words: rows start on
+// 32-bit boundaries).
+struct CollapseKind {
+    bool dense, gen, px, mr, whole_words;
+};
+template <typename OUT, bool L0>
+void launch_collapse(CollapseArgs<OUT, L0>& A, const CollapseKind& kd, int cols, int strips, int n, const MaskRowsArg& mra, hipStream_t s) {
+    if constexpr (L0) {  // what the caller's addresses take away from the record
+        if (kd.whole_words) {
+            if ((A.w % 4) != 0 || (reinterpret_cast<uintptr_t>(A.outs.p[0]) % (4 * sizeof(OUT))) != 0) A.xa = A.xb = 0;
+        } else {
+            A.u8_words = (A.w % 4) == 0;  // unsigned char rows start on 32-bit boundaries
+            for (int i = 0; i < n; ++i) {
+                if (sizeof(OUT) == 1) A.u8_words = A.u8_words && (reinterpret_cast<uintptr_t>(A.outs.p[i]) % 4) == 0;
+                A.u8_words = A.u8_words && (reinterpret_cast<uintptr_t>(A.outs.q[i]) % 4) == 0;
+                if (sizeof(OUT) == 4 && (reinterpret_cast<uintptr_t>(A.outs.p[i]) % 4) != 0) A.xa = A.xb = 0;  // a float canvas that is not even 4-byte aligned
+            }
+        }
+    }
+    const int xa = A.xa, xb = A.xb, rest = cols - (xb - xa);
+    const int nb4 = ((xb - xa) / 4 + WAVE - 1) / WAVE, ncb = (rest + C4_THREADS - 1) / C4_THREADS;
+    const dim3 g4(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, n), g1 = grid_xy(cols, strips, n);
+    if constexpr (L0) {
+        if (xb > xa && kd.dense && kd.gen)
+            k_collapse4<OUT, true, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+        else if (xb > xa && kd.dense)
+            k_collapse4<OUT, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+        else if (xb > xa && kd.gen)
+            k_collapse4<OUT, true, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+        else if (xb > xa)
+            k_collapse4<OUT, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+        else
+            k_collapse<OUT, true><<<g1, 256, 0, s>>>(A);
+    } else if (kd.mr) {  // the instances that take the mask sample of a flagged tile from row 0
+        if (xb > xa && kd.gen)
+            k_collapse4<float, false, false, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
+        else if (xb > xa)
+            k_collapse4<float, false, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
+        else if (kd.px)
+            k_collapse_px<true><<<grid_xy(A.pitch, A.h, n), 256, 0, s>>>(A, mra);
+        else
+            k_collapse<float, false, true><<<g1, 256, 0, s>>>(A, mra);
+    } else if (xb > xa && kd.gen)
+        k_collapse4<float, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+    else if (xb > xa)
+        k_collapse4<float, false><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
+    else if (kd.px)
+        k_collapse_px<<<grid_xy(A.pitch, A.h, n), 256, 0, s>>>(A);
+    else
+        k_collapse<float, false><<<g1, 256, 0, s>>>(A);
 }
 
 // REDUCE for every level (ImageProcess.cpp:705-715): blur(G_l) into T, decimate T into G_{l+1}.  Which kernels: the call's form
@@ -373,7 +466,7 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
         }
         int fill_l0 = 0;
         if (f.sweep == SW_BATCH) {
-            Wavefront wf = wavefront_of(p, l, np, f, zt, s);
+            Wavefront wf = wavefront_of(handoff_of(p, l), np, f.NR, f.NC, zt, s);
             wf.mask_l0 = f.mask_l0 ? (f.zt ? 2 : 1) : 0;  // 2: the mask blur below the first band is recorded in the flags, not stored
             if (f.fill_mask && l > 0) wf.mr = min_;
             fill_l0 = f.fill_mask;  // flagged tiles of the mask planes repeat the plane's row 0
@@ -386,17 +479,10 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
                 rcv.seam = p->d_seam;
                 if (f.src0) rcv.zi = zi;
             }
-            if (f.stamp) {  // diagnostic build: per-segment cycle sums of the level-0 launch
-                wf.dbg = p->wf_dbg;
-                k_vv_xbyf<true><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
-            } else if (f.rcmp && f.src0)
-                k_vv_xbyf<false, PX, 2><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, pa);
-            else if (f.rcmp)
-                k_vv_xbyf<false, float, 1><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
-            else
-                k_vv_xbyf<false><<<wg, 64, 0, s>>>(p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, NoPairArgs{});
+            if (f.stamp) wf.dbg = p->wf_dbg;  // diagnostic build: per-segment cycle sums of the level-0 launch
+            launch_xbyf<PX>(wg, s, f.stamp, f.rcmp, f.src0, false, p->T, a.w, a.h, a.pitch, p->vvk, p->state, lines, state_y, wf, rcv, pa);
         } else if (f.xby) {
-            Wavefront wf = wavefront_of(p, l, np, f, zt, s);
+            Wavefront wf = wavefront_of(handoff_of(p, l), np, f.NR, f.NC, zt, s);
             wf.mask_l0 = f.mask_l0;
             if (p->xy_dbg && l == 0) wf.dbg = p->xy_dbg, p->xy_dbg_nc = wf.NC;
             StageTimer t(p, s, STITCH_K_VV_XBYF, l);
@@ -427,7 +513,8 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
         if (f.y_bwd != YB_NONE) {
             StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
             if (f.y_bwd == YB_DEC)
-                launch_y_bwd_dec(p, f, np, s, a, b, ystate, zt, fill_l0, gout, mout);
+                launch_y_bwd_dec(DecInstance{f.rowz, f.dec_zt, f.dec_odd, false}, np, s, DecPlanes{p->T, a.w, a.h, a.pitch, a.ps, a.h}, DecPlanes{b.g, b.w, b.h, b.pitch, b.ps, b.h},
+                                 p->vvk, ystate, zt, nullptr, nullptr, 0, a.pitch, fill_l0, gout, mout);
             else if (f.y_bwd == YB_BWD)
                 k_vv_y_bwd<<<gy, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, ystate, nullptr, nullptr);
             else if (f.dec_odd)
@@ -487,61 +574,22 @@ int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hi
         const ZeroTiles none{};
         const ZeroTiles gz = f.g_in ? g_cols(p->gz[l - 1], a.w) : none, gzn = f.g_out ? g_cols(p->gz[l], nx.w) : none;
         const ZeroTiles mrz = f.c_mr ? mask_rows(p->mr[l - 1], a.w, a.h) : none;
-        int xa = f.xa, xb = f.xb;
-        int u8_words = 1;  // level 0: unsigned char rows start on 32-bit boundaries
-        if (l == 0) {      // what the caller's addresses take away from the record
-            u8_words = (a.w % 4) == 0;
-            for (int i = 0; i < n; ++i) {
-                if (sizeof(OUT) == 1) u8_words = u8_words && (reinterpret_cast<uintptr_t>(outs.p[i]) % 4) == 0;
-                u8_words = u8_words && (reinterpret_cast<uintptr_t>(outs.q[i]) % 4) == 0;
-                if (sizeof(OUT) == 4 && (reinterpret_cast<uintptr_t>(outs.p[i]) % 4) != 0) xa = xb = 0;  // a float canvas that is not even 4-byte aligned
-            }
-        }
-        const int cols = l == 0 ? a.w : a.pitch, rest = cols - (xb - xa);
-        const int nb4 = ((xb - xa) / 4 + WAVE - 1) / WAVE, ncb = (rest + C4_THREADS - 1) / C4_THREADS;
-        const int strips = (a.h + f.crows - 1) / f.crows;
-        const dim3 g4(c4_padded_blocks(nb4, c.c4_swizzle) + ncb * C4_SUB, strips, n);
+        const int cols = l == 0 ? a.w : a.pitch, strips = (a.h + f.crows - 1) / f.crows;
+        const MaskRowsArg mra{mrz.flags, mrz.NC, mrz.NR};
         if (l == 0) {  // level 0: the mask is the seam's step function itself (never read from memory)
             CollapseArgs<OUT, true> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, outs,
-                                      a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, c.src ? 1 : 0, f.crows, xa, xb, u8_words,
+                                      a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, c.src ? 1 : 0, f.crows, f.xa, f.xb, 1,
                                       c.c4_lock, c.c4_swizzle};
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
-            const bool dense = c.src && c.a_dense;
-            if (xb > xa && dense && f.gen)
-                k_collapse4<OUT, true, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa && dense)
-                k_collapse4<OUT, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa && f.gen)
-                k_collapse4<OUT, true, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa)
-                k_collapse4<OUT, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else
-                k_collapse<OUT, true><<<grid_xy(cols, strips, n), 256, 0, s>>>(A);
+            launch_collapse(A, CollapseKind{c.src && c.a_dense, f.gen, false, false, false}, cols, strips, n, mra, s);
         } else {
             OutPtrs<float> eo{};
             eo.p[0] = a.e;
             CollapseArgs<float, false> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, eo,
-                                         a.pitch, a.ps, nullptr, NoPairArgs{}, 0, f.crows, xa, xb, 1, c.c4_lock, c.c4_swizzle};
+                                         a.pitch, a.ps, nullptr, NoPairArgs{}, 0, f.crows, f.xa, f.xb, 1, c.c4_lock, c.c4_swizzle};
             A.gz = gz.flags, A.gnc = gz.NC, A.zo = (unsigned)(7 * (size_t)p->cap * a.ps);
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
-            const MaskRowsArg mra{mrz.flags, mrz.NC, mrz.NR};
-            if (f.c_mr) {  // the instances that take the mask sample of a flagged tile from row 0
-                if (xb > xa && f.gen)
-                    k_collapse4<float, false, false, true, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
-                else if (xb > xa)
-                    k_collapse4<float, false, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb, mra);
-                else if (f.px)
-                    k_collapse_px<true><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A, mra);
-                else
-                    k_collapse<float, false, true><<<grid_xy(cols, strips, n), 256, 0, s>>>(A, mra);
-            } else if (xb > xa && f.gen)
-                k_collapse4<float, false, false, true><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (xb > xa)
-                k_collapse4<float, false><<<g4, C4_THREADS, 0, s>>>(A, nb4, ncb);
-            else if (f.px)
-                k_collapse_px<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(A);
-            else
-                k_collapse<float, false><<<grid_xy(cols, strips, n), 256, 0, s>>>(A);
+            launch_collapse(A, CollapseKind{false, f.gen, f.px, f.c_mr, false}, cols, strips, n, mra, s);
         }
     }
     return launch_check("collapse");
@@ -1429,12 +1477,18 @@ int stitch_dev_move_f32(const float* d_src, int sw, int sh, int ox, int oy, floa
     return dev_move(d_src, sw, sh, ox, oy, d_canvas, cw, ch, stream);
 }
 
+static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out);
 int stitch_plan_create(int cw, int ch, const stitch_blend_opts* opts, stitch_plan** plan_out) {
     return stitch_plan_create_batched(cw, ch, opts, 1, plan_out);
 }
 
-// Fill the shape (plan_shape, stitch_call_form.h), carve one arena for it, upload the resize tables.
 int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, stitch_plan** plan_out) {
+    return plan_create(cw, ch, opts, max_pairs, false, plan_out);
+}
+
+// Fill the shape (plan_shape, stitch_call_form.h), carve one arena for it, upload the resize tables.  planes_in: the coarse levels of a
+// band-split pair (stitch_band_create).
+static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out) {
     if (!plan_out) return fail(STITCH_ERR_ARG, "plan_create: null plan_out");
     if (max_pairs < 1 || max_pairs > MAXB) return fail(STITCH_ERR_ARG, "plan_create: max_pairs must be 1..%d", MAXB);
     *plan_out = nullptr;
@@ -1455,7 +1509,7 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
     stamps.xy = std::getenv("STITCH_XBYM_STAMP") != nullptr;
     stamps.co = std::getenv("STITCH_COARSE_STAMP") != nullptr;
     if (std::getenv("STITCH_D7_STAMP")) stamps.d7_level = atoi(std::getenv("STITCH_D7_STAMP"));
-    plan_shape(*p, cw, ch, o, max_pairs, tn, stamps);
+    plan_shape(*p, cw, ch, o, max_pairs, tn, stamps, planes_in);
     const size_t B = (size_t)max_pairs;
     p->vvk = make_vvk(o.sigma);
     p->drk = make_drk(o.sigma);
@@ -2243,11 +2297,7 @@ int stitch_dev_check_collapse_taps(int w, int h, int probe, unsigned long long* 
             eo.p[0] = (float*)(base + off[3 + v]);
             CollapseArgs<float, false> A{(const float*)(base + off[0]), w, h, pitch, ps, (const float*)(base + off[1]), (const float*)(base + off[2]), sw, sh, spitch, sps,
                                          tb, eo, pitch, ps, nullptr, NoPairArgs{}, 0, crows, 0, v == 0 ? gxb : 0, 1, 0, 1};
-            if (v == 0) {
-                const int rest = pitch - gxb, nb4 = (gxb / 4 + WAVE - 1) / WAVE, ncb = (rest + C4_THREADS - 1) / C4_THREADS;
-                k_collapse4<float, false, false, true><<<dim3(c4_padded_blocks(nb4, A.swizzle) + ncb * C4_SUB, strips, 1), C4_THREADS>>>(A, nb4, ncb);
-            } else
-                k_collapse<float, false><<<grid_xy(pitch, strips, 1), 256>>>(A);
+            launch_collapse(A, CollapseKind{false, true, false, false, false}, pitch, strips, 1, MaskRowsArg{}, nullptr);
         }
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(o1.data(), base + off[3], bytes[3], hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(o2.data(), base + off[4], bytes[4], hipMemcpyDeviceToHost) == hipSuccess;

@@ -4,6 +4,8 @@ the choices lead to; and compares two such traces.
   rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python scripts/trace_call_forms.py
       every (switch, value, extra environment, shape, form, pixel type) of tests/switch_table.py whose form is a pair call, then the
       flag tests' shapes (tests/g_flags_ref.py's forms) with one and two pairs.  The environment is set before each plan is created.
+      Then the band path (pipeline.LocalBandGroup: every band of a pair from one host thread, so the order of launches is fixed): the
+      shapes of tests/test_gpu_band.py in every form of test_band_group_single_host_thread, both pixel types, under the band switches.
       Inputs are synthetic; nothing is compared -- the launches do not depend on the data.  STITCH_LIB selects the library.
   python scripts/trace_call_forms.py --compare A_kernel_trace.csv B_kernel_trace.csv [--out FILE] [--note TEXT]
       the two ordered lists of (kernel, grid, workgroup, LDS bytes, scratch bytes), line for line.
@@ -61,6 +63,45 @@ def cases():
                     yield g_flags_ref.FORMS[form], cw, ch, "batch", 2, n, dtype, g_flags_ref.OPTS
 
 
+# (world, canvas, split levels) of tests/test_gpu_band.py's parametrised cases and of its 132-row bands; its forms; the band switches
+BAND_SHAPES = [(2, 2048, 1024, 2), (2, 2048, 1024, 3), (8, 2048, 1024, 2), (4, 1024, 512, 1), (3, 770, 384, 2), (2, 770, 384, 2), (3, 768, 384, 2), (2, 1540, 768, 2),
+               (6, 772, 384, 1), (1, 1000, 500, 2), (3, 768, 396, 2)]
+BAND_FORMS = (True, False, "planes", "stored", "stored+fused", "chunks4")
+BAND_ENVS = ({}, {"STITCH_NO_ZERO_TILES": "1"}, {"STITCH_BAND_PLAIN": "1"}, {"STITCH_BAND_PLANES": "1"})
+
+
+def band_cases():
+    for world, cw, ch, Ls in BAND_SHAPES:
+        for env in BAND_ENVS:
+            for fuse in BAND_FORMS:
+                if fuse == "chunks4" and "STITCH_BAND_PLAIN" in env:
+                    continue  # (column chunks need the fused decimation: the call is refused)
+                for dtype in (np.uint8, np.float32):
+                    yield env, world, cw, ch, Ls, fuse, dtype
+
+
+def run_bands(dev):
+    import torch
+    from computervisionimagestich2_amd import pipeline
+    count = 0
+    for env, world, cw, ch, Ls, fuse, dtype in band_cases():
+        set_env(env)
+        F, P, offx, offy, M, ox, oy = pair_inputs(cw, ch, 0, dtype)
+        grp = pipeline.LocalBandGroup(cw, ch, Ls, world, dev, fuse_sweeps=fuse in (True, "stored+fused"), plane_pipeline_min=0 if fuse == "planes" else None,
+                                      col_chunks=4 if fuse == "chunks4" else 1)
+        try:
+            if str(fuse).startswith("stored"):
+                for b in grp.bands:
+                    b.band.set_level0(False)
+            for rep in range(2):  # twice: what a call leaves for the next (the live flags' level)
+                grp.run(torch.from_numpy(F).to(dev), P, offx, offy, torch.from_numpy(M).to(dev), ox, oy)
+            torch.cuda.synchronize()
+        finally:
+            grp.close()
+        count += 1
+    return count
+
+
 def run():
     import torch
     from computervisionimagestich2_amd import capi
@@ -98,8 +139,9 @@ def run():
         count += 1
         if count % 100 == 0:
             print(f"... {count}", flush=True)
+    bands = run_bands(dev)
     set_env({})
-    print(f"cases {count}")
+    print(f"cases {count} band cases {bands}")
 
 
 def dispatches(path):

@@ -1,7 +1,26 @@
 """GPU: ONE pair split into row bands over several ranks (BASELINE.json configs[4]).  The GPU box has
 one device, so the ranks of these tests are processes that all drive cuda:0 and exchange through gloo, staged through the
 host (pipeline.RankTransport(staged=True)); on a node the same BandStitcher runs with backend "nccl" (RCCL over xGMI) on
-device tensors.  Every rank's band of the mosaic must equal the oracle's rows bit for bit."""
+device tensors.  Every rank's band of the mosaic must equal the oracle's rows bit for bit.
+
+Which case selects each kernel instance the band path chooses between (csrc/stitch_call_form.h: band_form; the records of these shapes
+are tests/golden/band_forms.json, and tests/test_band_form_host.py checks that the list is complete).  "group" is
+test_band_group_single_host_thread, the canvas and band count name its case:
+  k_src_index, k_vv_x_fwd<PX, true>         level 0 from the frames: every case but group "stored", "stored+fused", "planes"
+  k_compose, k_mask, k_vv_x_fwd<float, false> at level 0   group "stored", "stored+fused", "planes"; test_pair_split_into_row_bands planes=True
+  k_vv_x_fwd<float, false>, k_vv_x_bwd      every case (levels >= 1; the separate x sweeps: every case that is not fused)
+  k_vv_xbyf<false>                          the plain instance, no halo rows and no resume state: test_single_rank_band_is_the_whole_pair;
+                                            level 0 of the first band of group True
+  k_vv_xbyf<false, float, 0, true>          BANDED: group True, 2048 x 1024 in 2 and 8 bands, 768 x 384 in 3 (level 1: halo rows; bands below the first)
+  k_vv_y_fwd, k_vv_y_fwd<true>              every case that is not fused; XCH: group "chunks4"
+  k_vv_y_bwd_dec<false>                     even widths, no flags or rows that 8 divides: test_pair_split_into_row_bands_threads, 1540 x 768
+  k_vv_y_bwd_dec<true>                      the per-row flag look-up: test_single_rank_band_is_the_whole_pair (500 and 250 rows);
+                                            with neighbours, test_fused_band_rows_that_eight_does_not_divide (132 rows)
+  k_vv_y_bwd_dec<false, YST, true, false, true>   XCH: group "chunks4", 2048 x 1024 and 768 x 384
+  k_vv_y_bwd_dec<true, YST, true, false, true>    XCH with the per-row look-up: test_fused_sweep_then_decimation_over_a_column_range (no sequence of
+                                            BandStitcher.steps selects it)
+  k_vv_y_bwd + k_decimate                   odd level widths: 770 x 384 (level 1 is 385 wide); STITCH_BAND_PLAIN=1 in test_gpu_switches.py
+  k_collapse4, k_collapse                   widths with and without a regular run of 256 columns: every case (2048 x 1024: levels 0 and 1 / level 2)"""
 import os
 import socket
 import sys
@@ -159,6 +178,58 @@ def test_band_group_single_host_thread(st, gpu, oracle, world, fw, fh, cw, ch, L
         assert bad.size == 0, (rep, len(bad), bad[:3].tolist())
     assert len({b.seam.as_tuple() for b in grp.bands}) == 1
     grp.close()
+
+
+def test_fused_band_rows_that_eight_does_not_divide(st, gpu, oracle):
+    """The per-row flag look-up of the decimating sweep (k_vv_y_bwd_dec<true>): bands of 132 rows at level 0 behind the fused sweep,
+    so that a chunk of eight rows straddles two 64-row bands of tiles.  Three bands, two split levels, against the oracle."""
+    import torch
+    from computervisionimagestich2_amd import pipeline
+    world, fw, fh, cw, ch, Ls = 3, 520, 396, 768, 396, 2
+    A, B, P = _inputs(oracle, fw, fh, np.uint8)
+    rc, ref = oracle.pair(B, P, 0.0, 0.0, A, 0, 0, cw, ch)
+    assert rc == 0
+    grp = pipeline.LocalBandGroup(cw, ch, Ls, world, gpu, fuse_sweeps=True)
+    assert [g["rows"] for g in grp.bands[0].geom[:2]] == [132, 66]
+    dA, dB = torch.from_numpy(A).to(gpu), torch.from_numpy(B).to(gpu)
+    for rep in range(2):
+        got = torch.cat(grp.run(dB, P, 0.0, 0.0, dA, 0, 0), dim=1).cpu().numpy()
+        bad = np.argwhere(got != ref)
+        assert bad.size == 0, (rep, len(bad), bad[:3].tolist())
+    grp.close()
+
+
+def test_fused_sweep_then_decimation_over_a_column_range(st, gpu, oracle):
+    """The same look-up in the column-chunk instance (k_vv_y_bwd_dec<true, YST, true, false, true>).  BandStitcher.steps never selects
+    it -- its column chunks follow the separate x sweeps, which leave no flags -- so the calls are issued here: one band (no exchange),
+    at both split levels the fused sweep, then the decimating sweep over the column range [0, pitch).  The pitches are multiples of 128,
+    so the range's state arrays are laid out as the fused sweep leaves them.  396 and 198 rows; against the oracle."""
+    import torch
+    from computervisionimagestich2_amd import capi
+    fw, fh, cw, ch, Ls = 520, 396, 768, 396, 2
+    A, B, P = _inputs(oracle, fw, fh, np.float32)
+    rc, ref = oracle.pair(B, P, 0.0, 0.0, A, 0, 0, cw, ch)
+    assert rc == 0
+    band = capi.Band(cw, ch, 0, 1, Ls)
+    geom = band.geom
+    assert all(g["pitch"] % 128 == 0 and g["rows"] % 8 for g in geom[:Ls])
+    f64 = dict(dtype=torch.float64, device=gpu)
+    out = torch.empty((3, geom[0]["rows"], geom[0]["w"]), dtype=torch.float32, device=gpu)
+    for rep in range(2):
+        band.compose(torch.from_numpy(B).to(gpu), P, 0.0, 0.0, torch.from_numpy(A).to(gpu), 0, 0)
+        for l in range(Ls):
+            fwd, bwd = torch.zeros(4 * 7 * geom[l]["pitch"], **f64), torch.zeros(3 * 7 * geom[l]["pitch"], **f64)
+            band.reduce_xy_fwd(l, None, fwd)
+            band.reduce_y_bwd_cols(l, 0, geom[l]["pitch"], fwd, None, bwd)
+        top = torch.empty((7, geom[Ls]["rows"], geom[Ls]["w"]), dtype=torch.float32, device=gpu)
+        band.rows(Ls, 2, 0, geom[Ls]["rows"], top, True)
+        band.top(top)
+        for l in range(Ls - 1, -1, -1):
+            band.collapse(l, out if l == 0 else None)
+        band.status()
+        got = out.cpu().numpy()
+        assert np.array_equal(got.view(np.uint8), ref.view(np.uint8)), (rep, int((got != ref).sum()))
+    band.close()
 
 
 def test_band_random_configs(st, gpu, oracle):
