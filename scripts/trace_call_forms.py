@@ -3,7 +3,8 @@ the choices lead to; and compares two such traces.
 
   rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python scripts/trace_call_forms.py
       every (switch, value, extra environment, shape, form, pixel type) of tests/switch_table.py whose form is a pair call, then the
-      flag tests' shapes (tests/g_flags_ref.py's forms) with one and two pairs.  The environment is set before each plan is created.
+      flag tests' shapes (tests/g_flags_ref.py's forms) with one and two pairs, then every case of tests/form_cover.py's two tables -- every
+      form the decision reaches at default switches -- in both pixel types.  The environment is set before each plan is created.
       Then the band path (pipeline.LocalBandGroup: every band of a pair from one host thread, so the order of launches is fixed): the
       shapes of tests/test_gpu_band.py in every form of test_band_group_single_host_thread, both pixel types, under the band switches.
       Inputs are synthetic; nothing is compared -- the launches do not depend on the data.  STITCH_LIB selects the library.
@@ -19,6 +20,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import form_cover  # noqa: E402
+import form_cover_refs  # noqa: E402
 import g_flags_ref  # noqa: E402
 import switch_table as T  # noqa: E402
 
@@ -36,6 +39,12 @@ def pair_inputs(cw, ch, i, dtype):
     fw, fh = cw * 5 // 8 - 13 * i, ch - 5 - 3 * i
     P = [1.0, 0.002, 1e-6, -(cw - fw - 3.0 - 5 * i), -0.001, 1.0, 5e-7, -3.5 + i]
     return image(fw, fh, 2 * i + 1, dtype), P, -0.25, -1.5, image(cw - fw // 2 + 9 * i, ch - 7, 2 * i, dtype), 0, -2
+
+
+def cover_inputs(cw, ch, i, dtype):
+    """Pair i of a case of form_cover.CASES: the placements of tests/test_gpu_form_cover.py's first call (canvases down to 3 x 3)."""
+    fw, P, mw, ox, _ = form_cover.inputs(cw)[g_flags_ref.BATCHES[0][i % 2]]
+    return image(fw, ch, 2 * i + 1, dtype), P, 0.0, 0.0, image(mw, ch, 2 * i, dtype), ox, 0
 
 
 def set_env(settings):
@@ -61,6 +70,9 @@ def cases():
             for n in (1, 2):
                 for dtype in (np.uint8, np.float32):
                     yield g_flags_ref.FORMS[form], cw, ch, "batch", 2, n, dtype, g_flags_ref.OPTS
+    for cw, ch, cap, n, dense, opts, _ in form_cover_refs.ALL_CASES:
+        for dtype in (np.uint8, np.float32):
+            yield {}, cw, ch, "cover_blend" if dense else "cover", cap, n, dtype, form_cover.OPTION_SETS[opts]
 
 
 # (world, canvas, split levels) of tests/test_gpu_band.py's parametrised cases and of its 132-row bands; its forms; the band switches
@@ -108,16 +120,16 @@ def run():
     dev = torch.device("cuda")
     cache, count = {}, 0
 
-    def inputs(cw, ch, n, dtype):
-        key = (cw, ch, n, np.dtype(dtype).name)
+    def inputs(cw, ch, n, dtype, make):
+        key = (cw, ch, n, np.dtype(dtype).name, make.__name__)
         if key not in cache:
             cache.clear()  # (one shape's tensors at a time)
-            host = [pair_inputs(cw, ch, i, dtype) for i in range(n)]
+            host = [make(cw, ch, i, dtype) for i in range(n)]
             cache[key] = host, [(torch.from_numpy(F).to(dev), P, ox_, oy_, torch.from_numpy(M).to(dev), ox, oy) for F, P, ox_, oy_, M, ox, oy in host]
         return cache[key]
 
     for env, cw, ch, form, cap, n, dtype, opts in cases():
-        host, items = inputs(cw, ch, max(n, cap), dtype)
+        host, items = inputs(cw, ch, max(n, cap), dtype, cover_inputs if form.startswith("cover") else pair_inputs)
         set_env(env)
         if form == "host":
             capi.pair(*host[0], cw, ch)
@@ -125,7 +137,10 @@ def run():
             plan = capi.Plan(cw, ch, opts=opts, max_pairs=cap)
             try:
                 tdt = torch.uint8 if dtype == np.uint8 else torch.float32
-                if form == "blend":
+                if form == "cover_blend":
+                    a = torch.from_numpy(image(cw, ch, 1, dtype)).to(dev)
+                    plan.blend(a, a.flip(2).contiguous())
+                elif form == "blend":
                     a = torch.zeros((3, ch, cw), dtype=tdt, device=dev)
                     a[:, : items[0][0].shape[1], : items[0][0].shape[2]] = items[0][0]
                     plan.blend(a, a.flip(2).contiguous())
