@@ -204,6 +204,8 @@ def lib():
             L.stitch_plan_g_flag_counts.restype, L.stitch_plan_g_flag_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_mask_row_counts"):  # include/stitch_mask_rows.h (likewise)
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
+        if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
+            L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
         _lib = L
     return _lib
 
@@ -1240,6 +1242,13 @@ class Plan(_Handle):
         plane's row 0 instead of storing them (stitch_plan_mask_row_counts)."""
         out = (C.c_uint64 * 2)()
         _chk(lib().stitch_plan_mask_row_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def index_counts(self):
+        """-> (computed, reused, shared): level-0 index planes of the plan's last call -- slots whose plane the call computed, slots
+        whose plane stood from an earlier call, pairs that read the plane of an earlier pair of the call (stitch_plan_index_counts)."""
+        out = (C.c_uint32 * 3)()
+        _chk(lib().stitch_plan_index_counts(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_handoff_spin_limit(self, polls):

@@ -50,6 +50,12 @@ struct PairSrc {
 };
 
 struct NoPairArgs {};  // levels >= 1 carry no pair description
+// the slot whose index plane and `zi` bytes pair pr gathers through (PairArgs::idx_pr); wave-uniform wherever pr is
+template <typename PX>
+__device__ __forceinline__ int index_owner(const PairArgs<PX>& pa, int pr) {
+    return pa.idx_pr[pr];
+}
+__device__ __forceinline__ int index_owner(const NoPairArgs&, int pr) { return pr; }
 template <typename OUT, bool DENSE>
 struct CollapseSrc {
     typedef NoPairArgs type;
@@ -156,27 +162,83 @@ __device__ __forceinline__ bool mask_row_flag(const uint8_t* __restrict__ flags,
     return flags != nullptr && flags[((size_t)pr * nc + min(x >> 6, nc - 1)) * nr + (y >> 6)] != 0;
 }
 
+// What the index plane and the `zi` bytes in a plan's slot were computed from, kept on the device so that the decision to reuse
+// them is taken in stream order (a captured sequence is replayed behind the host's back and decides again on every replay).
+// The plane is a function of exactly these fields and the plan's canvas; doubles and floats are compared by bit pattern.
+struct IndexKey {
+    unsigned long long map[8];
+    unsigned offx, offy;
+    int fw, fh;
+    unsigned px;     // sizeof(PX)
+    unsigned valid;  // 0 at creation, after a launch that overwrote the slot (k_index_forget) and after stitch_plan_clear_fault
+};
+// In front of a source-fused call of n pairs, one wavefront: lane i compares pair i's descriptor with the record of slot i, leaves
+// todo[i] = 1 where k_src_index has to run for the slot and takes the record over.  A pair whose owner is an earlier pair
+// (PairArgs::idx_pr) reads that pair's plane: its own slot and record stay as they are.  counts (stitch_plan_index_counts): slots
+// computed, slots reused from an earlier call, pairs that share another pair's plane.
+template <typename PX>
+__global__ __launch_bounds__(64) void k_index_keys(PairArgs<PX> pa, int n, IndexKey* __restrict__ keys, unsigned* __restrict__ todo,
+                                                   unsigned* __restrict__ counts) {
+    const int i = threadIdx.x;
+    const bool in = i < n, owner = in && pa.idx_pr[min(i, MAXB - 1)] == i;
+    bool same = false;
+    if (owner) {
+        IndexKey k;
+        for (int j = 0; j < 8; ++j) k.map[j] = (unsigned long long)__double_as_longlong(pa.map[i].p[j]);
+        k.offx = __float_as_uint(pa.offx[i]), k.offy = __float_as_uint(pa.offy[i]);
+        k.fw = pa.fw[i], k.fh = pa.fh[i];
+        k.px = (unsigned)sizeof(PX), k.valid = 1u;
+#ifndef STITCH_NO_INDEX_REUSE  // (the A/B library: every plane on every call)
+        const IndexKey r = keys[i];
+        same = r.valid != 0 && r.offx == k.offx && r.offy == k.offy && r.fw == k.fw && r.fh == k.fh && r.px == k.px;
+        for (int j = 0; j < 8; ++j) same = same && r.map[j] == k.map[j];
+#endif
+        if (!same) keys[i] = k;
+    }
+    if (i < MAXB) todo[i] = owner && !same ? 1u : 0u;
+    const int computed = __popcll(__ballot(owner && !same)), reused = __popcll(__ballot(owner && same)), shared = __popcll(__ballot(in && !owner));
+    if (i == 0) counts[0] = (unsigned)computed, counts[1] = (unsigned)reused, counts[2] = (unsigned)shared;
+}
+// Behind a launch that overwrote the level-0 slots of pairs 0 .. n-1 (k_compose, k_load_canvases): their records no longer hold
+__global__ __launch_bounds__(64) void k_index_forget(IndexKey* __restrict__ keys, int n) {
+    if ((int)threadIdx.x < n) keys[threadIdx.x].valid = 0u;
+}
+// the preset of the `zi` bytes ("outside" until k_src_index finds a sample) of the slots whose plane is computed in this call
+__global__ __launch_bounds__(256) void k_zi_preset(uint8_t* __restrict__ flags, int per_slot, const unsigned* __restrict__ todo) {
+    if (!todo[blockIdx.y]) return;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per_slot; i += gridDim.x * blockDim.x) flags[(size_t)blockIdx.y * per_slot + i] = 1;
+}
+
 constexpr int SI_ROWS = 8;  // rows per workgroup of k_src_index (a one-row workgroup is launch-bound: 393k workgroups per batch)
+// Workgroups per column block and pair in a plan's launch, each looping over the row groups.  A call whose planes all stand still
+// launches the grid, and every workgroup returns at once: 12 288 of them per 16-pair sequence at 6144 x 4096 instead of 196 608.
+constexpr int SI_WGY = 32;
+// todo (a plan's call): the plane of slot pr is computed only where todo[pr] is set (k_index_keys); nullptr (a band): always
 template <typename PX>
 __global__ __launch_bounds__(256) void k_src_index(PairArgs<PX> pa, float* __restrict__ g0_all, int cw, int ch, int pitch, size_t ps,
-                                                   ZeroTiles zi, int y_base = 0) {  // y_base: canvas row of plane row 0 (a rank's band)
+                                                   ZeroTiles zi, int y_base = 0,  // y_base: canvas row of plane row 0 (a rank's band)
+                                                   const unsigned* __restrict__ todo = nullptr) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, pr = blockIdx.z;
+    if (todo && !todo[pr]) return;
     if (x >= pitch) return;
     const MapP m = pa.map[pr];
     const float offx = pa.offx[pr], offy = pa.offy[pr];
     const int fw = pa.fw[pr], fh = pa.fh[pr];
     unsigned* __restrict__ idx = reinterpret_cast<unsigned*>(g0_all + (size_t)pr * 7 * ps);
-    const int y0 = blockIdx.y * SI_ROWS, y1 = min(y0 + SI_ROWS, ch);
-    for (int y = y0; y < y1; ++y) {
-        unsigned v = off_outside<PX>();
-        int nx, ny;
-        if (x < cw && map_to_src(m, (float)x + offx, (float)(y + y_base) + offy, fw, fh, nx, ny))
-            v = ((unsigned)ny * (unsigned)fw + (unsigned)nx) * (unsigned)sizeof(PX);  // the host checked that a plane fits 32 bits
-        // a wavefront is 64 consecutive pixels of one row = one row of one 64x64 tile (the pitch is a multiple of 64): the
-        // tile's "every pixel outside the frame" flag, preset to 1, is cleared by any row that holds a sample (same byte,
-        // same value)
-        if (zi.flags && __ballot(v != off_outside<PX>()) != 0 && (threadIdx.x & 63) == 0) zi.flags[zi.index(pr, y >> 6, x >> 6)] = 0;
-        idx[(size_t)y * pitch + x] = v;
+    // groups of SI_ROWS rows, gridDim.y apart (a plan's launch has at most SI_WGY workgroups per column block and pair)
+    for (int y0 = blockIdx.y * SI_ROWS; y0 < ch; y0 += gridDim.y * SI_ROWS) {
+        const int y1 = min(y0 + SI_ROWS, ch);
+        for (int y = y0; y < y1; ++y) {
+            unsigned v = off_outside<PX>();
+            int nx, ny;
+            if (x < cw && map_to_src(m, (float)x + offx, (float)(y + y_base) + offy, fw, fh, nx, ny))
+                v = ((unsigned)ny * (unsigned)fw + (unsigned)nx) * (unsigned)sizeof(PX);  // the host checked that a plane fits 32 bits
+            // a wavefront is 64 consecutive pixels of one row = one row of one 64x64 tile (the pitch is a multiple of 64): the
+            // tile's "every pixel outside the frame" flag, preset to 1, is cleared by any row that holds a sample (same byte,
+            // same value)
+            if (zi.flags && __ballot(v != off_outside<PX>()) != 0 && (threadIdx.x & 63) == 0) zi.flags[zi.index(pr, y >> 6, x >> 6)] = 0;
+            idx[(size_t)y * pitch + x] = v;
+        }
     }
 }
 

@@ -227,7 +227,8 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
         const bool gen_mask = MODE != 0 && pass_row;  // band 0 of an implicit mask plane: the step itself
         const bool gen_frame = MODE == 2 && src_q < 3 && !a_is_dense(pa), gen_mosaic = MODE == 2 && src_q < 6 && !gen_frame;
         const float* in_base = MODE == 1 ? rc.in + ((size_t)p * h + r0) * pitch : nullptr;
-        const float* idx_rows = MODE == 2 ? rc.in + ((size_t)src_pr * 7 * h + r0) * pitch : nullptr;  // rows r0.. of the pair's index plane
+        const int idx_pr = index_owner(pa, src_pr);
+        const float* idx_rows = MODE == 2 ? rc.in + ((size_t)idx_pr * 7 * h + r0) * pitch : nullptr;  // rows r0.. of the index plane the pair reads
         const __amdgpu_buffer_rsrc_t rs = x_rsrc<PX>(pa, src_pr, src_q);
         const XShift ms = x_shift<PX>(pa, src_pr, src_q);
         SeamDev sd{};
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
             } else if (MODE == 1)
                 tile_load(in_base, pitch, C * TS, lane, pre);
             else if (gen_frame) {
-                if (rc.zi.flags && rc.zi.flags[rc.zi.index(src_pr, R, C)]) {
+                if (rc.zi.flags && rc.zi.flags[rc.zi.index(idx_pr, R, C)]) {
                     const float o = __uint_as_float(off_outside<PX>());
 #pragma unroll
                     for (int i = 0; i < 16; ++i) pre[i] = f4{o, o, o, o};

@@ -17,7 +17,15 @@ struct PairArgs {
     // is frame[q][y][x] as it stands (fw x fh = the canvas), exactly like the mosaic with a zero shift; there is no map and
     // no index plane.  One value for the whole launch.
     int a_dense;
+    // The slot whose index plane (and `zi` bytes) pair i reads: i itself, or an earlier pair of the call with the same map, offsets,
+    // frame size and pixel size (k_index_keys, k_compose.inc).  Written by set_index_owners alone, for every PairArgs that is built.
+    int idx_pr[MAXB];
 };
+// idx_pr of the n pairs of a call: owner[i], or every pair its own owner (owner == nullptr: the band path, stitch_blend_*)
+template <typename PX>
+inline void set_index_owners(PairArgs<PX>& pa, int n, const int* owner) {
+    for (int i = 0; i < MAXB; ++i) pa.idx_pr[i] = owner && i < n ? owner[i] : i;
+}
 
 // Range-checked gathers of input samples: a raw buffer descriptor over one channel plane; a byte offset beyond the
 // plane (the index plane's "outside") reads as 0, which is the reference's untouched zero canvas.

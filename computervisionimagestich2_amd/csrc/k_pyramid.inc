@@ -152,7 +152,7 @@ __device__ __forceinline__ void level_ab(const PairArgs<OUT>& pa, int pr, int us
         if (src.a_dense)
             fin = src.frame_at(x, y, fso);  // canvas a as it stands: no index plane
         else {
-            const unsigned fo = reinterpret_cast<const unsigned*>(g)[o];  // k_src_index's byte offset in the slot of plane 0
+            const unsigned fo = reinterpret_cast<const unsigned*>(g)[o];  // k_src_index's byte offset in the slot of plane 0 (g: collapse_slot)
             fin = fo != off_outside<OUT>();
             fso = fo / sizeof(OUT);
         }
@@ -228,6 +228,12 @@ __device__ __forceinline__ bool g_span_flag(const uint8_t* __restrict__ flags, i
     return flags != nullptr && (g_col_flag(flags, nc, plane, x) || g_col_flag(flags, nc, plane, x2));
 }
 
+// The level's slot that pair pr reads.  A source-fused level 0 reads ONE thing from its slot, the index plane (the mask is the seam's
+// step, the six planes come from the frames), and that is the plane of the pair's owner (PairArgs::idx_pr); every other level: pr's own.
+template <typename OUT, bool DENSE>
+__device__ __forceinline__ int collapse_slot(const CollapseArgs<OUT, DENSE>& A, int pr) {
+    return DENSE && A.use_src ? index_owner(A.pa, pr) : pr;
+}
 // one column x, rows [y0, y1) of pair pr
 template <typename OUT, bool DENSE, bool MR = false>
 __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A, int x, int y0, int y1, int pr, MaskRowsArg mr = MaskRowsArg{}) {
@@ -235,7 +241,7 @@ __device__ __forceinline__ void collapse_cols1(const CollapseArgs<OUT, DENSE>& A
     const size_t ps = A.ps, sps = A.sps, ops = A.ops;
     const ExpandTab& tb = A.tb;
     const SeamDev* __restrict__ seam_l0 = A.seam_l0;
-    const float* g = A.g_all + (size_t)pr * 7 * ps;
+    const float* g = A.g_all + (size_t)collapse_slot(A, pr) * 7 * ps;
     const float* gn = A.gn_all + (size_t)pr * 7 * sps;
     const float* en = A.en_all + (size_t)pr * 3 * sps;
     OUT* __restrict__ out = DENSE ? A.outs.p[pr] : A.outs.p[0] + (size_t)pr * 3 * ops;
@@ -504,7 +510,7 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
     const size_t ps = A.ps, sps = A.sps, ops = A.ops;
     const ExpandTab& tb = A.tb;
     const SeamDev* __restrict__ seam_l0 = A.seam_l0;
-    const float* g = A.g_all + (size_t)pr * 7 * ps;
+    const float* g = A.g_all + (size_t)collapse_slot(A, pr) * 7 * ps;
     // A.lockstep == 2 (levels >= 1): the mask samples of a row are read by channel 0 and handed to the other two channels through LDS
     const bool share = !DENSE && !seam_l0 && A.lockstep == 2;
     // the three planes of level l+1 this channel expands: a_c, b_c of G_{l+1} and channel c of E_{l+1}

@@ -182,14 +182,15 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
     const __amdgpu_buffer_rsrc_t rs = x_rsrc<PX>(pa, src_pr, src_q);
     const XShift ms = x_shift<PX>(pa, src_pr, src_q);
     // rows src_y0.. of the pair's index plane (the slot of level-0 plane 0)
-    const float* idx_rows = in + ((size_t)src_pr * 7 * bd.h + src_y0) * pitch;
+    const int idx_pr = index_owner(pa, src_pr);  // (an equal pair of the call may own the plane and its flags)
+    const float* idx_rows = in + ((size_t)idx_pr * 7 * bd.h + src_y0) * pitch;
     // Element indices of the next tile, produced one tile ahead of the gather that consumes them: loaded from the index
     // plane (frame channels) or computed (the mosaic is a pure shift).
     f4 nidx[SRC ? 16 : 1];
     // index tile t of this block's band: from the index plane, or all "outside" when k_src_index left the tile's flag set
     // frame channels: tile t of this band lies outside the frame altogether (k_src_index's flag): its samples are +0
     auto tile_outside = [&](int t) -> bool {
-        if constexpr (SRC) return gen_frame && zi.flags && zi.flags[zi.index(src_pr, src_y0 >> 6, t)];
+        if constexpr (SRC) return gen_frame && zi.flags && zi.flags[zi.index(idx_pr, src_y0 >> 6, t)];
         // planes of G_1 / G_2: `zi` carries the level's G column flags (g_cols; per-plane bands) -- a flagged tile column was not stored
         return zi.flags && zi.flags[zi.index(plane, 0, t)];
     };

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(192) void k_vv_x_m(const float* __restrict__ in, fl
     const bool gen_frame = SRC && !gen_mask && src_q < 3 && !a_is_dense(pa), gen_mosaic = SRC && !gen_mask && !gen_frame;
     const __amdgpu_buffer_rsrc_t rs = x_rsrc<PX>(pa, src_pr, src_q);
     const XShift ms = x_shift<PX>(pa, src_pr, src_q);
-    const float* idx_rows = in + ((size_t)src_pr * 7 * bd.h + band_y0) * pitch;  // rows band_y0.. of the pair's index plane
+    const float* idx_rows = in + ((size_t)index_owner(pa, src_pr) * 7 * bd.h + band_y0) * pitch;  // rows band_y0.. of the index plane the pair reads
     const float* ib = in + (size_t)line0 * pitch;
     float* ob = out + (size_t)line0 * pitch;
     const int ntiles = (w + TS - 1) / TS;

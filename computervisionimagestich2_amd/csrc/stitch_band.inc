@@ -88,6 +88,7 @@ int band_compose(stitch_band* b, const PX* d_frame, int fw, int fh, const double
     pa.frame[0] = d_frame, pa.mosaic[0] = d_mosaic;
     std::memcpy(pa.map[0].p, pm, sizeof pa.map[0].p);
     pa.fw[0] = fw, pa.fh[0] = fh, pa.mw[0] = mw, pa.mh[0] = mh, pa.ox[0] = ox, pa.oy[0] = oy, pa.offx[0] = offx, pa.offy[0] = offy;
+    set_index_owners(pa, 1, nullptr);  // a band computes its plane on every compose
     const BandLevel& a = b->lv[0];
     b->px = (int)sizeof(PX);
     band_set_src_l0(*b, b->src_l0_next);

@@ -20,6 +20,7 @@
 
 #include "stitch.h"
 #include "stitch_g_flags.h"
+#include "stitch_index_plane.h"
 #include "stitch_handoff.h"
 #include "stitch_mask_rows.h"
 #include "stitch_panorama.h"
@@ -152,6 +153,7 @@ int pyramid_levels(int w, int h, int level_rule, int* lw, int* lh) {
 }
 
 constexpr int WF_CTRL_WORDS = 4 * 16 + 16;  // band-queue heads of up to 4 levels (64 bytes apart) + the abort word
+constexpr int IDX_HEAD_WORDS = 32, IDX_TODO_WORD = 16;  // in front of a plan's seam records: three counts, from word 16 the slots' todo words (k_index_keys)
 constexpr int WF_STICKY_WORDS = 16;         // behind them, outside what a launch sequence clears: the plan's count of timed-out waits and,
                                             // from word 2, its three 64-bit hand-off counts (stitch_plan_handoff_counts)
 
@@ -197,6 +199,13 @@ struct stitch_plan : PlanShape {
     unsigned long long* co_dbg = nullptr;  // STITCH_COARSE_STAMP=1: k_coarse's phase stamps of the last launch (diagnostics)
     SeamDev* d_seam = nullptr;
     SeamDev* h_seam = nullptr;  // pinned
+    // The level-0 index planes in the plan's slots (k_index_keys): per slot what its plane and `zi` bytes were computed from, and in
+    // front of the seam records IDX_HEAD_WORDS words -- the last call's three counts, then per slot "compute the plane in this call".
+    // The head travels to the pinned copy with the seam records.
+    IndexKey* idx_keys = nullptr;
+    unsigned* idx_head = nullptr;    // device: IDX_HEAD_WORDS words in front of d_seam
+    unsigned* h_idx_head = nullptr;  // pinned: the same words in front of h_seam (the allocation h_seam lives in)
+    bool last_idx = false;           // the last call went through k_index_keys (stitch_plan_index_counts)
     hipStream_t last_stream = nullptr;
     bool pending = false;
     VVK vvk{};
@@ -613,7 +622,8 @@ int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, 
         StageTimer t(p, s, STITCH_K_MASK, 0);
         k_mask<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(a.g, a.w, a.pitch, a.ps, p->d_seam);
     }
-    HIPCHK(hipMemcpyAsync(p->h_seam, p->d_seam, sizeof(SeamDev) * n, hipMemcpyDeviceToHost, s));
+    // (with the words in front of them: the index planes' counts of this call)
+    HIPCHK(hipMemcpyAsync(p->h_idx_head, p->idx_head, sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * n, hipMemcpyDeviceToHost, s));
     return launch_check("seam/mask");
 }
 
@@ -625,6 +635,13 @@ int check_plan_call(stitch_plan* p, const void* a, const void* b, const void* ou
     return STITCH_OK;
 }
 
+// Pairs i and j of a call have the same index plane: the fields of IndexKey, by bit pattern (one pixel type per call)
+template <typename PX>
+bool same_index_key(const PairArgs<PX>& pa, int i, int j) {
+    return std::memcmp(pa.map[i].p, pa.map[j].p, sizeof pa.map[i].p) == 0 && std::memcmp(&pa.offx[i], &pa.offx[j], sizeof(float)) == 0 &&
+           std::memcmp(&pa.offy[i], &pa.offy[j], sizeof(float)) == 0 && pa.fw[i] == pa.fw[j] && pa.fh[i] == pa.fh[j];
+}
+
 // The launch sequence of n pairs (or of one dense-canvas blend, pa.a_dense): S1, seam scan, REDUCE, collapse.
 // given: the pairs' seams as their four integers (stitch_dev_pairs_seamed_*), or nullptr for the scan.
 template <typename PX>
@@ -632,6 +649,10 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
     const Level& a = p->lv[0];
     int rc;
     const CallForm c = call_form(*p, n, src, pa.a_dense != 0);  // every kernel choice of REDUCE and the collapse, before the first launch
+    for (int i = 0; i < n; ++i) {  // a PairArgs that did not go through set_index_owners (all zeros: every pair reading slot 0) stops here
+        const int o = pa.idx_pr[i];
+        if (o < 0 || o > i || pa.idx_pr[o] != o || !same_index_key(pa, i, o)) return fail(STITCH_ERR_ARG, "pairs: pair %d names slot %d as the owner of its index plane", i, o);
+    }
     // source-fused: level 0 is a function of the inputs, evaluated by its three consumers (a warped frame through an index
     // plane, dense images as pure shifts)
     ZeroTiles zi{};
@@ -645,14 +666,22 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
         StageTimer t(p, s, STITCH_K_COMPOSE, 0);
         if (src) {
             if (!pa.a_dense) {
-                if (zi.flags) k_fill_bytes<<<64, 256, 0, s>>>(zi.flags, (size_t)n * zi.NR * zi.NC, (uint8_t)1);
-                k_src_index<PX><<<grid_xy(a.pitch, (a.h + SI_ROWS - 1) / SI_ROWS, n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, zi);
-            }
-        } else if (pa.a_dense)
-            k_load_canvases<PX><<<grid_xy(a.pitch, a.h), 256, 0, s>>>(pa.frame[0], pa.mosaic[0], a.g, a.w, a.h, a.pitch, a.ps);
-        else
-            k_compose<PX><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, 0);
+                // the index plane of a slot is computed where the slot's record (IndexKey) does not describe this call's pair already,
+                // and once for pairs of the call with equal keys; decided on the device, in stream order (k_index_keys)
+                unsigned* todo = p->idx_head + IDX_TODO_WORD;
+                k_index_keys<PX><<<1, 64, 0, s>>>(pa, n, p->idx_keys, todo, p->idx_head);
+                if (zi.flags) k_zi_preset<<<dim3(4, n), 256, 0, s>>>(zi.flags, zi.NR * zi.NC, todo);
+                k_src_index<PX><<<grid_xy(a.pitch, std::min((a.h + SI_ROWS - 1) / SI_ROWS, SI_WGY), n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, zi, 0, todo);
+            }  // (a dense pair has no index plane and writes nothing into the slot: the record stands)
+        } else {
+            if (pa.a_dense)
+                k_load_canvases<PX><<<grid_xy(a.pitch, a.h), 256, 0, s>>>(pa.frame[0], pa.mosaic[0], a.g, a.w, a.h, a.pitch, a.ps);
+            else
+                k_compose<PX><<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, 0);
+            k_index_forget<<<1, 64, 0, s>>>(p->idx_keys, n);  // level 0 of slots 0 .. n-1 now holds planes, not an index
+        }
     }
+    p->last_idx = src && !pa.a_dense;
     if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given))) return rc;
     p->last_form = c;
     if ((rc = run_reduce<PX>(p, c, s, pa, zi))) return rc;
@@ -682,6 +711,7 @@ int dev_blend(stitch_plan* p, const PX* d_a, const PX* d_b, PX* d_out, void* str
     pa.fw[0] = pa.mw[0] = p->cw;
     pa.fh[0] = pa.mh[0] = p->ch;
     pa.a_dense = 1;
+    set_index_owners(pa, 1, nullptr);
     OutPtrs<PX> outs{};
     outs.p[0] = d_out;
     const size_t bytes = sizeof(PX) * (size_t)3 * p->cw * p->ch;
@@ -734,6 +764,16 @@ int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, co
         pa.offx[i] = d[i].offx;
         pa.offy[i] = d[i].offy;
     }
+    // one index plane per distinct key of the call: a pair's owner is the first pair with the same key
+    int owner[MAXB];
+    for (int i = 0; i < n; ++i) {
+        owner[i] = i;
+#ifndef STITCH_NO_INDEX_REUSE
+        for (int j = 0; j < i && owner[i] == i; ++j)
+            if (same_index_key(pa, i, j)) owner[i] = j;
+#endif
+    }
+    set_index_owners(pa, n, owner);
     bool src = source_fused_call(*p, n);
     for (int i = 0; i < n; ++i)  // 32-bit element indices and byte offsets into one channel plane
         src = src && (unsigned long long)d[i].fw * d[i].fh * sizeof(PX) < 0xfffffff0ULL && (unsigned long long)d[i].mw * d[i].mh * sizeof(PX) < 0xfffffff0ULL;
@@ -1553,7 +1593,9 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     // x-sweep state [4][lines] followed by the y state the wavefront kernel leaves [4][planes][pitch]
     const size_t state_n = 4 * 7 * B * (size_t)(v0.h + 64) + 4 * 7 * B * (size_t)std::max(v0.h + 64, v0.pitch);
     const size_t st_off = take(sizeof(double) * state_n);
-    const size_t seam_off = take(sizeof(SeamDev) * B);
+    static_assert(sizeof(unsigned) * IDX_HEAD_WORDS % alignof(SeamDev) == 0 && MAXB <= IDX_HEAD_WORDS - IDX_TODO_WORD, "the words in front of the seam records");
+    const size_t seam_off = take(sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * B);
+    const size_t ik_off = take(sizeof(IndexKey) * B);  // zero at creation: no slot holds a plane
     const size_t side_off = take(sizeof(float) * B * v0.pitch);
     const size_t zp_off = take(4096);  // zeros for good (k_vv_xby_m's loader reads a flagged tile from here)
     p->arena_bytes = off;
@@ -1577,7 +1619,9 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     p->T = reinterpret_cast<float*>(base + t_off);
     p->T2 = o.blur_kind == 1 ? reinterpret_cast<float*>(base + t2_off) : nullptr;
     p->state = reinterpret_cast<double*>(base + st_off);
-    p->d_seam = reinterpret_cast<SeamDev*>(base + seam_off);
+    p->idx_head = reinterpret_cast<unsigned*>(base + seam_off);
+    p->d_seam = reinterpret_cast<SeamDev*>(p->idx_head + IDX_HEAD_WORDS);
+    p->idx_keys = reinterpret_cast<IndexKey*>(base + ik_off);
     p->side = reinterpret_cast<float*>(base + side_off);
     p->zero_page = reinterpret_cast<const float*>(base + zp_off);
     if (p->has_wf) {
@@ -1607,7 +1651,7 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     if (p->stamp_wf) p->stamp_wf = stamp_buffer(&p->wf_dbg, (size_t)p->wf_max_wgs * 8);  // one record per persistent workgroup, sized from the workgroup count actually used
     if (p->stamp_co) p->stamp_co = stamp_buffer(&p->co_dbg, (size_t)CO_MAXL * 8);
     // the slack rows and pitch padding are read by partial tiles: give them defined (zero) contents once
-    if (hipMemset(p->arena, 0, off) != hipSuccess || hipHostMalloc((void**)&p->h_seam, sizeof(SeamDev) * B) != hipSuccess) {
+    if (hipMemset(p->arena, 0, off) != hipSuccess || hipHostMalloc((void**)&p->h_idx_head, sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * B) != hipSuccess) {
         stitch_plan_destroy(p);
         return fail(STITCH_ERR_HIP, "plan_create: workspace initialisation failed");
     }
@@ -1629,7 +1673,8 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
             return fail(STITCH_ERR_HIP, "plan_create: table upload failed");
         }
     }
-    std::memset(p->h_seam, 0, sizeof(SeamDev) * B);
+    std::memset(p->h_idx_head, 0, sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * B);
+    p->h_seam = reinterpret_cast<SeamDev*>(p->h_idx_head + IDX_HEAD_WORDS);
     if (p->has_wf) {
         if (hipHostMalloc((void**)&p->h_wf_abort, sizeof(unsigned)) != hipSuccess) {
             stitch_plan_destroy(p);
@@ -1651,7 +1696,7 @@ void stitch_plan_destroy(stitch_plan* p) {
     }
     for (auto e : p->free_events) (void)hipEventDestroy(e);
     if (p->arena) (void)hipFree(p->arena);
-    if (p->h_seam) (void)hipHostFree(p->h_seam);
+    if (p->h_idx_head) (void)hipHostFree(p->h_idx_head);  // (h_seam lies in it)
     if (p->h_wf_abort) (void)hipHostFree(p->h_wf_abort);
     if (p->d7_dbg) {
         const int nc = p->d7_dbg_chunks;
@@ -1817,6 +1862,16 @@ int stitch_plan_g_flag_counts(stitch_plan* p, uint64_t out[2]) {
     return STITCH_OK;
 }
 
+int stitch_plan_index_counts(stitch_plan* p, uint32_t out[3]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    for (int i = 0; i < 3; ++i) out[i] = p->last_idx ? p->h_idx_head[i] : 0u;  // (the words of a call without an index plane are an earlier call's)
+    return STITCH_OK;
+}
+
 int stitch_plan_mask_row_counts(stitch_plan* p, uint64_t out[2]) {
     if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
     if (p->pending) {
@@ -1841,6 +1896,9 @@ int stitch_plan_clear_fault(stitch_plan* p) {
         p->pending = false;
     }
     if (p->h_wf_abort) p->wf_abort_seen = *p->h_wf_abort;
+    // no slot's index plane is taken on trust after a fault
+    HIPCHK(hipMemsetAsync(p->idx_keys, 0, sizeof(IndexKey) * p->cap, p->last_stream));
+    HIPCHK(hipStreamSynchronize(p->last_stream));
     return STITCH_OK;
 }
 
