@@ -174,6 +174,12 @@ RIG_SEAMS_SIGNATURES = _signatures(
     ("stitch_rig_step_canvas", i32, vp, i32, vp, vp),
 )
 
+# The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
+# holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
+COLLAPSE_SIDES_SIGNATURES = _signatures(
+    ("stitch_plan_collapse_sides", i32, vp, i32, vp), ("stitch_dev_check_collapse_sides", i32, i32, i32, i32, i32, i32, vp, vp, vp),
+)
+
 _lib = None
 
 
@@ -206,6 +212,10 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
+        for name, (res, args) in COLLAPSE_SIDES_SIGNATURES.items():  # include/stitch_collapse_sides.h (likewise)
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = res, args
         _lib = L
     return _lib
 
@@ -1087,6 +1097,14 @@ def dev_check_collapse_taps(w, h, probe):
     return t.value, m.value
 
 
+def dev_check_collapse_sides(w, h, probe, branch, seam_x):
+    """stitch_dev_check_collapse_sides: (samples compared, samples that differ between k_collapse4's one-sided forms and k_collapse,
+    (a-only, b-only, both) column blocks of the k_collapse4 launch)."""
+    t, m, n = C.c_ulonglong(), C.c_ulonglong(), (C.c_int * 3)()
+    _chk(lib().stitch_dev_check_collapse_sides(int(w), int(h), int(probe), int(branch), int(seam_x), C.byref(t), C.byref(m), n))
+    return t.value, m.value, tuple(int(v) for v in n)
+
+
 def dev_quantize(src, out=None):
     """float mosaic -> unsigned char by truncation (CImg.h:11167-11182, behind ImageProcess.cpp:772)."""
     import torch
@@ -1249,6 +1267,13 @@ class Plan(_Handle):
         whose plane stood from an earlier call, pairs that read the plane of an earlier pair of the call (stitch_plan_index_counts)."""
         out = (C.c_uint32 * 3)()
         _chk(lib().stitch_plan_index_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def collapse_sides(self, pair=0):
+        """-> (a_only, b_only, both): 256-column blocks of the last call's level-0 collapse of `pair` that read only image a, only
+        image b, both (stitch_plan_collapse_sides)."""
+        out = (C.c_int * 3)()
+        _chk(lib().stitch_plan_collapse_sides(self._h, int(pair), out))
         return tuple(int(v) for v in out)
 
     def set_handoff_spin_limit(self, polls):

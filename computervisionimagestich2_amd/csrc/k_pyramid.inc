@@ -449,18 +449,24 @@ struct SrcRow4 {
         fr = plane_rsrc(pa.frame[pr] + c * fe, fe);
     }
     // raw bits of a[j], b[j] of canvas row y; idx = the four byte offsets k_src_index left (or "outside"; unused with AD)
+    // SIDE (collapse_cols4): 1 leaves b as it is and reads only a, 2 leaves a as it is and reads only b
+    template <int SIDE = 0>
     __device__ __forceinline__ void issue(const u4 idx, int y, float a[4], float b[4]) const {
-        if constexpr (AD)
-            fa.issue(y, a);
-        else {
+        if constexpr (SIDE != 2) {
+            if constexpr (AD)
+                fa.issue(y, a);
+            else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = buf_raw<PX>(fr, idx[j]);  // "outside" is beyond the plane: reads 0
+                for (int j = 0; j < 4; ++j) a[j] = buf_raw<PX>(fr, idx[j]);  // "outside" is beyond the plane: reads 0
+            }
         }
+        if constexpr (SIDE != 1) {
 #if STITCH_C4_ABLATE == 3 || STITCH_C4_ABLATE >= 8  // the mosaic is not read
-        for (int j = 0; j < 4; ++j) b[j] = (float)y;
+            for (int j = 0; j < 4; ++j) b[j] = (float)y;
 #else
-        mo.issue(y, b);
+            mo.issue(y, b);
 #endif
+        }
     }
     // raw bits -> the values k_compose / k_load_canvases would have stored
     __device__ __forceinline__ void finish(float a[4], float b[4]) const {
@@ -473,6 +479,7 @@ struct SrcRow4 {
 };
 struct NoSrcRow4 {
     __device__ __forceinline__ NoSrcRow4(const NoPairArgs&, int, int, int, int) {}
+    template <int SIDE = 0>
     __device__ __forceinline__ void issue(const u4, int, float[4], float[4]) const {}
     __device__ __forceinline__ void finish(float[4], float[4]) const {}
 };
@@ -503,8 +510,14 @@ struct SrcRow4Of<OUT, true, AD> {
 // load, the tap pair of a column selected per lane.  Odd level widths need it: their step (sw - 1) / (w - 1) drifts by a whole
 // sample over the row, so the fixed pattern holds for well under half of the columns (1 792 of 4 421), and with it every column
 // group but the last few of a row qualifies.  About 30 more selects per source row; even widths keep the fixed pattern.
+//
+// SIDE (a level 0 whose mask is the seam's step, chosen per workgroup by k_collapse4): 0 reads both images; 1: the step is 1 at every
+// column of the workgroup, only image a is read; 2: the step is 0, only image b.  blend_ref(la, lb, m) with m = 1 is la and with
+// m = 0 is lb for finite samples, except that a kept term of +-0 takes its sign from the dropped one -- which the sum with ee erases
+// unless ee is -0.  A row in which some lane has a kept term of +-0 under an ee of -0 (both by bit pattern) is therefore redone with
+// the dropped image loaded and the full arithmetic; that block sits behind the row's last wait and loads what it needs itself.
 typedef __attribute__((address_space(3))) f4 lds_f4;
-template <typename OUT, bool DENSE, bool AD, bool GEN, bool MR = false>
+template <typename OUT, bool DENSE, bool AD, bool GEN, bool MR = false, int SIDE = 0>
 __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A, int c, int x0, int y0, int y1, int pr, float* sh, MaskRowsArg mr = MaskRowsArg{}) {
     const int pitch = A.pitch, sh_ = A.sh, spitch = A.spitch, opitch = A.opitch;
     const size_t ps = A.ps, sps = A.sps, ops = A.ops;
@@ -540,7 +553,8 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
 #if STITCH_G_IGNORE_COARSER & 1
     const bool za = false, zb = false;
 #else
-    const bool za = g_span_flag(A.gzn, A.gncn, pr * 7 + c, s0, s0 + 3), zb = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, s0, s0 + 3);
+    // (of the plane that is read: a one-sided form looks the other one up only where it redoes a row)
+    const bool za = SIDE != 2 && g_span_flag(A.gzn, A.gncn, pr * 7 + c, s0, s0 + 3), zb = SIDE != 1 && g_span_flag(A.gzn, A.gncn, pr * 7 + 3 + c, s0, s0 + 3);
 #endif
 #if STITCH_G_IGNORE_OWN & 1
     const bool zga = false, zgb = false;
@@ -554,13 +568,30 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
         const double2 a01 = *reinterpret_cast<const double2*>(tb.ax + x0), a23 = *reinterpret_cast<const double2*>(tb.ax + x0 + 2);
         axs[0] = a01.x, axs[1] = a01.y, axs[2] = a23.x, axs[3] = a23.y;
     }
-    // x pass of one source row for the three planes
+    // x pass of the 16 bytes of one plane's source row
+    auto xl4 = [&](const f4 v, float X[4]) {
+        if constexpr (GEN) {
+            const float x_ = v.x, y_ = v.y, z_ = v.z, w_ = v.w;
+            X[0] = lerp_ref(axs[0], x_, y_);
+            const float a1 = o1 ? y_ : x_, a2 = o2 == 0 ? x_ : o2 == 1 ? y_ : z_, a3 = o3 == 0 ? x_ : o3 == 1 ? y_ : z_;
+            X[1] = lerp_ref(axs[1], a1, e1 ? a1 : o1 ? z_ : y_);
+            X[2] = lerp_ref(axs[2], a2, e2 ? a2 : o2 == 0 ? y_ : o2 == 1 ? z_ : w_);
+            X[3] = lerp_ref(axs[3], a3, e3 ? a3 : o3 == 0 ? y_ : o3 == 1 ? z_ : w_);
+        } else {
+            X[0] = lerp_ref(axs[0], v.x, v.y);
+            X[1] = lerp_ref(axs[1], v.y, v.z);
+            X[2] = lerp_ref(axs[2], v.y, v.z);
+            X[3] = lerp_ref(axs[3], v.z, v.w);
+        }
+    };
+    // x pass of one source row for the three planes (a one-sided form: for the two it reads; X[q] of the other is never touched)
     auto xrow = [&](int row, float X[3][4]) {
         const unsigned o = (unsigned)row * (unsigned)spitch + (unsigned)s0;
 #if STITCH_C4_ABLATE == 1 || STITCH_C4_ABLATE >= 8  // counter experiments only (wrong results): the coarser level is not read
         const f4 v[3] = {f4{0.f, 0.f, 0.f, (float)o}, f4{0.f, 0.f, 0.f, 1.f}, f4{0.f, 0.f, 0.f, 2.f}};
 #else
-        const f4 v[3] = {*reinterpret_cast<const f4u*>(sa + (za ? zsa : o)), *reinterpret_cast<const f4u*>(sb + (zb ? zsb : o)), *reinterpret_cast<const f4u*>(se + o)};
+        const f4 v[3] = {SIDE != 2 ? *reinterpret_cast<const f4u*>(sa + (za ? zsa : o)) : f4{0.f, 0.f, 0.f, 0.f},
+                         SIDE != 1 ? *reinterpret_cast<const f4u*>(sb + (zb ? zsb : o)) : f4{0.f, 0.f, 0.f, 0.f}, *reinterpret_cast<const f4u*>(se + o)};
 #endif
 #if STITCH_C4_OPAQUE_ALPHA
         // registers are what bounds the number of resident wavefronts here: keep the four alphas, not also the four
@@ -570,19 +601,17 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
 #endif
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            if constexpr (GEN) {
-                const float x_ = v[q].x, y_ = v[q].y, z_ = v[q].z, w_ = v[q].w;
-                X[q][0] = lerp_ref(axs[0], x_, y_);
-                const float a1 = o1 ? y_ : x_, a2 = o2 == 0 ? x_ : o2 == 1 ? y_ : z_, a3 = o3 == 0 ? x_ : o3 == 1 ? y_ : z_;
-                X[q][1] = lerp_ref(axs[1], a1, e1 ? a1 : o1 ? z_ : y_);
-                X[q][2] = lerp_ref(axs[2], a2, e2 ? a2 : o2 == 0 ? y_ : o2 == 1 ? z_ : w_);
-                X[q][3] = lerp_ref(axs[3], a3, e3 ? a3 : o3 == 0 ? y_ : o3 == 1 ? z_ : w_);
-            } else {
-                X[q][0] = lerp_ref(axs[0], v[q].x, v[q].y);
-                X[q][1] = lerp_ref(axs[1], v[q].y, v[q].z);
-                X[q][2] = lerp_ref(axs[2], v[q].y, v[q].z);
-                X[q][3] = lerp_ref(axs[3], v[q].z, v[q].w);
-            }
+            if ((q == 0 && SIDE == 2) || (q == 1 && SIDE == 1)) continue;
+            xl4(v[q], X[q]);
+        }
+    };
+    // X1 = X2 and back, of the planes that are read
+    auto xcopy = [&](float D[3][4], const float S[3][4]) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if ((q == 0 && SIDE == 2) || (q == 1 && SIDE == 1)) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) D[q][j] = S[q][j];
         }
     };
     float X1[3][4], X2[3][4];
@@ -612,12 +641,23 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
             src.issue(c == 0 && STITCH_C4_ABLATE == 6 ? *reinterpret_cast<const u4*>(g + o) : STITCH_C4_ABLATE >= 8 ? u4{0u, 4u, 8u, 12u} : calc, y, ga, gb);
         }
 #else
-            src.issue(AD ? u4{0u, 0u, 0u, 0u} : *reinterpret_cast<const u4*>(g + o), y, ga, gb);
+        {
+            u4 idx = {0u, 0u, 0u, 0u};
+            if constexpr (!AD && SIDE != 2) idx = *reinterpret_cast<const u4*>(g + o);  // the index word is image a's
+            src.template issue<SIDE>(idx, y, ga, gb);
+        }
 #endif
         else {
-            const f4 va = *reinterpret_cast<const f4*>(g + (zga ? zg : o + c * ps)), vb = *reinterpret_cast<const f4*>(g + (zgb ? zg : o + (3 + c) * ps));
+            if constexpr (SIDE != 2) {
+                const f4 va = *reinterpret_cast<const f4*>(g + (zga ? zg : o + c * ps));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ga[j] = va[j], gb[j] = vb[j];
+                for (int j = 0; j < 4; ++j) ga[j] = va[j];
+            }
+            if constexpr (SIDE != 1) {
+                const f4 vb = *reinterpret_cast<const f4*>(g + (zgb ? zg : o + (3 + c) * ps));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gb[j] = vb[j];
+            }
         }
         if (share) {
             if (c == 0) vm = *reinterpret_cast<const f4*>(g + om + 6 * ps);
@@ -630,7 +670,7 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
         if (!seam_l0) vm = *reinterpret_cast<const f4*>(g + om + 6 * ps);
 #endif
     };
-    float ga[4], gb[4];
+    float ga[4] = {0.f, 0.f, 0.f, 0.f}, gb[4] = {0.f, 0.f, 0.f, 0.f};  // (raw 0 = sample 0: what a one-sided form leaves of the other image)
     f4 vm = {0.f, 0.f, 0.f, 0.f};
 #if STITCH_C4_PREFETCH
     // the row's loads are issued one row ahead of their use
@@ -646,22 +686,16 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
         const int iy = tb.iy[y], iy2 = iy < sh_ - 1 ? iy + 1 : iy;
         const double ay = tb.ay[y];
         if (iy != cur1) {
-            if (iy == cur2) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) X1[q][j] = X2[q][j];
-            } else
+            if (iy == cur2)
+                xcopy(X1, X2);
+            else
                 xrow(iy, X1);
             cur1 = iy;
         }
         if (iy2 != cur2) {
-            if (iy2 == cur1) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) X2[q][j] = X1[q][j];
-            } else
+            if (iy2 == cur1)
+                xcopy(X2, X1);
+            else
                 xrow(iy2, X2);
             cur2 = iy2;
         }
@@ -685,20 +719,93 @@ __device__ __forceinline__ void collapse_cols4(const CollapseArgs<OUT, DENSE>& A
             for (int j = 0; j < 4; ++j) m4[j] = vm[j];
         }
         float v4[4];
+        if constexpr (SIDE == 0) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float ea = lerp_ref(ay, X1[0][j], X2[0][j]);
-            const float eb = lerp_ref(ay, X1[1][j], X2[1][j]);
-            const float ee = lerp_ref(ay, X1[2][j], X2[2][j]);
-            const float la = ga[j] - ea;
-            const float lb = gb[j] - eb;
-            const float s_ = blend_ref(la, lb, m4[j]);
-            float v = s_ + ee;
-            if (v > 255.f)
-                v = 255.f;
-            else if (v < 0.f)
-                v = 0.f;
-            v4[j] = v;
+            for (int j = 0; j < 4; ++j) {
+                const float ea = lerp_ref(ay, X1[0][j], X2[0][j]);
+                const float eb = lerp_ref(ay, X1[1][j], X2[1][j]);
+                const float ee = lerp_ref(ay, X1[2][j], X2[2][j]);
+                const float la = ga[j] - ea;
+                const float lb = gb[j] - eb;
+                const float s_ = blend_ref(la, lb, m4[j]);
+                float v = s_ + ee;
+                if (v > 255.f)
+                    v = 255.f;
+                else if (v < 0.f)
+                    v = 0.f;
+                v4[j] = v;
+            }
+        } else {
+            constexpr int K = SIDE == 1 ? 0 : 1;  // the plane that is kept
+            const float* gk = SIDE == 1 ? ga : gb;
+            bool redo = false;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float ek = lerp_ref(ay, X1[K][j], X2[K][j]);
+                const float ee = lerp_ref(ay, X1[2][j], X2[2][j]);
+                const float lk = gk[j] - ek;  // blend_ref's value, but for the sign of a zero
+                float v = lk + ee;
+                redo = redo || ((__float_as_uint(lk) << 1) == 0u && __float_as_uint(ee) == 0x80000000u);
+                if (v > 255.f)
+                    v = 255.f;
+                else if (v < 0.f)
+                    v = 0.f;
+                v4[j] = v;
+            }
+#ifndef STITCH_C4_NO_SIDE_REDO  // (defined only to prove that the signed-zero probe of stitch_dev_check_collapse_sides sees the missing sign)
+            if (__builtin_expect(__any(redo), 0)) {
+                // the row again with the dropped image: its sample, its two source rows of G_{l+1}, the full blend.  Everything of
+                // that image is worked out here, from a column number the compiler cannot move out of the row loop: the main loop
+                // keeps no register for it.
+                int xr = x0;
+                asm volatile("" : "+v"(xr));
+                constexpr int D = 1 - K;
+                const float* sd_ = D == 0 ? sa : sb;
+                const unsigned zsd = D == 0 ? zsa : zsb;
+#if STITCH_G_IGNORE_COARSER & 1
+                const bool zd = false;
+#else
+                const bool zd = g_span_flag(A.gzn, A.gncn, pr * 7 + 3 * D + c, tb.ix[xr], tb.ix[xr] + 3);
+#endif
+                float gd[4] = {0.f, 0.f, 0.f, 0.f}, gu[4] = {0.f, 0.f, 0.f, 0.f};
+                const unsigned o = (unsigned)y * (unsigned)pitch + (unsigned)xr;
+                if (use_src) {
+                    const typename SrcRow4Of<OUT, DENSE, AD>::type srd(A.pa, pr, c, xr, A.w);
+                    u4 idx = {0u, 0u, 0u, 0u};
+                    if constexpr (!AD && D == 0) idx = *reinterpret_cast<const u4*>(g + o);
+                    if constexpr (D == 0) {
+                        srd.template issue<1>(idx, y, gd, gu);
+                        srd.finish(gd, gu);
+                    } else {
+                        srd.template issue<2>(idx, y, gu, gd);
+                        srd.finish(gu, gd);
+                    }
+                } else {
+                    const f4 vd = *reinterpret_cast<const f4*>(g + o + (3 * D + c) * ps);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) gd[j] = vd[j];
+                }
+                float D1[4], D2[4];
+                const unsigned sr = (unsigned)tb.ix[xr];  // (= s0)
+                xl4(*reinterpret_cast<const f4u*>(sd_ + (zd ? zsd : (unsigned)iy * (unsigned)spitch + sr)), D1);
+                xl4(*reinterpret_cast<const f4u*>(sd_ + (zd ? zsd : (unsigned)iy2 * (unsigned)spitch + sr)), D2);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float ek = lerp_ref(ay, X1[K][j], X2[K][j]);
+                    const float ed = lerp_ref(ay, D1[j], D2[j]);
+                    const float ee = lerp_ref(ay, X1[2][j], X2[2][j]);
+                    const float lk = gk[j] - ek;
+                    const float ld = gd[j] - ed;
+                    const float s_ = SIDE == 1 ? blend_ref(lk, ld, m4[j]) : blend_ref(ld, lk, m4[j]);
+                    float v = s_ + ee;
+                    if (v > 255.f)
+                        v = 255.f;
+                    else if (v < 0.f)
+                        v = 0.f;
+                    v4[j] = v;
+                }
+            }
+#endif
         }
 #if STITCH_C4_ABLATE == 4  // nothing is stored (unless a sample is a NaN: the compiler must keep the arithmetic)
         if (!(v4[0] != v4[0] || v4[3] != v4[3])) continue;
@@ -725,6 +832,10 @@ constexpr int C4_SUB = 8, C4_THREADS = 3 * WAVE;
 // four-column blocks per strip in the launch: with a block order, strips of eight blocks and more are padded to a multiple of 8
 // (the extra workgroups return at once) so that every block of a strip is renumbered; narrower levels are left as they are
 __host__ __device__ inline int c4_padded_blocks(int nb4, int swizzle) { return swizzle && nb4 >= 8 ? (nb4 + 7) & ~7 : nb4; }
+// A level 0 whose mask is the seam's step (A.seam_l0) takes, per workgroup, the form of collapse_cols4 that reads only the image the
+// step selects: the step is monotone in x, so equal values at the block's first and last column (c4_block_side, stitch_call_form.h:
+// the rule stitch_plan_collapse_sides counts by) mean one value over the block.  The record is read on the device, in stream order:
+// a captured call decides again on every replay.  -DSTITCH_NO_C4_SIDES: always both images (A/B libraries).
 template <typename OUT, bool DENSE, bool AD = false, bool GEN = false, bool MR = false>
 __global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(CollapseArgs<OUT, DENSE> A, int nb4, int ncb, MaskRowsArg mr = MaskRowsArg{}) {
     const int pr = blockIdx.z;
@@ -759,7 +870,30 @@ __global__ __launch_bounds__(C4_THREADS, STITCH_C4_WAVES) void k_collapse4(Colla
         }
         const int y0 = strip * A.crows, y1 = min(y0 + A.crows, A.h);
         const int x0 = A.xa + (blk * WAVE + (threadIdx.x & 63)) * 4;
-        if (blk < nb4 && x0 < A.xb) collapse_cols4<OUT, DENSE, AD, GEN, MR>(A, c, x0, y0, y1, pr, c4_sh, mr);
+        if (blk < nb4 && x0 < A.xb) {
+            int side = 0;
+#ifndef STITCH_NO_C4_SIDES
+            if constexpr (DENSE) {
+                if (A.seam_l0) {
+                    const SeamDev& sd = A.seam_l0[pr];
+                    const int xf = A.xa + blk * (4 * WAVE);
+                    side = __builtin_amdgcn_readfirstlane(c4_block_side(sd.branch, sd.start, sd.thr, xf, min(xf + 4 * WAVE - 1, A.xb - 1)));
+#ifdef STITCH_C4_WRONG_SIDE  // (defined only in a hand-check library, to prove that the tests see a one-sided block that reads the other image)
+                    side = side ? 3 - side : 0;
+#endif
+                }
+            }
+#endif
+            if constexpr (DENSE) {
+                if (side == 1)
+                    collapse_cols4<OUT, DENSE, AD, GEN, MR, 1>(A, c, x0, y0, y1, pr, c4_sh, mr);
+                else if (side == 2)
+                    collapse_cols4<OUT, DENSE, AD, GEN, MR, 2>(A, c, x0, y0, y1, pr, c4_sh, mr);
+                else
+                    collapse_cols4<OUT, DENSE, AD, GEN, MR, 0>(A, c, x0, y0, y1, pr, c4_sh, mr);
+            } else
+                collapse_cols4<OUT, DENSE, AD, GEN, MR>(A, c, x0, y0, y1, pr, c4_sh, mr);
+        }
     } else {
         const int y0 = blockIdx.y * A.crows, y1 = min(y0 + A.crows, A.h);
         const int r = blockIdx.x - nb4p, cb = r % ncb, sub = r / ncb, rows = (A.crows + C4_SUB - 1) / C4_SUB;

@@ -147,6 +147,25 @@ inline void general_range(const std::vector<int32_t>& idx, int w, int sw, int sh
     *xb = x0 / 256 * 256;
 }
 
+// ---- the level-0 collapse of a call with the step mask: which image(s) a 256-column block of k_collapse4 reads --------------------
+// The level-0 mask of such a call is the seam's step (k_sweeps.inc, mask_step): branch 0: 1 where (double)x < thr, otherwise 1 where
+// x >= start -- one function of x for every row, monotone in x.  (constexpr: the kernel evaluates the same lines.)
+constexpr int c4_step_at(int branch, int start, double thr, int x) { return branch == 0 ? ((double)x < thr ? 1 : 0) : (x >= start ? 1 : 0); }
+// The block whose first and last live columns are xf and xl: 1 = the step is 1 on all of it (only image a is read), 2 = it is 0 (only
+// image b), 0 = the step changes inside it (both).
+constexpr int c4_block_side(int branch, int start, double thr, int xf, int xl) {
+    return c4_step_at(branch, start, thr, xf) != c4_step_at(branch, start, thr, xl) ? 0 : c4_step_at(branch, start, thr, xf) ? 1 : 2;
+}
+// counts[0..2] = the blocks of columns [xa, xb) (k_collapse4's range of the launch: block b starts at xa + 256 b) that read only a, only
+// b, both.  sides == 0 (no step mask, or a library that always reads both): every block reads both.
+inline void c4_side_counts(int branch, int start, double thr, int xa, int xb, int sides, int counts[3]) {
+    counts[0] = counts[1] = counts[2] = 0;
+    for (int xf = xa; xf < xb; xf += 256) {
+        const int side = sides ? c4_block_side(branch, start, thr, xf, std::min(xf + 255, xb - 1)) : 0;
+        ++counts[side == 1 ? 0 : side == 2 ? 1 : 2];
+    }
+}
+
 // Level sizes of a w x h canvas (ImageProcess.cpp:675-676, :706-707) -> the level count, 1..32.  0: a non-positive size;
 // -1: a count outside 1..32; -(2 + i): level i has a zero dimension (the reference degenerates there).
 inline int pyramid_sizes(int w, int h, int level_rule, int* lw, int* lh) {

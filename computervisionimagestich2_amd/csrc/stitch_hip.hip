@@ -21,6 +21,7 @@
 #include "stitch.h"
 #include "stitch_g_flags.h"
 #include "stitch_index_plane.h"
+#include "stitch_collapse_sides.h"
 #include "stitch_handoff.h"
 #include "stitch_mask_rows.h"
 #include "stitch_panorama.h"
@@ -206,6 +207,10 @@ struct stitch_plan : PlanShape {
     unsigned* idx_head = nullptr;    // device: IDX_HEAD_WORDS words in front of d_seam
     unsigned* h_idx_head = nullptr;  // pinned: the same words in front of h_seam (the allocation h_seam lives in)
     bool last_idx = false;           // the last call went through k_index_keys (stitch_plan_index_counts)
+    // the last call's level-0 launch of k_collapse4 (stitch_plan_collapse_sides): its column range as the caller's addresses left it,
+    // and whether its workgroups chose a form by the seam's step
+    int c4_l0_xa = 0, c4_l0_xb = 0;
+    bool c4_l0_sides = false;
     hipStream_t last_stream = nullptr;
     bool pending = false;
     VVK vvk{};
@@ -591,6 +596,12 @@ int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hi
                                       c.c4_lock, c.c4_swizzle};
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
             launch_collapse(A, CollapseKind{c.src && c.a_dense, f.gen, false, false, false}, cols, strips, n, mra, s);
+            p->c4_l0_xa = A.xa, p->c4_l0_xb = A.xb;
+#ifdef STITCH_NO_C4_SIDES
+            p->c4_l0_sides = false;
+#else
+            p->c4_l0_sides = A.seam_l0 != nullptr;
+#endif
         } else {
             OutPtrs<float> eo{};
             eo.p[0] = a.e;
@@ -1872,6 +1883,19 @@ int stitch_plan_index_counts(stitch_plan* p, uint32_t out[3]) {
     return STITCH_OK;
 }
 
+int stitch_plan_collapse_sides(stitch_plan* p, int pair, int counts[3]) {
+    if (!p || !counts) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (pair < 0 || pair >= std::max(1, p->last_n))
+        return fail(STITCH_ERR_ARG, "collapse_sides: pair %d outside the %d pair(s) of the plan's last call", pair, p->last_n);
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    const SeamDev& sd = p->h_seam[pair];
+    c4_side_counts(sd.branch, sd.start, sd.thr, p->c4_l0_xa, p->last_n > 0 ? p->c4_l0_xb : p->c4_l0_xa, p->c4_l0_sides ? 1 : 0, counts);
+    return STITCH_OK;
+}
+
 int stitch_plan_mask_row_counts(stitch_plan* p, uint64_t out[2]) {
     if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
     if (p->pending) {
@@ -2374,6 +2398,94 @@ int stitch_dev_check_collapse_taps(int w, int h, int probe, unsigned long long* 
             }
     *compared = n;
     *mismatches = bad;
+    return STITCH_OK;
+}
+int stitch_dev_check_collapse_sides(int w, int h, int probe, int branch, int seam_x, unsigned long long* compared, unsigned long long* mismatches,
+                                    int counts[3]) {
+    int rc = need_device();
+    if (rc) return rc;
+    if (w < 256 || (w & 1) || h < 4 || (h & 1) || w > 16384 || h > 16384 || probe < 0 || probe > 1 || branch < 0 || branch > 1 || seam_x < 0 || seam_x > w ||
+        !compared || !mismatches)
+        return fail(STITCH_ERR_ARG, "check_collapse_sides: even w >= 256, even h >= 4 (both <= 16384), probe 0 or 1, branch 0 or 1, 0 <= seam_x <= w");
+    const int sw = w / 2, sh = h / 2, pitch = round_up(w, 64), spitch = round_up(sw, 64);
+    const size_t ps = (size_t)pitch * h, sps = (size_t)spitch * sh, ops = (size_t)w * h;
+    std::vector<int32_t> ix, iy;
+    std::vector<double> ax, ay;
+    expand_table(sw, w, ix, ax);
+    expand_table(sh, h, iy, ay);
+    int gxb = 0;
+    general_range(ix, w, sw, sh, &gxb);
+    if (gxb < 256) return fail(STITCH_ERR_ARG, "check_collapse_sides: no block of this width takes the four-column path");
+    // level 0: the six materialised planes of a and b (the mask plane is not read: the mask is the step); level 1: G (a, b) and E.
+    // probe 0: pseudo-random finite samples of both signs.  probe 1, the signed-zero probe: G_1 = +0 and the level-0 samples +0 or -0 in
+    // a pattern of their own per image, so every Laplacian term (sample - 0) is +0 or -0 and kept and dropped terms meet in all four sign
+    // pairs; E_1 alternates, from sample to sample, -0, -1e-45 (the smallest denormal: its interpolation with a zero underflows to -0 or
+    // stays a tiny negative) and +0, shifted by one per row.  blend_ref's zero takes its sign from the dropped term and keeps it through
+    // the sum with an ee of -0: a one-sided form that does not redo those rows leaves wrong signs on both sides of the seam.
+    std::vector<float> g(7 * ps + (size_t)pitch * 64, 0.f), gn(7 * sps + (size_t)spitch * 64, 0.f), en(3 * sps + (size_t)spitch * 64, 0.f);
+    uint32_t lcg = 0x51DE5u ^ (uint32_t)(w * 31 + h);
+    auto rnd = [&]() {
+        lcg = lcg * 1664525u + 1013904223u;
+        return ((int)(lcg >> 8) % 60001 - 30000) / 117.0f;
+    };
+    for (size_t q = 0; q < 6; ++q)
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x)
+                g[q * ps + (size_t)y * pitch + x] = !probe ? rnd() : ((q < 3 ? (x + y + (int)q) % 3 : (x / 3 + y + (int)q) % 2) == 0 ? -0.0f : 0.0f);
+    if (!probe)
+        for (size_t q = 0; q < 6; ++q)
+            for (int y = 0; y < sh; ++y)
+                for (int x = 0; x < sw; ++x) gn[q * sps + (size_t)y * spitch + x] = rnd();
+    for (size_t q = 0; q < 3; ++q)
+        for (int y = 0; y < sh; ++y)
+            for (int x = 0; x < sw; ++x) {
+                const int k = (x + y + (int)q) % 3;
+                en[q * sps + (size_t)y * spitch + x] = !probe ? rnd() : k == 0 ? -0.0f : k == 1 ? -1.401298464e-45f : 0.0f;
+            }
+    SeamDev sd{};
+    sd.branch = branch, sd.start = seam_x, sd.thr = (double)seam_x;
+    const size_t bytes[] = {g.size() * 4, gn.size() * 4, en.size() * 4, 3 * ops * 4, 3 * ops * 4, (size_t)w * 4, (size_t)w * 8, (size_t)h * 4, (size_t)h * 8, sizeof sd};
+    size_t off[11] = {0};
+    for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + align256(bytes[i]);
+    char* base = nullptr;
+    HIPCHK(hipMalloc((void**)&base, off[10] + 256));
+    auto up = [&](int i, const void* src) { return hipMemcpy(base + off[i], src, bytes[i], hipMemcpyHostToDevice) == hipSuccess; };
+    bool ok = up(0, g.data()) && up(1, gn.data()) && up(2, en.data()) && up(5, ix.data()) && up(6, ax.data()) && up(7, iy.data()) && up(8, ay.data()) && up(9, &sd) &&
+              hipMemset(base + off[3], 0xff, 2 * align256(bytes[3])) == hipSuccess;
+    std::vector<float> o1(3 * ops), o2(3 * ops);
+    int got[3] = {0, 0, 0};
+    if (ok) {
+        const ExpandTab tb{(const int32_t*)(base + off[5]), (const double*)(base + off[6]), (const int32_t*)(base + off[7]), (const double*)(base + off[8])};
+        const int crows = 8, strips = (h + crows - 1) / crows;
+        for (int v = 0; v < 2; ++v) {  // v = 0: k_collapse4 with per-lane taps on [0, gxb), one column per work-item behind; v = 1: k_collapse everywhere
+            OutPtrs<float> eo{};
+            eo.p[0] = (float*)(base + off[3 + v]);
+            CollapseArgs<float, true> A{(const float*)(base + off[0]), w, h, pitch, ps, (const float*)(base + off[1]), (const float*)(base + off[2]), sw, sh, spitch, sps,
+                                        tb, eo, w, ops, (const SeamDev*)(base + off[9]), PairArgs<float>{}, 0, crows, 0, v == 0 ? gxb : 0, 1, 0, 1};
+            launch_collapse(A, CollapseKind{false, true, false, false, false}, w, strips, 1, MaskRowsArg{}, nullptr);
+            if (v == 0) {
+#ifdef STITCH_NO_C4_SIDES
+                c4_side_counts(sd.branch, sd.start, sd.thr, A.xa, A.xb, 0, got);
+#else
+                c4_side_counts(sd.branch, sd.start, sd.thr, A.xa, A.xb, 1, got);
+#endif
+            }
+        }
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(o1.data(), base + off[3], bytes[3], hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(o2.data(), base + off[4], bytes[4], hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    const hipError_t e = ok ? hipSuccess : hipGetLastError();
+    (void)hipFree(base);
+    if (!ok) return fail(STITCH_ERR_HIP, "check_collapse_sides: %s", hipGetErrorString(e));
+    *compared = (unsigned long long)o1.size();
+    *mismatches = 0;
+    for (size_t i = 0; i < o1.size(); ++i) {
+        uint32_t a, b;
+        std::memcpy(&a, &o1[i], 4);
+        std::memcpy(&b, &o2[i], 4);
+        *mismatches += a != b;
+    }
+    if (counts) counts[0] = got[0], counts[1] = got[1], counts[2] = got[2];
     return STITCH_OK;
 }
 int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* stream) {
