@@ -180,6 +180,13 @@ COLLAPSE_SIDES_SIGNATURES = _signatures(
     ("stitch_plan_collapse_sides", i32, vp, i32, vp), ("stitch_dev_check_collapse_sides", i32, i32, i32, i32, i32, i32, vp, vp, vp),
 )
 
+# The same for include/stitch_src_runs.h, the level-0 index planes kept in 16-byte runs; tests/test_src_runs_host.py holds it to that
+# header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the three.)
+SRC_RUNS_SIGNATURES = _signatures(
+    ("stitch_plan_src_run_counts", i32, vp, vp), ("stitch_src_run_classes", i32, vp, C.c_float, C.c_float, i32, i32, i32, i32, i32, vp, vp),
+    ("stitch_plan_src_runs_fill", i32, vp, i32),
+)
+
 _lib = None
 
 
@@ -212,7 +219,7 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        for name, (res, args) in COLLAPSE_SIDES_SIGNATURES.items():  # include/stitch_collapse_sides.h (likewise)
+        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()):  # include/stitch_collapse_sides.h, stitch_src_runs.h (likewise)
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1097,6 +1104,16 @@ def dev_check_collapse_taps(w, h, probe):
     return t.value, m.value
 
 
+def src_run_classes(p, offx, offy, fw, fh, cw, ch, px_bytes=4):
+    """stitch_src_run_classes, on the host: -> ((outside, no patch, 1..64, general), classes as a (bands, tiles) uint8 array)."""
+    import numpy as np
+    m = (C.c_double * 8)(*[float(v) for v in p])
+    n = (C.c_uint32 * 4)()
+    cls = np.zeros(((int(ch) + 63) // 64, (int(cw) + 63) // 64), dtype=np.uint8)
+    _chk(lib().stitch_src_run_classes(m, float(offx), float(offy), int(fw), int(fh), int(cw), int(ch), int(px_bytes), n, cls.ctypes.data_as(vp)))
+    return tuple(int(v) for v in n), cls
+
+
 def dev_check_collapse_sides(w, h, probe, branch, seam_x):
     """stitch_dev_check_collapse_sides: (samples compared, samples that differ between k_collapse4's one-sided forms and k_collapse,
     (a-only, b-only, both) column blocks of the k_collapse4 launch)."""
@@ -1268,6 +1285,17 @@ class Plan(_Handle):
         out = (C.c_uint32 * 3)()
         _chk(lib().stitch_plan_index_counts(self._h, out))
         return tuple(int(v) for v in out)
+
+    def src_run_counts(self):
+        """-> (outside, no patch, 1..64 patches, general): 64 x 64 tiles of the index planes the last call's causal x sweep gathered
+        through in 16-byte runs, each plane once (stitch_plan_src_run_counts)."""
+        out = (C.c_uint32 * 4)()
+        _chk(lib().stitch_plan_src_run_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def src_runs_fill(self, byte):
+        """Test hook: every byte of the plan's run arrays set to `byte` (stitch_plan_src_runs_fill)."""
+        _chk(lib().stitch_plan_src_runs_fill(self._h, int(byte)))
 
     def collapse_sides(self, pair=0):
         """-> (a_only, b_only, both): 256-column blocks of the last call's level-0 collapse of `pair` that read only image a, only

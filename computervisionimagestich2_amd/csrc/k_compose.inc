@@ -242,6 +242,87 @@ __global__ __launch_bounds__(256) void k_src_index(PairArgs<PX> pa, float* __res
     }
 }
 
+// The index plane of a slot in 16-byte runs (src_runs_rule.h; float frames).  A map that is close to a translation sends the four
+// samples of an aligned group to four adjacent frame samples almost everywhere, so the causal x sweep of a frame channel can take a
+// group with one 16-byte load from the group's base instead of four 4-byte gathers through four index words.  Per 64x64 tile, in
+// tile_load's element-to-lane layout (lane -> rows lane/16 + 4i, columns 4(lane%16)..+3):
+//   bases    [4][64 lanes][4] words: base of the lane's group i at [i / 4][lane][i % 4] -- four 16-byte loads per lane;
+//   patches  64 records (position in the padded LDS tile, byte offset or off_outside): the samples a base does not deliver;
+//   cls      the number of records, 0..64, or 255 = "general": gathered through the full index plane as before;
+//   live     1 where any pixel of the tile has a sample (for the counts alone: the sweep knows outside tiles from `zi`).
+// Plan-owned per slot with the lifecycle of the index plane and of `zi`: written -- every byte -- by k_src_runs behind k_src_index
+// wherever a slot's todo word is set, kept while the slot's record stands, shared through index_owner.  flags-style null = absent.
+struct SrcRuns {
+    unsigned* bases;
+    uint2* patches;
+    uint8_t* cls;
+    uint8_t* live;
+    int NR, NC;    // 64-row bands per plane, 64-column tiles per row
+    int mosaic16;  // the same sweep takes the mosaic's interior tiles in 16-byte loads too (k_vv_x_fwd; nothing of the arrays is involved)
+    __device__ __forceinline__ size_t tile(int slot, int band, int t) const { return ((size_t)slot * NR + band) * NC + t; }
+};
+// One wavefront per tile of the planes k_src_index has just computed (rows >= ch of a partial last band count as outside); a workgroup
+// loops over the bands gridDim.y apart, so that a call whose planes all stand launches few workgroups that return at once (SR_WGY).
+constexpr int SR_WGY = 8;
+template <typename PX>
+__device__ __forceinline__ void src_runs_tile(const PairArgs<PX>& pa, const float* __restrict__ g0_all, int ch, int pitch, size_t ps, const SrcRuns& sr, int t,
+                                              int band, int pr, int lane);
+template <typename PX>
+__global__ __launch_bounds__(64) void k_src_runs(PairArgs<PX> pa, const float* __restrict__ g0_all, int ch, int pitch, size_t ps, SrcRuns sr,
+                                                 const unsigned* __restrict__ todo) {
+    const int t = blockIdx.x, pr = blockIdx.z, lane = threadIdx.x;
+    if (!todo[pr]) return;
+    for (int band = blockIdx.y; band < sr.NR; band += gridDim.y) src_runs_tile<PX>(pa, g0_all, ch, pitch, ps, sr, t, band, pr, lane);
+}
+template <typename PX>
+__device__ __forceinline__ void src_runs_tile(const PairArgs<PX>& pa, const float* __restrict__ g0_all, int ch, int pitch, size_t ps, const SrcRuns& sr, int t,
+                                              int band, int pr, int lane) {
+    constexpr unsigned OUT = off_outside<PX>(), px = (unsigned)sizeof(PX);
+    const unsigned plane_bytes = (unsigned)pa.fw[pr] * (unsigned)pa.fh[pr] * px;
+    const int r0 = lane >> 4, c = (lane & 15) << 2;
+    const unsigned* __restrict__ idx = reinterpret_cast<const unsigned*>(g0_all + (size_t)pr * 7 * ps) + (size_t)band * TS * pitch + t * TS + c;
+    u4 o[16];
+    unsigned b[16];
+    unsigned long long pm = 0;  // bit 4i + j: sample j of group i is a patch
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int y = band * TS + r0 + 4 * i;
+        o[i] = y < ch ? *reinterpret_cast<const u4*>(idx + (size_t)(r0 + 4 * i) * pitch) : u4{OUT, OUT, OUT, OUT};
+        b[i] = src_runs::group_base(o[i][0], OUT, plane_bytes);
+        any = any || o[i][0] != OUT || o[i][1] != OUT || o[i][2] != OUT || o[i][3] != OUT;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (src_runs::is_patch(b[i], j, o[i][j], OUT, px)) pm |= 1ull << (4 * i + j);
+    }
+    unsigned incl = (unsigned)__popcll(pm);  // inclusive scan over the lanes
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const unsigned up = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += up;
+    }
+    const unsigned total = __shfl(incl, WAVE - 1, WAVE), cls = src_runs::tile_class(total, px);
+    const size_t ti = sr.tile(pr, band, t);
+    u4* bo = reinterpret_cast<u4*>(sr.bases) + ti * 4 * WAVE + lane;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bo[q * WAVE] = u4{b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]};
+    uint2* rec = sr.patches + ti * src_runs::SR_MAX_PATCHES;
+    if (cls == src_runs::SR_GENERAL || (unsigned)lane >= total) rec[lane] = uint2{0u, OUT};  // the records nobody reads: defined all the same
+    if (cls != src_runs::SR_GENERAL) {
+        unsigned k = incl - (unsigned)__popcll(pm);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((pm >> (4 * i + j)) & 1ull) {
+                    if (k < src_runs::SR_MAX_PATCHES) rec[k] = uint2{(unsigned)((r0 + 4 * i) * (TS + 4) + c + j), o[i][j]};
+                    ++k;
+                }
+    }
+    const bool live = __ballot(any) != 0;
+    if (lane == 0) sr.cls[ti] = (uint8_t)cls, sr.live[ti] = live ? 1 : 0;
+}
+
 // row0: canvas row of the planes' row 0 (0 for a whole canvas; the first row of a rank's band when one pair is split over GPUs)
 template <typename PX>
 __global__ __launch_bounds__(256) void k_compose(PairArgs<PX> pa, float* __restrict__ g0_all, int cw, int ch, int pitch,

@@ -10,6 +10,7 @@
 // current one runs its 64 recurrence steps.  The forward kernel leaves (v1,v2,v3,iplus) of every line in
 // `state`; the backward kernel starts from the Triggs boundary values computed from them.
 constexpr int TP = 68;  // padded LDS row (floats)
+static_assert(TP == TS + 4, "k_src_runs (k_compose.inc) records a patch's position in the padded tile");
 
 __device__ __forceinline__ void tile_load(const float* __restrict__ base, int pitch, int c0, int lane, f4 pre[16]) {
     // lane -> (row group, 4-column group): rows lane/16 + 4*i, columns 4*(lane%16)..+3
@@ -100,6 +101,13 @@ __device__ __forceinline__ void src_gather(__amdgpu_buffer_rsrc_t rs, const f4 n
         pre[i] = v;
     }
 }
+// The same tile through the groups' bases (SrcRuns): 16 loads of 16 bytes.  A base is the offset of a group whose 16 bytes lie inside
+// the plane, or SR_BASE_OUTSIDE, whose four words all lie beyond it and read as 0: no load straddles the plane's end.
+__device__ __forceinline__ void src_gather_runs(__amdgpu_buffer_rsrc_t rs, const f4 nbase[4], f4 pre[16]) {  // raw bits
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        pre[i] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, __float_as_uint(nbase[i >> 2][i & 3]), 0, 0));
+}
 template <typename PX>
 __device__ __forceinline__ void src_finish(bool warped, f4 pre[16]) {  // raw bits -> the value k_compose would have stored
 #pragma unroll
@@ -125,7 +133,7 @@ template <typename PX, bool SRC, bool CKPT = false>
 __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, float* __restrict__ out, int w, int pitch,
                                                   long lines, VVK k, double* __restrict__ state, MaskL0 mk,
                                                   typename CollapseSrc<PX, SRC>::type pa, ZeroTiles zt, ZeroTiles zi,
-                                                  double* __restrict__ ckpt, Bands bd, ZeroTiles mr = ZeroTiles{}) {
+                                                  double* __restrict__ ckpt, Bands bd, ZeroTiles mr = ZeroTiles{}, SrcRuns sr = SrcRuns{}) {
     __shared__ __attribute__((aligned(16))) float tile[TS * TP];
     const int lane = threadIdx.x;
     long blk = blockIdx.x;
@@ -194,9 +202,63 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
         // planes of G_1 / G_2: `zi` carries the level's G column flags (g_cols; per-plane bands) -- a flagged tile column was not stored
         return zi.flags && zi.flags[zi.index(plane, 0, t)];
     };
+    // Frame channels of float frames with the plane's runs at hand (SrcRuns): a tile of class <= 64 is gathered through its 16 bases
+    // (nidx[0..3]) and mended by at most one patch per lane (record in nidx[4]); class 255 goes through the index tile as before.
+    // The class is wave-uniform: one scalar branch per tile.
+    const bool runs_on = SRC && sizeof(PX) == 4 && gen_frame && sr.cls != nullptr;
+    const size_t sr_band = runs_on ? sr.tile(idx_pr, src_y0 >> 6, 0) : 0;
+    unsigned ncls = src_runs::SR_GENERAL;  // class of the tile whose indices `nidx` holds
+    unsigned pcls = 0, ppos = 0;           // tile in `pre`: its patches (0: none to apply), this lane's patch position and raw value
+    float pval = 0.f;
     auto index_tile = [&](int t) {
         if constexpr (SRC)
-            if (!tile_outside(t)) tile_load(idx_rows, pitch, t * TS, lane, nidx);  // an outside tile is not gathered at all
+            if (!tile_outside(t)) {  // an outside tile is not gathered at all
+                ncls = runs_on ? __builtin_amdgcn_readfirstlane((unsigned)sr.cls[sr_band + t]) : src_runs::SR_GENERAL;
+                if (ncls != src_runs::SR_GENERAL) {
+                    const f4* bp = reinterpret_cast<const f4*>(sr.bases) + (sr_band + t) * (4 * WAVE) + lane;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) nidx[q] = bp[q * WAVE];
+                    if (ncls > 0) {
+                        const uint2 r = sr.patches[(sr_band + t) * src_runs::SR_MAX_PATCHES + lane];
+                        nidx[4].x = __uint_as_float(r.x), nidx[4].y = __uint_as_float(r.y);
+                    }
+                } else
+                    tile_load(idx_rows, pitch, t * TS, lane, nidx);
+            }
+    };
+    // tile T through what index_tile(T) left in `nidx`
+    auto gather_tile = [&](f4 pre_[16]) {
+        pcls = 0;
+        if constexpr (SRC) {
+            if (gen_frame && ncls != src_runs::SR_GENERAL) {
+                src_gather_runs(rs, nidx, pre_);
+                pcls = ncls;
+                if (pcls > 0) {
+                    ppos = __float_as_uint(nidx[4].x);
+                    pval = buf_raw<PX>(rs, __float_as_uint(nidx[4].y));
+                }
+            } else
+                src_gather<PX>(rs, nidx, pre_);
+        }
+    };
+    // The mosaic planes of float frames (sr.mosaic16): a pure shift, so a tile whose 64 columns and 64 rows all lie inside the mosaic
+    // is 16 loads of 16 bytes from one computed offset per group, and a tile wholly beside the mosaic is zeros without a load; only a
+    // tile the mosaic's edge crosses (or a partial last band) needs mosaic_indices' 64 range-checked offsets.  Wave-uniform per tile.
+    const bool mos16 = SRC && sizeof(PX) == 4 && gen_mosaic && sr.mosaic16 != 0;
+    const long long my0 = (long long)src_y0 + ms.oy;  // mosaic row of the band's first row
+    const bool rows_in = nrows == TS && my0 >= 0 && my0 + TS <= ms.mh, rows_out = my0 + TS <= 0 || my0 >= ms.mh;
+    enum { MK_EDGE = 0, MK_IN = 1, MK_OUT = 2 };
+    auto mosaic_kind = [&](int t) -> int {
+        if (!mos16) return MK_EDGE;
+        const long long mx0 = (long long)t * TS + ms.ox;
+        if (rows_out || mx0 + TS <= 0 || mx0 >= ms.mw) return MK_OUT;
+        return rows_in && mx0 >= 0 && mx0 + TS <= ms.mw && (t + 1) * TS <= w ? MK_IN : MK_EDGE;
+    };
+    auto mosaic_tile_in = [&](int t, f4 pre_[16]) {  // every offset lies inside the plane: (my0 + row) * mw + mx0 + column, in bytes
+        const unsigned row_b = (unsigned)ms.mw * (unsigned)sizeof(PX);
+        const unsigned o = ((unsigned)my0 + (unsigned)(lane >> 4)) * row_b + ((unsigned)(t * TS + ms.ox) + (unsigned)((lane & 15) << 2)) * (unsigned)sizeof(PX);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pre_[i] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, o + (unsigned)(4 * i) * row_b, 0, 0));
     };
     auto gen_tile = [&](int c0, f4 pre[16]) {
         f4 v;
@@ -225,13 +287,20 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
             gen_tile((T) * TS, pre);                                           \
         else if constexpr (SRC) {                                              \
             if (tile_outside(T)) {                                             \
+                pcls = 0;                                                      \
+                _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) pre[i_] = f4{0.f, 0.f, 0.f, 0.f}; \
+            } else if (mosaic_kind(T) == MK_IN) {                              \
+                pcls = 0;                                                      \
+                mosaic_tile_in((T), pre);                                      \
+            } else if (mosaic_kind(T) == MK_OUT) {                             \
+                pcls = 0;                                                      \
                 _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) pre[i_] = f4{0.f, 0.f, 0.f, 0.f}; \
             } else                                                             \
-                src_gather<PX>(rs, nidx, pre);                                 \
+                gather_tile(pre);                                              \
             if ((T) + 1 < ntiles) {                                            \
                 if (gen_frame)                                                 \
                     index_tile((T) + 1);                                       \
-                else                                                           \
+                else if (mosaic_kind((T) + 1) == MK_EDGE)                      \
                     mosaic_indices<PX>(ms, ((T) + 1) * TS, lane, src_y0, w, nidx); \
             }                                                                  \
         } else if (tile_outside(T)) {                                          \
@@ -244,7 +313,7 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
     if constexpr (SRC) {
         if (gen_frame)
             index_tile(0);
-        else if (gen_mosaic)
+        else if (gen_mosaic && mosaic_kind(0) == MK_EDGE)
             mosaic_indices<PX>(ms, 0, lane, src_y0, w, nidx);
     }
     STITCH_X_FETCH(0);
@@ -265,6 +334,12 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
         if constexpr (SRC)
             if (!gen_mask) src_finish<PX>(gen_frame, pre);
         tile_to_lds(tile, lane, pre);
+        if constexpr (SRC) {
+            if (pcls > 0) {  // the samples the bases did not deliver: the same element through the same conversion, over what the run left there
+                __builtin_amdgcn_wave_barrier();
+                if ((unsigned)lane < pcls && ppos < (unsigned)(TS * TP)) tile[ppos] = warped_px<PX>(raw_to_px<PX>(pval));
+            }
+        }
         if (t + 1 < ntiles) STITCH_X_FETCH(t + 1);
         __syncthreads();  // one wave per workgroup: orders the tile writes before the per-lane row reads
         float* row = tile + lane * TP;

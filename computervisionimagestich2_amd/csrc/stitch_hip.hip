@@ -22,6 +22,7 @@
 #include "stitch_g_flags.h"
 #include "stitch_index_plane.h"
 #include "stitch_collapse_sides.h"
+#include "stitch_src_runs.h"
 #include "stitch_handoff.h"
 #include "stitch_mask_rows.h"
 #include "stitch_panorama.h"
@@ -207,6 +208,12 @@ struct stitch_plan : PlanShape {
     unsigned* idx_head = nullptr;    // device: IDX_HEAD_WORDS words in front of d_seam
     unsigned* h_idx_head = nullptr;  // pinned: the same words in front of h_seam (the allocation h_seam lives in)
     bool last_idx = false;           // the last call went through k_index_keys (stitch_plan_index_counts)
+    // The same planes in 16-byte runs (SrcRuns, k_compose.inc), [cap][bands][tiles] of level 0: written by k_src_runs behind k_src_index,
+    // valid exactly where the slot's IndexKey is.  last_runs: the last call's sweep was handed them; last_owner: that call's idx_pr.
+    SrcRuns runs{};
+    size_t runs_bytes = 0;  // bases, patches and classes are one region of the arena, starting at runs.bases
+    bool last_runs = false;
+    int last_owner[MAXB] = {};
     // the last call's level-0 launch of k_collapse4 (stitch_plan_collapse_sides): its column range as the caller's addresses left it,
     // and whether its workgroups chose a form by the seam's step
     int c4_l0_xa = 0, c4_l0_xb = 0;
@@ -430,7 +437,7 @@ void launch_collapse(CollapseArgs<OUT, L0>& A, const CollapseKind& kd, int cols,
 // REDUCE for every level (ImageProcess.cpp:705-715): blur(G_l) into T, decimate T into G_{l+1}.  Which kernels: the call's form
 // (stitch_call_form.h); here are their arguments.
 template <typename PX>
-int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<PX>& pa, const ZeroTiles& zi) {
+int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<PX>& pa, const ZeroTiles& zi, const SrcRuns& sr = SrcRuns{}) {
     const int n = c.n, np = 7 * n;  // planes in flight: every launch covers all pairs of the batch
     if (c.wf_ctrl) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
     for (int l = 0; l < c.l_end; ++l) {
@@ -465,7 +472,7 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
                 if (f.rcmp)
                     k_vv_x_fwd<PX, true, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, p->ckpt, bd);
                 else
-                    k_vv_x_fwd<PX, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd);
+                    k_vv_x_fwd<PX, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, pa, zt, zi, nullptr, bd, none, sr);
             } else if (f.rcmp)
                 k_vv_x_fwd<PX, false, true><<<f.nbx, 64, 0, s>>>(a.g, p->T, a.w, a.pitch, lines, p->vvk, p->state, mk, NoPairArgs{}, zt, none, p->ckpt, bd);
             else
@@ -673,6 +680,12 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
         zi.NR = (a.h + TS - 1) / TS;
         zi.NC = (a.w + TS - 1) / TS;
     }
+    // the index planes in 16-byte runs for k_vv_x_fwd<PX, true>; the forms that gather elsewhere (k_vv_x_m, the CKPT sweep) do without
+    SrcRuns runs{}, sr{};  // what k_src_runs writes; what this call's sweep is handed
+#ifndef STITCH_NO_SRC_RUNS  // (the A/B library: every frame tile through the full index plane)
+    runs = p->runs;
+    if (src && !pa.a_dense && c.lv[0].src0 && c.lv[0].x_fwd == XF_FWD && !c.lv[0].rcmp) sr = runs;
+#endif
     {
         StageTimer t(p, s, STITCH_K_COMPOSE, 0);
         if (src) {
@@ -683,6 +696,9 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
                 k_index_keys<PX><<<1, 64, 0, s>>>(pa, n, p->idx_keys, todo, p->idx_head);
                 if (zi.flags) k_zi_preset<<<dim3(4, n), 256, 0, s>>>(zi.flags, zi.NR * zi.NC, todo);
                 k_src_index<PX><<<grid_xy(a.pitch, std::min((a.h + SI_ROWS - 1) / SI_ROWS, SI_WGY), n), 256, 0, s>>>(pa, a.g, a.w, a.h, a.pitch, a.ps, zi, 0, todo);
+                // and the same plane in 16-byte runs, every tile of a computed slot -- whichever form this call's sweep takes: a later call
+                // that finds the slot's record unchanged may take the other
+                if (runs.cls) k_src_runs<PX><<<dim3(runs.NC, std::min(runs.NR, SR_WGY), n), 64, 0, s>>>(pa, a.g, a.h, a.pitch, a.ps, runs, todo);
             }  // (a dense pair has no index plane and writes nothing into the slot: the record stands)
         } else {
             if (pa.a_dense)
@@ -693,9 +709,11 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
         }
     }
     p->last_idx = src && !pa.a_dense;
+    p->last_runs = sr.cls != nullptr;
+    for (int i = 0; i < MAXB; ++i) p->last_owner[i] = pa.idx_pr[i];
     if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given))) return rc;
     p->last_form = c;
-    if ((rc = run_reduce<PX>(p, c, s, pa, zi))) return rc;
+    if ((rc = run_reduce<PX>(p, c, s, pa, zi, sr))) return rc;
     if ((rc = run_collapse<PX>(p, c, outs, s, pa))) return rc;
     p->last_stream = s;
     p->pending = true;
@@ -1609,6 +1627,10 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     const size_t ik_off = take(sizeof(IndexKey) * B);  // zero at creation: no slot holds a plane
     const size_t side_off = take(sizeof(float) * B * v0.pitch);
     const size_t zp_off = take(4096);  // zeros for good (k_vv_xby_m's loader reads a flagged tile from here)
+    // the index planes in 16-byte runs: per tile 4 KB of bases, 512 B of patch records, one class byte (a plan that can be source-fused)
+    const size_t sr_tiles = !planes_in && p->src_fuse ? (size_t)B * NR0 * NC0 : 0;
+    const size_t sr_base_off = take(sr_tiles * 4 * WAVE * sizeof(u4)), sr_patch_off = take(sr_tiles * src_runs::SR_MAX_PATCHES * sizeof(uint2)), sr_cls_off = take(sr_tiles), sr_live_off = take(sr_tiles);
+    p->runs_bytes = off - sr_base_off;
     p->arena_bytes = off;
     if (hipMalloc(&p->arena, off) != hipSuccess) {
         (void)hipGetLastError();
@@ -1635,6 +1657,7 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     p->idx_keys = reinterpret_cast<IndexKey*>(base + ik_off);
     p->side = reinterpret_cast<float*>(base + side_off);
     p->zero_page = reinterpret_cast<const float*>(base + zp_off);
+    if (sr_tiles) p->runs = SrcRuns{reinterpret_cast<unsigned*>(base + sr_base_off), reinterpret_cast<uint2*>(base + sr_patch_off), reinterpret_cast<uint8_t*>(base + sr_cls_off), reinterpret_cast<uint8_t*>(base + sr_live_off), NR0, NC0, 1};
     if (p->has_wf) {
         p->wf_yg = reinterpret_cast<u64*>(base + yg_off);
         p->wf_yg_bytes = sizeof(u64) * B * 7 * NC0 * WF_GRAN * WAVE;
@@ -1880,6 +1903,43 @@ int stitch_plan_index_counts(stitch_plan* p, uint32_t out[3]) {
         p->pending = false;
     }
     for (int i = 0; i < 3; ++i) out[i] = p->last_idx ? p->h_idx_head[i] : 0u;  // (the words of a call without an index plane are an earlier call's)
+    return STITCH_OK;
+}
+
+int stitch_plan_src_run_counts(stitch_plan* p, uint32_t out[4]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (!p->last_runs) return STITCH_OK;  // (the arrays of a call that was not handed them are an earlier call's)
+    const size_t nt = (size_t)p->runs.NR * p->runs.NC;
+    std::vector<uint8_t> cls(nt), live(nt);
+    for (int i = 0; i < p->last_n; ++i) {
+        if (p->last_owner[i] != i) continue;  // a pair that reads an earlier pair's plane
+        HIPCHK(hipMemcpy(cls.data(), p->runs.cls + i * nt, nt, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(live.data(), p->runs.live + i * nt, nt, hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < nt; ++t) ++out[!live[t] ? 0 : cls[t] == 0 ? 1 : cls[t] == src_runs::SR_GENERAL ? 3 : 2];
+    }
+    return STITCH_OK;
+}
+
+int stitch_src_run_classes(const double p[8], float offx, float offy, int fw, int fh, int cw, int ch, int px_bytes, uint32_t counts[4], uint8_t* cls) {
+    if (!p || !counts || fw <= 0 || fh <= 0 || cw <= 0 || ch <= 0 || (px_bytes != 4 && px_bytes != 1) || (unsigned long long)fw * fh * px_bytes >= 0xfffffff0ULL)
+        return fail(STITCH_ERR_ARG, "src_run_classes: null map or counts, a non-positive size, a sample size other than 4 or 1, or a plane of 4 GB");
+    src_runs::host_classes(p, offx, offy, fw, fh, cw, ch, (unsigned)px_bytes, counts, cls);
+    return STITCH_OK;
+}
+
+int stitch_plan_src_runs_fill(stitch_plan* p, int byte) {
+    if (!p) return fail(STITCH_ERR_ARG, "null plan");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    if (p->runs.cls) HIPCHK(hipMemset(p->runs.bases, byte, p->runs_bytes));
+    HIPCHK(hipDeviceSynchronize());
     return STITCH_OK;
 }
 

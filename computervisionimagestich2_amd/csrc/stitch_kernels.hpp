@@ -16,6 +16,7 @@
 
 #include "stitch_elem.h"
 #include "stitch_call_form.h"  // the constants kernels and host decisions share (TS, YCH, YCOLS, XY_MAXNC, CROWS, CO_*, MAXB)
+#include "src_runs_rule.h"     // level-0 index plane -> 16-byte runs and patches: the rule k_src_runs applies and the host restates
 
 #pragma clang fp contract(off)
 
