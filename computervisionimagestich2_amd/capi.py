@@ -174,6 +174,12 @@ RIG_SEAMS_SIGNATURES = _signatures(
     ("stitch_rig_step_canvas", i32, vp, i32, vp, vp),
 )
 
+# The same for include/stitch_rig_crop.h, the crop of a rig's output; tests/test_rig_crop_host.py holds it to that header.
+RIG_CROP_SIGNATURES = _signatures(
+    ("stitch_dev_largest_rect_u8", i32, vp, i32, i32, vp, vp), ("stitch_dev_rig_inscribed_rect", i32, vp, i32, vp, vp),
+    ("stitch_rig_set_crop", i32, vp, vp, i32), ("stitch_rig_clear_crop", i32, vp), ("stitch_rig_crop stitch_rig_output_size", i32, vp, vp, vp),
+)
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -219,7 +225,8 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()):  # include/stitch_collapse_sides.h, stitch_src_runs.h (likewise)
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h (likewise)
+        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1452,6 +1459,33 @@ def rig_steps(steps, start=None):
     return int(start), arr
 
 
+class Rect(C.Structure):
+    """stitch_rect (include/stitch_rig_crop.h): x0, y0, w, h."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.x0, self.y0, self.w, self.h)
+
+
+CROP_AFTER_FINISH, CROP_BEFORE_FINISH = 1, 2
+
+
+def _rect(rect):
+    return rect if isinstance(rect, Rect) else Rect(*[int(v) for v in rect])
+
+
+def dev_largest_rect(mask):
+    """stitch_dev_largest_rect_u8 on torch's current stream, which it waits for: the largest axis-aligned rectangle of non-zero
+    bytes inside a contiguous (h, w) uint8 device tensor, as (x0, y0, w, h) -- the largest area, then the smallest y0, the smallest
+    x0, the widest; (0, 0, 0, 0) where nothing is covered."""
+    import torch
+    if not mask.is_cuda or not mask.is_contiguous() or mask.dim() != 2 or mask.dtype != torch.uint8:
+        raise ValueError("expected a contiguous (H, W) uint8 tensor on the HIP device")
+    r = Rect()
+    _chk(lib().stitch_dev_largest_rect_u8(_dp(mask), mask.shape[1], mask.shape[0], C.byref(r), _stream()))
+    return r.as_tuple()
+
+
 class Rig(_Handle):
     """stitch_rig: the recorded stitch order, maps and canvases of a panorama, replayed on many frame sets -- step k of all the
     sets of a call is one batched launch sequence."""
@@ -1565,11 +1599,56 @@ class Rig(_Handle):
         _chk(lib().stitch_dev_rig_coverage_u8(self._h, int(step), int(which), _dp(out), _stream()))
         return out
 
+    def inscribed_rect(self, step=-1):
+        """stitch_dev_rig_inscribed_rect on torch's current stream, which it waits for: the largest rectangle (x0, y0, w, h) inside
+        step's A | B coverage, read from the rig's bit planes (dev_largest_rect's rule); step -1: inside the output's validity mask."""
+        r = Rect()
+        _chk(lib().stitch_dev_rig_inscribed_rect(self._h, int(step), C.byref(r), _stream()))
+        return r.as_tuple()
+
+    def set_crop(self, rect=None, mode=CROP_AFTER_FINISH):
+        """stitch_rig_set_crop (host only): every later stitch() writes the rectangle (x0, y0, w, h) of the output canvas alone --
+        mode 1 (CROP_AFTER_FINISH) the slice of the finished canvas, mode 2 (CROP_BEFORE_FINISH) the finish pass on the slice of the
+        unfinished one.  rect=None takes inscribed_rect() (on the device) and raises ValueError if it is empty.  Returns self."""
+        if rect is None:
+            rect = self.inscribed_rect()
+            if rect[2] < 1 or rect[3] < 1:
+                raise ValueError("the output's coverage holds no rectangle")
+        _chk(lib().stitch_rig_set_crop(self._h, C.byref(_rect(rect)), int(mode)))
+        return self
+
+    def clear_crop(self):
+        """stitch_rig_clear_crop: back to the whole canvas.  Returns self."""
+        _chk(lib().stitch_rig_clear_crop(self._h))
+        return self
+
+    @property
+    def crop(self):
+        """stitch_rig_crop: ((x0, y0, w, h), mode); mode 0 is no crop, with the whole canvas as the rectangle."""
+        r, mode = Rect(), C.c_int()
+        _chk(lib().stitch_rig_crop(self._h, C.byref(r), C.byref(mode)))
+        return r.as_tuple(), mode.value
+
+    def _out_size(self):
+        w, h = C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_output_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    @property
+    def out_width(self):
+        """stitch_rig_output_size: the width of what stitch() writes per set (the crop's, or the canvas's)."""
+        return self._out_size()[0]
+
+    @property
+    def out_height(self):
+        return self._out_size()[1]
+
     def stitch(self, sets, out=None, return_stats=False):
         """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for (with return_stats
         stitch_dev_rig_stitch_exposure_u8, and a fourth result: an (n_sets, n_steps, 12) float32 array of every transfer's
         statistics; the rig must have been made with an exposure mode).  sets: a list of frame sets, each a list of
-        n_frames (3, H, W) uint8 device tensors.  Returns (outputs, statuses, seams): one (3, height, width) tensor per set, each
+        n_frames (3, H, W) uint8 device tensors.  Returns (outputs, statuses, seams): one (3, height, width) tensor per set -- with a
+        crop set (set_crop) one (3, out_height, out_width) tensor, and `out` is checked against that shape --, each
         set's status (OK, ERR_EMPTY_MIDROW or ERR_ZERO_OVERLAP: a failed set does not raise, the others are valid), and per set the
         Seam tuples of its steps.  self.last_rc keeps the call's return value (the status of the first set that is not OK).
         Anything else -- a bad argument, a failed HIP call, a hand-off time-out -- raises StitchError."""
@@ -1580,11 +1659,13 @@ class Rig(_Handle):
             raise ValueError(f"every set has {self.n_frames} frames")
         flat, arr = _frames_u8(flat)
         n_sets = len(sets)
+        # the crop's size while one is set (an A/B build of an earlier tree, STITCH_LIB, has no crop: the canvas)
+        ow, oh = self._out_size() if hasattr(lib(), "stitch_rig_output_size") else (self.width, self.height)
         if out is None:
-            out = [torch.empty((3, self.height, self.width), dtype=torch.uint8, device=flat[0].device) for _ in range(n_sets)]
+            out = [torch.empty((3, oh, ow), dtype=torch.uint8, device=flat[0].device) for _ in range(n_sets)]
         out = [_timg(o) for o in out]
-        if len(out) != n_sets or any(tuple(o.shape) != (3, self.height, self.width) or o.dtype != torch.uint8 for o in out):
-            raise ValueError(f"one (3, {self.height}, {self.width}) uint8 output per set")
+        if len(out) != n_sets or any(tuple(o.shape) != (3, oh, ow) or o.dtype != torch.uint8 for o in out):
+            raise ValueError(f"one (3, {oh}, {ow}) uint8 output per set")
         ptrs = (C.c_void_p * max(n_sets, 1))(*[o.data_ptr() for o in out])
         status = (C.c_int32 * max(n_sets, 1))()
         seams = (Seam * max(n_sets * self.n_steps, 1))()

@@ -31,6 +31,7 @@
 #include "stitch_rig_exposure.h"
 #include "stitch_calibrate.h"
 #include "stitch_rig_seams.h"
+#include "stitch_rig_crop.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2569,3 +2570,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_rig_exposure.inc"
 #include "stitch_calibrate.inc"
 #include "stitch_rig_seams.inc"
+#include "stitch_rig_crop.inc"

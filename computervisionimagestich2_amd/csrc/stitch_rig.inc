@@ -36,8 +36,14 @@ struct stitch_rig {
     unsigned long long* cover = nullptr;         // every plane, one block: C_proj per distinct frame size, then A, B, A | B per step
     std::vector<size_t> cover_proj, cover_step;  // word offsets: per frame (its size's plane), per step (A; B and A | B follow)
     std::vector<SeamDev> cover_seams;            // the scan of every step over coverage
+    // ---- the crop of the output (include/stitch_rig_crop.h; stitch_rig_crop.inc) ----
+    int crop_mode = 0;  // 0: the whole canvas, 1: the rectangle of the finished canvas, 2: the finish pass on the rectangle
+    stitch_rect crop{0, 0, 0, 0};
+    uint8_t* crop_full = nullptr;  // max_sets full canvases the last step writes, `crop_full_bytes` apart; from the first cropped call on
+    size_t crop_full_bytes = 0;
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
+        if (crop_full) (void)hipFree(crop_full);
         if (cover) (void)hipFree(cover);
         for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
             if (p) (void)hipFree(p);
@@ -59,6 +65,11 @@ int rig_ex_workspaces(stitch_rig* R);
 size_t rig_ex_table_bytes(const stitch_rig* R);
 void rig_ex_fill_tables(const stitch_rig* R, unsigned char* host);
 int rig_ex_transfer(stitch_rig* R, const unsigned char* d_tables, int k, int m, hipStream_t s);
+
+// The crop of a rig that has one (stitch_rig_crop.inc): the full-canvas buffers its last step writes, and the copy of the rectangle
+// out of the m buffers of a sequence (the src entries of the table) to the caller's (the dst entries), one launch.
+int rig_crop_workspace(stitch_rig* R);
+int rig_crop_copy(const stitch_rig* R, const RigImage* d_tab, int m, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -347,7 +358,9 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     stitch_rig* R = rig;
     if (stats && !R->ex.mode) return fail(STITCH_ERR_ARG, "rig_stitch: statistics asked of a rig made without a transfer (mode 0)");
     const int n = R->n, ns = (int)R->steps.size();
-    const size_t out_bytes = (size_t)3 * R->out_w * R->out_h;
+    // include/stitch_rig_crop.h: a cropped rig writes the rectangle to d_out, and its last step a full canvas of the rig's own
+    const bool cropped = R->crop_mode != 0;
+    const size_t out_bytes = cropped ? (size_t)3 * R->crop.w * R->crop.h : (size_t)3 * R->out_w * R->out_h;
     for (int i = 0; i < n_sets; ++i) {
         if (!d_out[i]) return fail(STITCH_ERR_ARG, "rig_stitch: set %d has no output buffer", i);
         for (int f = 0; f < n; ++f) {
@@ -366,13 +379,16 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             if (ranges_overlap(d_out[j], out_bytes, d_out[i], out_bytes)) return fail(STITCH_ERR_ARG, "rig_stitch: the outputs of sets %d and %d overlap", j, i);
     }
     if ((rc = rig_workspaces(R))) return rc;
+    if (cropped && (rc = rig_crop_workspace(R))) return rc;
     hipStream_t s = as_stream(stream);
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
 
     // ---- the pointer tables of the whole call, uploaded once: per sequence one slice per projected frame, then the outputs ----
     const int n_need = (int)R->needed.size();
     const std::vector<int> seqs = rig_sequences(n_sets, R->max_sets);
-    std::vector<RigImage> tab((size_t)(n_need + 1) * n_sets);
+    // (a cropped rig: the outputs' entries name the full canvas as their source, and one more slice names it as a destination)
+    std::vector<RigImage> tab((size_t)(n_need + (cropped ? 2 : 1)) * n_sets);
+    auto full_of = [&](int i) { return R->crop_full + (size_t)i * R->crop_full_bytes; };  // set i of a sequence
     {
         size_t at = 0;
         int set0 = 0;
@@ -380,10 +396,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             for (int f : R->needed)
                 for (int i = 0; i < m; ++i) {
                     // zero steps: the start frame is projected straight into the caller's buffer
-                    uint8_t* dst = ns == 0 ? d_out[set0 + i] : R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
+                    uint8_t* dst = ns == 0 ? (cropped ? full_of(i) : d_out[set0 + i]) : R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
                     tab[at++] = RigImage{frames[(size_t)(set0 + i) * n + f].data, dst};
                 }
-            for (int i = 0; i < m; ++i) tab[at++] = RigImage{nullptr, d_out[set0 + i]};
+            for (int i = 0; i < m; ++i) tab[at++] = RigImage{cropped ? full_of(i) : nullptr, d_out[set0 + i]};
+            for (int i = 0; cropped && i < m; ++i) tab[at++] = RigImage{nullptr, full_of(i)};
             set0 += m;
         }
     }
@@ -443,7 +460,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
                 d.mh = mh;
                 d.ox = st.geom.ox;
                 d.oy = st.geom.oy;
-                d.out = last ? d_out[set0 + i] : R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes;
+                d.out = !last ? R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes : cropped ? full_of(i) : d_out[set0 + i];
             }
             // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
             if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
@@ -458,7 +475,16 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             mw = st.geom.cw;
             mh = st.geom.ch;
         }
-        if (R->finish && (rc = rig_finish_many(tab.data() + at, d_tab + at, d_eq + (size_t)RIG_EQ_WORDS * set0, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
+        if (!cropped) {
+            if (R->finish && (rc = rig_finish_many(tab.data() + at, d_tab + at, d_eq + (size_t)RIG_EQ_WORDS * set0, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
+        } else {
+            // mode 1 finishes the full canvases and copies; mode 2 copies and finishes the rectangles as images of their own
+            int32_t* eq = R->finish ? d_eq + (size_t)RIG_EQ_WORDS * set0 : nullptr;
+            if (R->finish && R->crop_mode == 1 && (rc = rig_finish_many(tab.data() + at + m, d_tab + at + m, eq, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
+            if ((rc = rig_crop_copy(R, d_tab + at, m, s))) return rc;
+            if (R->finish && R->crop_mode == 2 && (rc = rig_finish_many(tab.data() + at, d_tab + at, eq, m, R->crop.w, R->crop.h, R->num, R->den, s))) return rc;
+            at += m;
+        }
         at += m;
         // the sequence's statistics leave the device in one copy, behind its last transfer; the next sequence overwrites them
         if (!h_stats.empty())

@@ -126,7 +126,7 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
     return proj_dst
 
 
-def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None):
+def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -139,6 +139,8 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     running mosaic (exposure_match; include/stitch_exposure.h), keep_black leaving the projection's black corners black.
     seams: per step a capi.Seam or a tuple (sum_a_x, n_a, sum_ov_x, n_ov, ...) that replaces the step's seam scan
     (include/stitch_rig_seams.h): the single-set chain with given seams, the yardstick of a rig with fixed seams.
+    crop: a pair ((x0, y0, w, h), mode) (include/stitch_rig_crop.h), applied with plain slicing: mode 1 the slice of the finished
+    mosaic, mode 2 the finish pass on the slice of the unfinished one -- the single-set statement of a cropped rig.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     proj = {}
 
@@ -166,7 +168,18 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             exposure_match(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black)
         result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"], seam=None if seams is None else seams[k])
         used.append(plan)
-    if finish:
+    if crop is not None:
+        (x0, y0, w, h), mode = crop
+        if mode not in (1, 2):
+            raise ValueError("crop mode 1 (after the finish pass) or 2 (before it)")
+        if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > result.shape[2] or y0 + h > result.shape[1]:
+            raise ValueError("the crop is empty or not inside the mosaic")
+        if finish and mode == 1:
+            capi.dev_finish(result, num, den)
+        result = result[:, y0:y0 + h, x0:x0 + w].contiguous()
+        if finish and mode == 2:
+            capi.dev_finish(result, num, den)
+    elif finish:
         capi.dev_finish(result, num, den)
     # the steps only depend on each other on the device; their seam scans are checked once, at the end (raises StitchError)
     try:
