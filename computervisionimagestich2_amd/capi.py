@@ -180,6 +180,15 @@ RIG_CROP_SIGNATURES = _signatures(
     ("stitch_rig_set_crop", i32, vp, vp, i32), ("stitch_rig_clear_crop", i32, vp), ("stitch_rig_crop stitch_rig_output_size", i32, vp, vp, vp),
 )
 
+# The same for include/stitch_rig_formats.h, a rig's frames and mosaics in camera layouts; tests/test_pixfmt_host.py holds it to that
+# header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the eight.)
+RIG_FORMAT_SIGNATURES = _signatures(
+    ("stitch_image_bytes", i32, i32, i32, i32, i32, i32, vp, vp),
+    ("stitch_dev_unpack_many_u8 stitch_dev_pack_many_u8", i32, i32, i32, vp, vp, i32, vp),
+    ("stitch_rig_set_formats", i32, vp, i32, i32, i32), ("stitch_rig_formats", i32, vp, vp, vp, vp), ("stitch_rig_clear_formats", i32, vp),
+    ("stitch_dev_rig_stitch_fmt_u8", i32, vp, vp, i32, vp, vp, vp, vp, vp),
+)
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -225,8 +234,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h (likewise)
-        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()):
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h (likewise)
+        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
+                + list(RIG_FORMAT_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1486,6 +1496,109 @@ def dev_largest_rect(mask):
     return r.as_tuple()
 
 
+# ---- camera layouts: include/stitch_rig_formats.h ---------------------------------------------------------------------------
+PIX_PLANAR, PIX_RGB24, PIX_BGR24, PIX_RGBX32, PIX_BGRX32, PIX_NV12 = range(6)
+_PIX_BPP = {PIX_RGB24: 3, PIX_BGR24: 3, PIX_RGBX32: 4, PIX_BGRX32: 4, PIX_NV12: 1}
+
+
+class ImageDesc(C.Structure):
+    """stitch_image."""
+    _fields_ = [("data", C.c_void_p), ("data2", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("pitch2", C.c_int32)]
+
+
+def tight_pitches(fmt, w):
+    """(pitch, pitch2) of rows without padding; (0, 0) for PIX_PLANAR, which has none."""
+    if fmt == PIX_PLANAR:
+        return 0, 0
+    return _PIX_BPP[fmt] * w, (2 * ((w + 1) // 2) if fmt == PIX_NV12 else 0)
+
+
+def image_bytes(fmt, w, h, pitch=None, pitch2=None):
+    """stitch_image_bytes (host only): the extent of each plane in bytes, (bytes, bytes2); a pitch of None is the tight one.  Raises
+    StitchError(ERR_ARG) for a bad format, size or pitch."""
+    tight = tight_pitches(fmt, w) if 0 <= fmt <= PIX_NV12 else (0, 0)
+    b1, b2 = C.c_size_t(), C.c_size_t()
+    _chk(lib().stitch_image_bytes(int(fmt), int(w), int(h), int(tight[0] if pitch is None else pitch), int(tight[1] if pitch2 is None else pitch2),
+                                  C.byref(b1), C.byref(b2)))
+    return b1.value, b2.value
+
+
+class Image:
+    """One image in a layout of include/stitch_rig_formats.h: uint8 device tensors plus pitches.  `data` (and for PIX_NV12 `data2`, the
+    CbCr plane) are contiguous uint8 tensors that start at the plane's first byte and hold at least image_bytes(...) bytes -- any shape,
+    so a view into a larger buffer gives an odd base; for PIX_PLANAR `data` is the dense (3, h, w) tensor of every other call."""
+
+    def __init__(self, fmt, width, height, data, data2=None, pitch=None, pitch2=None):
+        tight = tight_pitches(fmt, width)
+        self.fmt, self.width, self.height, self.data, self.data2 = int(fmt), int(width), int(height), data, data2
+        self.pitch, self.pitch2 = int(tight[0] if pitch is None else pitch), int(tight[1] if pitch2 is None else pitch2)
+        need = image_bytes(self.fmt, self.width, self.height, self.pitch, self.pitch2)
+        for t, n in ((data, need[0]), (data2, need[1])):
+            if n and (t is None or not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.uint8" or t.numel() < n):
+                raise ValueError(f"every plane is a contiguous uint8 device tensor of at least {n} bytes")
+
+    @classmethod
+    def empty(cls, fmt, width, height, device="cuda", pitch=None, pitch2=None, fill=None):
+        """A fresh image of exactly image_bytes(...) bytes per plane (fill: a byte value to set every byte to)."""
+        import torch
+        tight = tight_pitches(fmt, width)
+        pitch, pitch2 = tight[0] if pitch is None else pitch, tight[1] if pitch2 is None else pitch2
+        b1, b2 = image_bytes(fmt, width, height, pitch, pitch2)
+        make = (lambda n: torch.empty(n, dtype=torch.uint8, device=device)) if fill is None else (lambda n: torch.full((n,), fill, dtype=torch.uint8, device=device))
+        data = make(b1).view(3, height, width) if fmt == PIX_PLANAR else make(b1)
+        return cls(fmt, width, height, data, make(b2) if b2 else None, pitch, pitch2)
+
+    def desc(self):
+        return ImageDesc(self.data.data_ptr(), self.data2.data_ptr() if self.data2 is not None else None, self.width, self.height, self.pitch, self.pitch2)
+
+
+def _image_array(images):
+    return (ImageDesc * max(len(images), 1))(*[im.desc() for im in images])
+
+
+def _planar_list(planar, w, h):
+    import torch
+    planar = [_timg(t) for t in planar]
+    if any(tuple(t.shape) != (3, h, w) or t.dtype != torch.uint8 for t in planar):
+        raise ValueError(f"every planar image is a (3, {h}, {w}) uint8 tensor")
+    return planar
+
+
+def dev_unpack_many(images, matrix=0, out=None):
+    """stitch_dev_unpack_many_u8 on torch's current stream, which it waits for: same-size, same-format Images -> dense planar
+    (3, h, w) tensors, one launch."""
+    import torch
+    images = list(images)
+    fmt, w, h = images[0].fmt, images[0].width, images[0].height
+    if any(im.fmt != fmt for im in images):
+        raise ValueError("one format per call")
+    if out is None:
+        out = [torch.empty((3, h, w), dtype=torch.uint8, device=images[0].data.device) for _ in images]
+    out = _planar_list(out, w, h)
+    if len(out) != len(images):
+        raise ValueError("one planar output per image")
+    ptrs = (C.c_void_p * max(len(out), 1))(*[t.data_ptr() for t in out])
+    _chk(lib().stitch_dev_unpack_many_u8(fmt, int(matrix), _image_array(images), ptrs, len(images), _stream()))
+    return out
+
+
+def dev_pack_many(planar, fmt=None, matrix=0, out=None, pitch=None, pitch2=None):
+    """stitch_dev_pack_many_u8 on torch's current stream, which it waits for: dense planar (3, h, w) tensors -> Images of `fmt`, one
+    launch; into `out` (Images; their format is the call's) or fresh images of the given pitches (None: tight)."""
+    planar = list(planar)
+    _, h, w = planar[0].shape
+    planar = _planar_list(planar, w, h)
+    if out is None:
+        out = [Image.empty(fmt, w, h, planar[0].device, pitch, pitch2) for _ in planar]
+    out = list(out)
+    fmt = out[0].fmt if fmt is None else fmt
+    if len(out) != len(planar) or any(im.fmt != fmt for im in out):
+        raise ValueError("one image of the call's format per planar input")
+    ptrs = (C.c_void_p * max(len(planar), 1))(*[t.data_ptr() for t in planar])
+    _chk(lib().stitch_dev_pack_many_u8(int(fmt), int(matrix), ptrs, _image_array(out), len(planar), _stream()))
+    return out
+
+
 class Rig(_Handle):
     """stitch_rig: the recorded stitch order, maps and canvases of a panorama, replayed on many frame sets -- step k of all the
     sets of a call is one batched launch sequence."""
@@ -1643,8 +1756,59 @@ class Rig(_Handle):
     def out_height(self):
         return self._out_size()[1]
 
+    def set_formats(self, in_fmt, out_fmt, matrix=0):
+        """stitch_rig_set_formats (host only): every later stitch() takes its frames as Images of in_fmt and returns Images of
+        out_fmt (include/stitch_rig_formats.h); matrix: the NV12 matrix of both sides.  Returns self."""
+        _chk(lib().stitch_rig_set_formats(self._h, int(in_fmt), int(out_fmt), int(matrix)))
+        return self
+
+    def clear_formats(self):
+        """stitch_rig_clear_formats: planar both ways again.  Returns self."""
+        _chk(lib().stitch_rig_clear_formats(self._h))
+        return self
+
+    @property
+    def formats(self):
+        """stitch_rig_formats: (in_fmt, out_fmt, matrix); (0, 0, 0) is every rig that never set one."""
+        if not hasattr(lib(), "stitch_rig_formats"):  # an A/B build of an earlier tree, STITCH_LIB
+            return 0, 0, 0
+        v = [C.c_int() for _ in range(3)]
+        _chk(lib().stitch_rig_formats(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _stitch_fmt(self, sets, out, return_stats):
+        """stitch() of a rig with a format set: stitch_dev_rig_stitch_fmt_u8."""
+        in_fmt, out_fmt, _ = self.formats
+        sets = [[f if isinstance(f, Image) else Image(PIX_PLANAR, f.shape[2], f.shape[1], _timg(f)) for f in fs] for fs in sets]
+        if any(len(fs) != self.n_frames for fs in sets):
+            raise ValueError(f"every set has {self.n_frames} frames")
+        flat = [f for fs in sets for f in fs]
+        if any(f.fmt != in_fmt for f in flat):
+            raise ValueError(f"every frame is an Image of format {in_fmt}")
+        n_sets = len(sets)
+        ow, oh = self._out_size()
+        if out is None:
+            out = [Image.empty(out_fmt, ow, oh, flat[0].data.device) for _ in range(n_sets)]
+        out = [o if isinstance(o, Image) else Image(PIX_PLANAR, o.shape[2], o.shape[1], _timg(o)) for o in out]
+        if len(out) != n_sets or any((o.fmt, o.width, o.height) != (out_fmt, ow, oh) for o in out):
+            raise ValueError(f"one {ow} x {oh} output Image of format {out_fmt} per set")
+        status = (C.c_int32 * max(n_sets, 1))()
+        seams = (Seam * max(n_sets * self.n_steps, 1))()
+        stats = np.zeros((n_sets, self.n_steps, 12), np.float32) if return_stats else None
+        rc = lib().stitch_dev_rig_stitch_fmt_u8(self._h, _image_array(flat), n_sets, _image_array(out), status, seams, _p(stats) if return_stats else None, _stream())
+        statuses = list(status[:n_sets])
+        seam_rows = [[seams[i * self.n_steps + k].as_tuple() for k in range(self.n_steps)] for i in range(n_sets)]
+        self.last_rc = rc
+        if rc < 0 and rc not in (ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP):
+            raise StitchError(rc, lib().stitch_last_error().decode())
+        return (out, statuses, seam_rows, stats) if return_stats else (out, statuses, seam_rows)
+
     def stitch(self, sets, out=None, return_stats=False):
-        """stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for (with return_stats
+        """With a format set (set_formats): stitch_dev_rig_stitch_fmt_u8 -- the frames are Images of in_fmt (a planar side also takes
+        plain (3, H, W) tensors), the outputs come back as Images of out_fmt, allocated by image_bytes at tight pitch unless given as
+        `out`; everything else as below.
+
+        stitch_dev_rig_stitch_u8 on torch's current stream, which it waits for (with return_stats
         stitch_dev_rig_stitch_exposure_u8, and a fourth result: an (n_sets, n_steps, 12) float32 array of every transfer's
         statistics; the rig must have been made with an exposure mode).  sets: a list of frame sets, each a list of
         n_frames (3, H, W) uint8 device tensors.  Returns (outputs, statuses, seams): one (3, height, width) tensor per set -- with a
@@ -1654,6 +1818,8 @@ class Rig(_Handle):
         Anything else -- a bad argument, a failed HIP call, a hand-off time-out -- raises StitchError."""
         import torch
         sets = [list(fs) for fs in sets]
+        if self.formats[:2] != (0, 0):
+            return self._stitch_fmt(sets, out, return_stats)
         flat = [f for fs in sets for f in fs]
         if any(len(fs) != self.n_frames for fs in sets):
             raise ValueError(f"every set has {self.n_frames} frames")

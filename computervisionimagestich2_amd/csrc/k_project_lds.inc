@@ -214,6 +214,19 @@ __device__ __forceinline__ void pj_stage_box(const PX* __restrict__ src, size_t 
     else
         pj_stage<PX, ((TH + TH / 8 + 11) / 8 > 4 ? (TH + TH / 8 + 11) / 8 : 4)>(src, pl, w, r0, nrow, c0a, ncol, smem);
 }
+// The staging policy of project_lds_tile / project_lds_tile_t: how a tile's source box gets into LDS.  This one is pj_stage_box on the
+// planar source; k_rig_formats.inc has one that stages the same dwords straight from a packed or NV12 frame.  That one has no planar
+// source (kPlanarSource = false), so a tile without a staged box cannot take the per-pixel form.  Such a tile is one of two kinds.
+// A box over the LDS budget: the host's sizing rules it out for every tile.  An EMPTY box, c1 < c0: every source column of the tile
+// lies outside the frame (edge tiles of wide frames at larger angles), so every pixel of it is 0, which is what the per-pixel form
+// writes too -- pj_zero_px writes it without a source.
+template <typename PX, int TH>
+struct PjStagePlanar {
+    static constexpr bool kPlanarSource = true;
+    __device__ __forceinline__ void operator()(const PX* __restrict__ src, size_t pl, int w, int r0, int nrow, int c0a, int ncol, uint8_t* smem) const {
+        pj_stage_box<PX, TH>(src, pl, w, r0, nrow, c0a, ncol, smem);
+    }
+};
 // a finished sample into plane c: the row's offset is wave-uniform (one output row per wavefront and step), the lane adds its column
 template <typename PX>
 __device__ __forceinline__ void pj_store(__amdgpu_buffer_rsrc_t rd, unsigned x, unsigned row_c_elems, PX v);
@@ -281,11 +294,16 @@ __device__ __noinline__ void project_px_global(const PX* __restrict__ src, PX* _
         }
     }
 }
+// One pixel of a tile whose source columns all lie outside the frame: 0 in the three planes (what project_px_global stores there).
+template <typename PX>
+__device__ __forceinline__ void pj_zero_px(PX* __restrict__ dst, size_t pl, size_t off) {
+    dst[off] = PX(0), dst[off + pl] = PX(0), dst[off + 2 * pl] = PX(0);
+}
 // (The tile's work is a device function so that k_project_lds_many, k_rig.inc, runs it per image of a batch: blockIdx.x / .y
 // address the tile.)
-template <typename PX, int TW, int TH>
+template <typename PX, int TW, int TH, typename STAGE = PjStagePlanar<PX, TH>>
 __device__ __forceinline__ void project_lds_tile(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
-                                                 uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+                                                 uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes, STAGE stage = STAGE()) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pj_smem[];
     __shared__ ProjCol corner[4];
     constexpr int CPX = PJ_CHUNK / (int)sizeof(PX);  // pixels per staging chunk
@@ -323,11 +341,15 @@ __device__ __forceinline__ void project_lds_tile(const PX* __restrict__ src, PX*
         if (xa + tx <= xb)
             for (int q = 0; q < RPT; ++q) {
                 const int y = ya + ty * RPT + q;
-                if (y <= yb) project_px_global<PX>(src, dst, w, h, 0, r, xa + tx, y, gray, gray_f32);
+                if (y > yb) continue;
+                if constexpr (STAGE::kPlanarSource)
+                    project_px_global<PX>(src, dst, w, h, 0, r, xa + tx, y, gray, gray_f32);
+                else
+                    pj_zero_px<PX>(dst, pl, (size_t)y * w + xa + tx);
             }
         return;
     }
-    pj_stage_box<PX, TH>(src, pl, w, r0, nrow, c0a, ncol, pj_smem);
+    stage(src, pl, w, r0, nrow, c0a, ncol, pj_smem);
     __syncthreads();
     if (xa + tx > xb) return;
     const float u = col.u;
@@ -375,9 +397,9 @@ __global__ __launch_bounds__(256) void k_project_lds(const PX* __restrict__ src,
 // source ROW u depend on the output row alone, the source column v = (x - w/2)/k(y) + w/2 on both.  Same tiling; the per-row
 // terms of a tile's TH rows are evaluated by TH work-items and shared through LDS, the tile's source box is bounded by its
 // first and last row (u grows with y) and, for the columns, by its rows nearest to / farthest from the axis.
-template <typename PX, int TW, int TH>
+template <typename PX, int TW, int TH, typename STAGE = PjStagePlanar<PX, TH>>
 __device__ __forceinline__ void project_lds_tile_t(const PX* __restrict__ src, PX* __restrict__ dst, int w, int h, float r,
-                                                   uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes) {
+                                                   uint8_t* __restrict__ gray, float* __restrict__ gray_f32, int lds_bytes, STAGE stage = STAGE()) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pj_smem[];
     __shared__ ProjCol corner[4];
     __shared__ __attribute__((aligned(16))) ProjRow rowc[TH];
@@ -415,11 +437,15 @@ __device__ __forceinline__ void project_lds_tile_t(const PX* __restrict__ src, P
         if (x <= xb)
             for (int q = 0; q < RPT; ++q) {
                 const int y = ya + ty * RPT + q;
-                if (y <= yb) project_px_global<PX>(src, dst, w, h, 1, r, x, y, gray, gray_f32);
+                if (y > yb) continue;
+                if constexpr (STAGE::kPlanarSource)
+                    project_px_global<PX>(src, dst, w, h, 1, r, x, y, gray, gray_f32);
+                else
+                    pj_zero_px<PX>(dst, pl, (size_t)y * w + x);
             }
         return;
     }
-    pj_stage_box<PX, TH>(src, pl, w, r0, nrow, c0a, ncol, pj_smem);
+    stage(src, pl, w, r0, nrow, c0a, ncol, pj_smem);
     __syncthreads();
     if (x > xb) return;
     const __amdgpu_buffer_rsrc_t rd = plane_rsrc(dst, 3 * pl);

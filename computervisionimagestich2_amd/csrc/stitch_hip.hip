@@ -32,6 +32,7 @@
 #include "stitch_calibrate.h"
 #include "stitch_rig_seams.h"
 #include "stitch_rig_crop.h"
+#include "stitch_rig_formats.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2571,3 +2572,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_calibrate.inc"
 #include "stitch_rig_seams.inc"
 #include "stitch_rig_crop.inc"
+#include "stitch_rig_formats.inc"

@@ -41,9 +41,17 @@ struct stitch_rig {
     stitch_rect crop{0, 0, 0, 0};
     uint8_t* crop_full = nullptr;  // max_sets full canvases the last step writes, `crop_full_bytes` apart; from the first cropped call on
     size_t crop_full_bytes = 0;
+    // ---- frames and outputs in camera layouts (include/stitch_rig_formats.h; stitch_rig_formats.inc) ----
+    int in_fmt = 0, out_fmt = 0, matrix = 0;  // (0, 0): planar both ways, the replay as it is
+    std::vector<uint8_t*> fmt_in;  // per projected frame: max_sets planar frames the input is converted to; from the first such call on
+    uint8_t* fmt_out = nullptr;    // max_sets planar outputs the last step (or the crop copy) writes, `fmt_out_bytes` apart; likewise
+    size_t fmt_out_bytes = 0;
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
         if (crop_full) (void)hipFree(crop_full);
+        if (fmt_out) (void)hipFree(fmt_out);
+        for (uint8_t* p : fmt_in)
+            if (p) (void)hipFree(p);
         if (cover) (void)hipFree(cover);
         for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
             if (p) (void)hipFree(p);
@@ -70,6 +78,22 @@ int rig_ex_transfer(stitch_rig* R, const unsigned char* d_tables, int k, int m, 
 // out of the m buffers of a sequence (the src entries of the table) to the caller's (the dst entries), one launch.
 int rig_crop_workspace(stitch_rig* R);
 int rig_crop_copy(const stitch_rig* R, const RigImage* d_tab, int m, hipStream_t s);
+
+// A call with images (stitch_rig_formats.inc; NULL: the planar calls).  The call has checked its images; its device table holds, per
+// sequence, m entries per projected frame (a formatted input) and then m for the outputs (a formatted output).
+struct RigFmtCall {
+    const stitch_image* frames;
+    const stitch_image* out;
+    std::vector<char> fused;    // per frame index: its projection stages the packed source itself (rig_fmt_workspace decides)
+    std::vector<FmtImage> tab;  // filled by rig_fmt_tables
+    FmtImage* d_tab = nullptr;
+};
+int rig_fmt_workspace(stitch_rig* R, RigFmtCall* fc, int n_sets);
+void rig_fmt_tables(const stitch_rig* R, RigFmtCall* fc, const RigImage* h_tab, int n_sets);
+int rig_fmt_unpack(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int h, hipStream_t s);
+int rig_fmt_project(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int h, hipStream_t s);  // the fused form of rig_project_many
+// the end of a sequence with a formatted output: histogram and LUT where the rig finishes, the crop copy of mode 2, then the one pack
+int rig_fmt_finish_pack(const stitch_rig* R, const RigImage* h_tab, const RigImage* d_tab, const FmtImage* d_fmt, int32_t* d_eq, int m, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -99,22 +123,29 @@ int rig_project_many(const RigImage* h_tab, const RigImage* d_tab, int count, in
     return launch_check("k_project_many");
 }
 
-// `count` same-size mosaics (the dst entries of the table) through the finish pass in three launches.  d_scratch: RIG_EQ_WORDS
-// int32 per mosaic, the bins zeroed.  The word form only when every mosaic allows it (words_ok).
-int rig_finish_many(const RigImage* h_tab, const RigImage* d_tab, int32_t* d_scratch, int count, int w, int h, double num, double den, hipStream_t s) {
+// The first two launches of the finish pass on `count` same-size mosaics (the dst entries of the table): histogram and LUT.
+// d_scratch: RIG_EQ_WORDS int32 per mosaic, the bins zeroed.  -> whether the word form ran: only when every mosaic allows it
+// (words_ok).  Shared with the pack of stitch_rig_formats.inc, which applies the LUT itself.
+bool rig_hist_lut_many(const RigImage* h_tab, const RigImage* d_tab, int32_t* d_scratch, int count, int w, int h, hipStream_t s) {
     const size_t n = (size_t)w * h;
     bool v4 = true;
     for (int i = 0; i < count; ++i) v4 = v4 && words_ok(h_tab[i].dst, n);
-    const MixK mk = mix_params(num, den);
-    if (v4) {
+    if (v4)
         k_hist_many<true><<<dim3((unsigned)std::min(eq_grid(n / 4), 512), (unsigned)count), HIST_WAVES * 64, 0, s>>>(d_tab, n, d_scratch);
-        k_lut_many<<<(unsigned)count, 256, 0, s>>>(d_scratch, w, h);
-        k_finish_apply_many<true><<<dim3((unsigned)eq_grid(n / 4), (unsigned)count), 256, 0, s>>>(d_tab, n, d_scratch, mk);
-    } else {
+    else
         k_hist_many<false><<<dim3((unsigned)eq_grid(n), (unsigned)count), HIST_WAVES * 64, 0, s>>>(d_tab, n, d_scratch);
-        k_lut_many<<<(unsigned)count, 256, 0, s>>>(d_scratch, w, h);
+    k_lut_many<<<(unsigned)count, 256, 0, s>>>(d_scratch, w, h);
+    return v4;
+}
+
+// `count` same-size mosaics through the finish pass in three launches: the two above, then the apply pass in the same form.
+int rig_finish_many(const RigImage* h_tab, const RigImage* d_tab, int32_t* d_scratch, int count, int w, int h, double num, double den, hipStream_t s) {
+    const size_t n = (size_t)w * h;
+    const MixK mk = mix_params(num, den);
+    if (rig_hist_lut_many(h_tab, d_tab, d_scratch, count, w, h, s))
+        k_finish_apply_many<true><<<dim3((unsigned)eq_grid(n / 4), (unsigned)count), 256, 0, s>>>(d_tab, n, d_scratch, mk);
+    else
         k_finish_apply_many<false><<<dim3((unsigned)eq_grid(n), (unsigned)count), 256, 0, s>>>(d_tab, n, d_scratch, mk);
-    }
     return launch_check("finish_many");
 }
 
@@ -351,7 +382,7 @@ namespace {
 
 // stitch_dev_rig_stitch_u8, and stitch_dev_rig_stitch_exposure_u8 with its statistics (a host array, or NULL)
 int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status, stitch_seam* seams, float* stats,
-               void* stream) {
+               void* stream, RigFmtCall* fc = nullptr) {
     int rc = need_device();
     if (rc) return rc;
     if (!rig || !frames || !d_out || !set_status || n_sets < 1) return fail(STITCH_ERR_ARG, "rig_stitch: null argument or %d sets", n_sets);
@@ -361,7 +392,8 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     // include/stitch_rig_crop.h: a cropped rig writes the rectangle to d_out, and its last step a full canvas of the rig's own
     const bool cropped = R->crop_mode != 0;
     const size_t out_bytes = cropped ? (size_t)3 * R->crop.w * R->crop.h : (size_t)3 * R->out_w * R->out_h;
-    for (int i = 0; i < n_sets; ++i) {
+    const bool fin = fc && rig->in_fmt, fout = fc && rig->out_fmt;  // (a call with images has checked them itself)
+    for (int i = 0; i < n_sets && !fc; ++i) {
         if (!d_out[i]) return fail(STITCH_ERR_ARG, "rig_stitch: set %d has no output buffer", i);
         for (int f = 0; f < n; ++f) {
             const stitch_frame_u8& fr = frames[(size_t)i * n + f];
@@ -380,6 +412,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     }
     if ((rc = rig_workspaces(R))) return rc;
     if (cropped && (rc = rig_crop_workspace(R))) return rc;
+    if ((fin || fout) && (rc = rig_fmt_workspace(R, fc, n_sets))) return rc;
     hipStream_t s = as_stream(stream);
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
 
@@ -389,6 +422,12 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     // (a cropped rig: the outputs' entries name the full canvas as their source, and one more slice names it as a destination)
     std::vector<RigImage> tab((size_t)(n_need + (cropped ? 2 : 1)) * n_sets);
     auto full_of = [&](int i) { return R->crop_full + (size_t)i * R->crop_full_bytes; };  // set i of a sequence
+    // set `set`, the i-th of its sequence: where its output goes, and frame f as the projection reads it
+    // (a formatted output whose pack reads the full canvases has no buffer of its own: NULL, which nothing reads)
+    auto out_of = [&](int set, int i) { return !fout ? d_out[set] : R->fmt_out ? R->fmt_out + (size_t)i * R->fmt_out_bytes : nullptr; };
+    auto src_of = [&](int set, int i, int f) {  // (NULL: the projection stages the packed frame itself)
+        return !fin ? (const uint8_t*)frames[(size_t)set * n + f].data : fc->fused[f] ? nullptr : R->fmt_in[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
+    };
     {
         size_t at = 0;
         int set0 = 0;
@@ -396,10 +435,10 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             for (int f : R->needed)
                 for (int i = 0; i < m; ++i) {
                     // zero steps: the start frame is projected straight into the caller's buffer
-                    uint8_t* dst = ns == 0 ? (cropped ? full_of(i) : d_out[set0 + i]) : R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
-                    tab[at++] = RigImage{frames[(size_t)(set0 + i) * n + f].data, dst};
+                    uint8_t* dst = ns == 0 ? (cropped ? full_of(i) : out_of(set0 + i, i)) : R->proj[f] + (size_t)i * 3 * R->fw[f] * R->fh[f];
+                    tab[at++] = RigImage{src_of(set0 + i, i, f), dst};
                 }
-            for (int i = 0; i < m; ++i) tab[at++] = RigImage{cropped ? full_of(i) : nullptr, d_out[set0 + i]};
+            for (int i = 0; i < m; ++i) tab[at++] = RigImage{cropped ? full_of(i) : nullptr, out_of(set0 + i, i)};
             for (int i = 0; cropped && i < m; ++i) tab[at++] = RigImage{nullptr, full_of(i)};
             set0 += m;
         }
@@ -415,10 +454,12 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     const size_t up_bytes = ex_bytes ? up.size() : tab_bytes;
     const void* up_from = ex_bytes ? (const void*)up.data() : (const void*)tab.data();
     std::vector<float> h_stats(stats ? (size_t)16 * ns * n_sets : 0);  // 16 floats per set and step, as on the device
+    if (fc) rig_fmt_tables(R, fc, tab.data(), n_sets);
     PanoArena A(s);
     unsigned char* d_up = nullptr;
     int32_t* d_eq = nullptr;
     if ((rc = A.take(&d_up, up_bytes))) return rc;
+    if (fc && !fc->tab.empty() && (rc = A.take(&fc->d_tab, sizeof(FmtImage) * fc->tab.size()))) return rc;
     RigImage* d_tab = reinterpret_cast<RigImage*>(d_up);
     if (R->finish && (rc = A.take(&d_eq, sizeof(int32_t) * RIG_EQ_WORDS * n_sets))) return rc;
     // the tables are read by their upload, h_stats is written by the statistics' copies, and what the arena frees is idle: every
@@ -426,6 +467,8 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     PanoWait wait{s};
     RigOutcome O(R, n_sets, set_status, seams);  // destroyed before the wait: reads what is pending
     HIPCHK(hipMemcpyAsync(d_up, up_from, up_bytes, hipMemcpyHostToDevice, s));
+    if (fc && fc->d_tab) HIPCHK(hipMemcpyAsync(fc->d_tab, fc->tab.data(), sizeof(FmtImage) * fc->tab.size(), hipMemcpyHostToDevice, s));
+    size_t fat = 0;  // the place in the images' table
     if (R->finish) HIPCHK(hipMemsetAsync(d_eq, 0, sizeof(int32_t) * RIG_EQ_WORDS * n_sets, s));
 
     size_t at = 0;
@@ -435,7 +478,13 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         O.set0 = set0;
         O.m = m;
         for (int f : R->needed) {
-            if ((rc = rig_project_many(tab.data() + at, d_tab + at, m, R->fw[f], R->fh[f], R->fov_deg, s))) return rc;
+            if (fin && fc->fused[f]) {
+                if ((rc = rig_fmt_project(R, fc->d_tab + fat, m, R->fw[f], R->fh[f], s))) return rc;
+            } else {
+                if (fin && (rc = rig_fmt_unpack(R, fc->d_tab + fat, m, R->fw[f], R->fh[f], s))) return rc;
+                if ((rc = rig_project_many(tab.data() + at, d_tab + at, m, R->fw[f], R->fh[f], R->fov_deg, s))) return rc;
+            }
+            if (fin) fat += m;
             at += m;
         }
         const uint8_t* cur = ns ? R->proj[R->start] : nullptr;
@@ -460,7 +509,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
                 d.mh = mh;
                 d.ox = st.geom.ox;
                 d.oy = st.geom.oy;
-                d.out = !last ? R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes : cropped ? full_of(i) : d_out[set0 + i];
+                d.out = !last ? R->mosaic[k & 1] + (size_t)i * R->mosaic_bytes : cropped ? full_of(i) : out_of(set0 + i, i);
             }
             // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
             if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
@@ -475,7 +524,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             mw = st.geom.cw;
             mh = st.geom.ch;
         }
-        if (!cropped) {
+        if (fout) {
+            if ((rc = rig_fmt_finish_pack(R, tab.data() + at, d_tab + at, fc->d_tab + fat, R->finish ? d_eq + (size_t)RIG_EQ_WORDS * set0 : nullptr, m, s))) return rc;
+            fat += m;
+            if (cropped) at += m;
+        } else if (!cropped) {
             if (R->finish && (rc = rig_finish_many(tab.data() + at, d_tab + at, d_eq + (size_t)RIG_EQ_WORDS * set0, m, R->out_w, R->out_h, R->num, R->den, s))) return rc;
         } else {
             // mode 1 finishes the full canvases and copies; mode 2 copies and finishes the rectangles as images of their own
@@ -513,6 +566,7 @@ extern "C" {
 
 int stitch_dev_rig_stitch_u8(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status,
                              stitch_seam* seams, void* stream) {
+    if (rig && (rig->in_fmt || rig->out_fmt)) return fail(STITCH_ERR_ARG, "rig_stitch: the rig has formats set (include/stitch_rig_formats.h): call stitch_dev_rig_stitch_fmt_u8");
     return rig_stitch(rig, frames, n_sets, d_out, set_status, seams, nullptr, stream);
 }
 

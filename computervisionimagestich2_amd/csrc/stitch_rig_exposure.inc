@@ -137,6 +137,7 @@ int stitch_rig_from_panorama_exposure(const stitch_panorama* pano, const stitch_
 
 int stitch_dev_rig_stitch_exposure_u8(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status,
                                       stitch_seam* seams, float* stats, void* stream) {
+    if (rig && (rig->in_fmt || rig->out_fmt)) return fail(STITCH_ERR_ARG, "rig_stitch: the rig has formats set (include/stitch_rig_formats.h): call stitch_dev_rig_stitch_fmt_u8");
     return rig_stitch(rig, frames, n_sets, d_out, set_status, seams, stats, stream);
 }
 

@@ -126,7 +126,7 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
     return proj_dst
 
 
-def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None):
+def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -141,7 +141,17 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     (include/stitch_rig_seams.h): the single-set chain with given seams, the yardstick of a rig with fixed seams.
     crop: a pair ((x0, y0, w, h), mode) (include/stitch_rig_crop.h), applied with plain slicing: mode 1 the slice of the finished
     mosaic, mode 2 the finish pass on the slice of the unfinished one -- the single-set statement of a cropped rig.
+    formats: (in_fmt, out_fmt, matrix) (include/stitch_rig_formats.h), through the conversions on their own: the frames are
+    capi.Images of in_fmt, unpacked first (capi.dev_unpack_many); the result is packed last (capi.dev_pack_many) and returned as a
+    capi.Image of out_fmt at tight pitch.  A planar side stays a tensor -- the single-set statement of a rig with formats.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
+    if formats is not None:
+        in_fmt, out_fmt, matrix = formats
+        if in_fmt != capi.PIX_PLANAR:
+            used_frames = {steps[0]["start"]} | {st["src"] for st in steps}  # the rig reads no other frame either
+            frames = [capi.dev_unpack_many([f], matrix)[0] if i in used_frames else None for i, f in enumerate(frames)]
+        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop)
+        return result if out_fmt == capi.PIX_PLANAR else capi.dev_pack_many([result], out_fmt, matrix)[0]
     proj = {}
 
     def projected(i):
