@@ -189,6 +189,15 @@ RIG_FORMAT_SIGNATURES = _signatures(
     ("stitch_dev_rig_stitch_fmt_u8", i32, vp, vp, i32, vp, vp, vp, vp, vp),
 )
 
+# The same for include/stitch_rig_monitor.h, a rig's alignment monitor; tests/test_rig_monitor_host.py holds it to that header.
+# (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the eight.)
+RIG_MONITOR_SIGNATURES = _signatures(
+    ("stitch_residual_words", i32, i32), ("stitch_dev_pairs_residual_u8", i32, vp, i32, i32, i32, vp, i32, vp, vp),
+    ("stitch_rig_set_monitor", i32, vp, i32), ("stitch_rig_clear_monitor", i32, vp), ("stitch_rig_monitor", i32, vp, vp),
+    ("stitch_rig_residuals", i32, vp, vp, sz, vp, vp, vp), ("stitch_dev_rig_residual_domain_u8", i32, vp, i32, i32, vp, vp),
+    ("stitch_residual_best_shift", i32, vp, i32, i32, vp, vp),
+)
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -234,9 +243,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h (likewise)
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
-                + list(RIG_FORMAT_SIGNATURES.items()):
+                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1776,6 +1785,54 @@ class Rig(_Handle):
         _chk(lib().stitch_rig_formats(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def set_monitor(self, radius):
+        """stitch_rig_set_monitor (host only): every later stitch() also measures, per set and step, the residuals of the blend's
+        two inputs over the step's overlap under every integer shift within `radius` (0 .. 8; include/stitch_rig_monitor.h);
+        residuals() reads them.  Outputs, statuses, seams and statistics stay what they are.  Returns self."""
+        _chk(lib().stitch_rig_set_monitor(self._h, int(radius)))
+        return self
+
+    def clear_monitor(self):
+        """stitch_rig_clear_monitor: no monitor.  Returns self."""
+        _chk(lib().stitch_rig_clear_monitor(self._h))
+        return self
+
+    @property
+    def monitor(self):
+        """stitch_rig_monitor: the monitor's radius, or None when none is set."""
+        r = C.c_int(-1)
+        _chk(lib().stitch_rig_monitor(self._h, C.byref(r)))
+        return None if r.value < 0 else r.value
+
+    def residuals(self):
+        """stitch_rig_residuals (host only): the records of the last monitored stitch() as an (n_sets, n_steps, words) uint64 numpy
+        array -- n, sum_b, then sum_a, sad, ssd per shift; n_sets = 0 when there is none."""
+        n_sets, n_steps, radius = C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_residuals(self._h, None, 0, C.byref(n_sets), C.byref(n_steps), C.byref(radius)))
+        words = residual_words(radius.value) if radius.value >= 0 else 0
+        out = np.zeros((n_sets.value, n_steps.value, words), np.uint64)
+        if out.size:
+            _chk(lib().stitch_rig_residuals(self._h, _p(out), out.size, None, None, None))
+        return out
+
+    def residual_domain(self, step=-1, radius=None, out=None, device=None):
+        """stitch_dev_rig_residual_domain_u8 on torch's current stream: the domain the monitor sums step's records over, as a
+        (ch, cw) uint8 tensor of 0 / 255 -- the moved mosaic's coverage and the warped frame's, eroded by the shift box of `radius`
+        (None: the monitor's).  Does not change the rig's monitor."""
+        import torch
+        if radius is None:
+            radius = self.monitor
+            if radius is None:
+                raise ValueError("no monitor is set: state the radius")
+        cw, ch = C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_step_canvas(self._h, int(step), C.byref(cw), C.byref(ch)))
+        w, h = cw.value, ch.value
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=device or "cuda")
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= w * h
+        _chk(lib().stitch_dev_rig_residual_domain_u8(self._h, int(step), int(radius), _dp(out), _stream()))
+        return out
+
     def _stitch_fmt(self, sets, out, return_stats):
         """stitch() of a rig with a format set: stitch_dev_rig_stitch_fmt_u8."""
         in_fmt, out_fmt, _ = self.formats
@@ -1936,6 +1993,53 @@ def calibrate(sets, pooled_threshold=0, sift_opts=None, ransac_opts=None, kp_cap
 
 def _ptr_table(tensors):
     return (C.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+
+
+# ---- a rig's alignment monitor: include/stitch_rig_monitor.h ------------------------------------------------------------------
+def residual_words(radius):
+    """stitch_residual_words (host only): the words of a record, 2 + 3 * (2 * radius + 1) ** 2; 0 for a radius outside 0 .. 8."""
+    return lib().stitch_residual_words(int(radius))
+
+
+def dev_pairs_residual(pairs, cw, ch, domains, radius):
+    """stitch_dev_pairs_residual_u8 on torch's current stream, which it waits for.  pairs: (frame, p, offx, offy, mosaic, ox, oy)
+    with (3, H, W) uint8 device tensors -- the inputs of a blend; domains: one (ch, cw) uint8 device mask per pair (non-zero = in the
+    domain; the same tensor may serve several pairs).  Returns an (n, words) int64 device tensor of records: n, sum_b, then
+    sum_a, sad, ssd per shift, dy-major (every value is below 2^51)."""
+    import torch
+    pairs, domains = list(pairs), list(domains)
+    if len(domains) != len(pairs) or not pairs:
+        raise ValueError("one domain per pair, and at least one pair")
+    arr = (PairDesc * len(pairs))()
+    for d, it in zip(arr, pairs):
+        frame, p, offx, offy, mosaic, ox, oy = it[:7]
+        frame, mosaic = _timg(frame), _timg(mosaic)
+        if frame.dtype != torch.uint8 or mosaic.dtype != torch.uint8:
+            raise TypeError("expected uint8 images")
+        d.frame, d.fw, d.fh = frame.data_ptr(), frame.shape[2], frame.shape[1]
+        d.p = _map8(p)
+        d.offx, d.offy = float(offx), float(offy)
+        d.mosaic, d.mw, d.mh = mosaic.data_ptr(), mosaic.shape[2], mosaic.shape[1]
+        d.ox, d.oy = int(ox), int(oy)
+    for m in domains:
+        if not m.is_cuda or not m.is_contiguous() or m.dtype != torch.uint8 or tuple(m.shape) != (ch, cw):
+            raise ValueError(f"every domain is a contiguous ({ch}, {cw}) uint8 device mask")
+    words = residual_words(radius)
+    rec = torch.empty((len(pairs), max(words, 1)), dtype=torch.int64, device=pairs[0][0].device)
+    _chk(lib().stitch_dev_pairs_residual_u8(arr, len(pairs), int(cw), int(ch), _ptr_table(domains), int(radius), _dp(rec), _stream()))
+    return rec
+
+
+def residual_best_shift(record, radius, zero_mean=False):
+    """stitch_residual_best_shift (host only): (dx, dy) of the shift a record favours -- the least ssd, or with zero_mean the least
+    n * ssd - (sum_a - sum_b) ** 2, compared exactly; ties to the shortest shift, then the smallest dy, then the smallest dx.
+    Raises StitchError(ERR_ZERO_OVERLAP) for a record with n == 0."""
+    rec = np.ascontiguousarray(np.asarray(record.cpu() if hasattr(record, "cpu") else record).astype(np.uint64).reshape(-1))
+    if rec.size != residual_words(radius) or not rec.size:
+        raise ValueError(f"a record of radius {radius} has {residual_words(radius)} words, got {rec.size}")
+    dx, dy = C.c_int(), C.c_int()
+    _chk(lib().stitch_residual_best_shift(_p(rec), int(radius), int(bool(zero_mean)), C.byref(dx), C.byref(dy)))
+    return dx.value, dy.value
 
 
 def dev_project_many(srcs, fov_deg=15.0, out=None):

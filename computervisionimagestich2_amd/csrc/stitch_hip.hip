@@ -33,6 +33,7 @@
 #include "stitch_rig_seams.h"
 #include "stitch_rig_crop.h"
 #include "stitch_rig_formats.h"
+#include "stitch_rig_monitor.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -2573,3 +2574,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_rig_seams.inc"
 #include "stitch_rig_crop.inc"
 #include "stitch_rig_formats.inc"
+#include "stitch_rig_monitor.inc"

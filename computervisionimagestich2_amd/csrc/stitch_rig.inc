@@ -46,6 +46,16 @@ struct stitch_rig {
     std::vector<uint8_t*> fmt_in;  // per projected frame: max_sets planar frames the input is converted to; from the first such call on
     uint8_t* fmt_out = nullptr;    // max_sets planar outputs the last step (or the crop copy) writes, `fmt_out_bytes` apart; likewise
     size_t fmt_out_bytes = 0;
+    // ---- the alignment monitor (include/stitch_rig_monitor.h; stitch_rig_monitor.inc) ----
+    int mon_radius = -1;                     // -1: no monitor, the replay as it is
+    int mon_dom_radius = -1;                 // the radius the domains below were computed at, -1: not computed yet
+    unsigned long long* mon_dom = nullptr;   // D_k of every step as bit planes, one block, then 4 words of bounding box per step
+    std::vector<size_t> mon_dom_at;          // word offsets per step
+    size_t mon_dom_words = 0;
+    std::vector<stitch_rect> mon_box;        // per step: what a residual launch covers (w = 0: an empty domain)
+    unsigned long long* mon_rec = nullptr;   // the records of the sequence in flight: max_sets sets, set-major then step
+    std::vector<uint64_t> mon_last;          // the records of the last monitored replay, and whose they are
+    int mon_last_sets = 0, mon_last_radius = -1;
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
         if (crop_full) (void)hipFree(crop_full);
@@ -53,6 +63,8 @@ struct stitch_rig {
         for (uint8_t* p : fmt_in)
             if (p) (void)hipFree(p);
         if (cover) (void)hipFree(cover);
+        if (mon_dom) (void)hipFree(mon_dom);
+        if (mon_rec) (void)hipFree(mon_rec);
         for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
             if (p) (void)hipFree(p);
         for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
@@ -94,6 +106,13 @@ int rig_fmt_unpack(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int
 int rig_fmt_project(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int h, hipStream_t s);  // the fused form of rig_project_many
 // the end of a sequence with a formatted output: histogram and LUT where the rig finishes, the crop copy of mode 2, then the one pack
 int rig_fmt_finish_pack(const stitch_rig* R, const RigImage* h_tab, const RigImage* d_tab, const FmtImage* d_fmt, int32_t* d_eq, int m, hipStream_t s);
+
+// The monitor of a rig that has one (stitch_rig_monitor.inc): its domains and record buffer, the zeroing of a sequence's records,
+// step k's residual launch over the m sets in flight from the step's pair descriptors, the copy of a sequence's records to the host.
+int rig_mon_prepare(stitch_rig* R, hipStream_t s);
+int rig_mon_begin(stitch_rig* R, int m, hipStream_t s);
+int rig_mon_step(stitch_rig* R, const stitch_pair_desc* pd, int k, int m, hipStream_t s);
+int rig_mon_collect(stitch_rig* R, uint64_t* host, int m, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -414,6 +433,15 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     if (cropped && (rc = rig_crop_workspace(R))) return rc;
     if ((fin || fout) && (rc = rig_fmt_workspace(R, fc, n_sets))) return rc;
     hipStream_t s = as_stream(stream);
+    // include/stitch_rig_monitor.h: a failed call leaves no records behind, a completed one its own
+    const bool monitored = R->mon_radius >= 0 && ns > 0;
+    if (R->mon_radius >= 0) {
+        R->mon_last.clear();
+        R->mon_last_sets = 0;
+    }
+    if (monitored && (rc = rig_mon_prepare(R, s))) return rc;
+    const size_t mon_words = monitored ? (size_t)(2 + 3 * (2 * R->mon_radius + 1) * (2 * R->mon_radius + 1)) * ns : 0;  // per set
+    std::vector<uint64_t> h_mon(mon_words * n_sets);  // written by the records' copies: waited for like h_stats
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
 
     // ---- the pointer tables of the whole call, uploaded once: per sequence one slice per projected frame, then the outputs ----
@@ -490,6 +518,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         const uint8_t* cur = ns ? R->proj[R->start] : nullptr;
         size_t cur_stride = (size_t)3 * R->fw[R->start] * R->fh[R->start];
         int mw = R->fw[R->start], mh = R->fh[R->start];
+        if (monitored && (rc = rig_mon_begin(R, m, s))) return rc;
         for (int k = 0; k < ns; ++k) {
             const stitch_panorama_step& st = R->steps[k];
             const int pi = R->plan_of_step[k], f = st.dst;
@@ -513,6 +542,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             }
             // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
             if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
+            if (monitored && (rc = rig_mon_step(R, pd.data(), k, m, s))) return rc;  // the blend's own inputs, before it runs
             if (!R->fixed.empty()) {  // include/stitch_rig_seams.h: the step's fixed record for each of the m sets
                 const std::vector<stitch_seam> given((size_t)m, R->fixed[k]);
                 if ((rc = stitch_dev_pairs_seamed_u8(R->plans[pi], pd.data(), m, given.data(), s))) return rc;
@@ -542,6 +572,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         // the sequence's statistics leave the device in one copy, behind its last transfer; the next sequence overwrites them
         if (!h_stats.empty())
             HIPCHK(hipMemcpyAsync(h_stats.data() + (size_t)16 * ns * set0, R->ex_stats, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
+        if (monitored && (rc = rig_mon_collect(R, h_mon.data() + mon_words * set0, m, s))) return rc;  // likewise
         O.read_all();  // the next sequence uses the same workspaces
         if (O.hip_fault) break;
         set0 += m;
@@ -552,6 +583,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     }
     HIPCHK(hipStreamSynchronize(s));  // the finish pass of the last sequence (read_all waited for the steps only)
     for (size_t j = 0; j < h_stats.size() / 16; ++j) std::memcpy(stats + 12 * j, h_stats.data() + 16 * j, sizeof(float) * 12);
+    if (R->mon_radius >= 0) {
+        R->mon_last.swap(h_mon);
+        R->mon_last_sets = n_sets;
+        R->mon_last_radius = R->mon_radius;
+    }
     for (int i = 0; i < n_sets; ++i)
         if (set_status[i] != STITCH_OK)
             return fail(set_status[i], "rig_stitch: set %d, step %d (frame %d): %s", i, O.fail_step[i], R->steps[O.fail_step[i]].dst,

@@ -126,7 +126,8 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
     return proj_dst
 
 
-def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None):
+def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None,
+                 residuals=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -144,14 +145,20 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     formats: (in_fmt, out_fmt, matrix) (include/stitch_rig_formats.h), through the conversions on their own: the frames are
     capi.Images of in_fmt, unpacked first (capi.dev_unpack_many); the result is packed last (capi.dev_pack_many) and returned as a
     capi.Image of out_fmt at tight pitch.  A planar side stays a tensor -- the single-set statement of a rig with formats.
+    residuals: dict(radius=r, domains=[one (ch, cw) uint8 device mask per step]) (include/stitch_rig_monitor.h): the chain also
+    measures every step's record by capi.dev_pairs_residual on the exact inputs of its blend -- after the transfer, where exposure
+    is set -- and returns (mosaic, records), records an (n_steps, words) int64 device tensor: the single-set statement of a rig
+    with a monitor.  With residuals=None the return value and every byte stay as they are.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     if formats is not None:
         in_fmt, out_fmt, matrix = formats
         if in_fmt != capi.PIX_PLANAR:
             used_frames = {steps[0]["start"]} | {st["src"] for st in steps}  # the rig reads no other frame either
             frames = [capi.dev_unpack_many([f], matrix)[0] if i in used_frames else None for i, f in enumerate(frames)]
-        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop)
-        return result if out_fmt == capi.PIX_PLANAR else capi.dev_pack_many([result], out_fmt, matrix)[0]
+        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop, residuals=residuals)
+        result, records = result if residuals is not None else (result, None)
+        result = result if out_fmt == capi.PIX_PLANAR else capi.dev_pack_many([result], out_fmt, matrix)[0]
+        return result if residuals is None else (result, records)
     proj = {}
 
     def projected(i):
@@ -163,8 +170,10 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         seams = list(seams)
         if len(seams) != len(steps):
             raise ValueError("one seam per step")
+    if residuals is not None and len(residuals["domains"]) != len(steps):
+        raise ValueError("one residual domain per step")
     result = projected(steps[0]["start"])
-    used = []
+    used, records = [], []
     for k, st in enumerate(steps):
         key = (st["cw"], st["ch"])
         plan = plans.get(key) if plans is not None else None
@@ -176,6 +185,9 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             plan.status()
         if exposure:
             exposure_match(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black)
+        if residuals is not None:
+            records.append(capi.dev_pairs_residual([(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])], st["cw"], st["ch"],
+                                                   [residuals["domains"][k]], residuals["radius"])[0])
         result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"], seam=None if seams is None else seams[k])
         used.append(plan)
     if crop is not None:
@@ -199,6 +211,9 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         if plans is None:
             for plan in used:
                 plan.close()
+    if residuals is not None:
+        import torch
+        return result, (torch.stack(records) if records else torch.empty((0, capi.residual_words(residuals["radius"])), dtype=torch.int64, device=result.device))
     return result
 
 
