@@ -138,7 +138,10 @@ struct ZeroTiles {
 // tile column t reads the tile columns 2t and 2t + 1 of the level above, and where 2t + 1 lies past that level's last tile column (an
 // odd count of them) it neither takes its all-zero path nor passes for a zero neighbour: t counts as zero, for itself and as a neighbour,
 // only if 2t + 1 < ceil(w_{l-1} / 64).  Below such a level the last two tile columns are therefore never flagged, whatever they hold:
-// they are stored and read like data (tests/g_flags_ref.py states the rule on the host).  Carried as a ZeroTiles with one "band":
+// they are stored and read like data (tests/g_flags_ref.py states the rule on the host).  The producer decides from what it READS, the
+// zero-tile flags of the blurred tile columns 2t and 2t + 1 and a +0 sweep state, so the flag is sufficient for "+0 throughout", not
+// necessary: where the blur's tail ends on an odd column, which the decimation drops, the tile column of G is +0 in every sample
+// and still stored as data (tests/test_gpu_hard_content.py: a black band inside a frame).  Carried as a ZeroTiles with one "band":
 // index(plane, 0, tile) = plane * NC + tile.  Readers (k_vv_x_fwd, the collapse kernels) take zeros instead of loading; a 16-byte
 // load of the collapse that straddles two tile columns is zero when either column is flagged: a flagged column's neighbours are zero,
 // and an unflagged DATA column never has a flagged neighbour.

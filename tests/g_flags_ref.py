@@ -38,19 +38,26 @@ def tile_columns(w):
     return (w + TS - 1) // TS
 
 
-def flagged_in_level(g, parent_w, ragged_exception=True):
+def flagged_in_level(g, parent_w, ragged_exception=True, parent_blurred=None):
     """Flagged tile columns of the planes g (planes, rows, columns; float32) of a level produced from a level parent_w wide.
     A 64-column tile column counts when it is +0 by bit pattern in every row and so are both neighbouring tile columns; the plane's
     edge counts as a zero neighbour.  A level produced from an odd width has no flags.
     ragged_exception: the producer's workgroup of tile column t reads the parent's tile columns 2t and 2t + 1, and where the second
     lies past the parent's last tile column (an odd count of them) it neither takes its all-zero path nor is it taken for a zero
     neighbour: t can count as zero, for itself and as a neighbour, only if 2t + 1 < ceil(parent_w / 64).  So the last tile column of
-    such a level and the one before it are never flagged.  False: the rule without that exception."""
+    such a level and the one before it are never flagged.  False: the rule without that exception.
+    parent_blurred: the blurred planes of the level above, before the decimation.  The producer takes its all-zero path from what it
+    READS -- the blurred tile columns 2t and 2t + 1 of the level above, +0 throughout -- not from what it writes: where the blur's
+    tail ends on an odd column, which the decimation drops, the tile column of G is +0 in every sample and still stored as data.
+    Given the planes, t counts as zero only if those 128 columns are +0 as well."""
     g = np.ascontiguousarray(g, dtype=np.float32)
     if parent_w & 1:
         return 0
     nc = tile_columns(g.shape[2])
     zero = np.array([[not g[q, :, t * TS:(t + 1) * TS].view(np.uint32).any() for t in range(nc)] for q in range(g.shape[0])]).reshape(g.shape[0], nc)
+    if parent_blurred is not None:
+        pb = np.ascontiguousarray(parent_blurred, dtype=np.float32)
+        zero &= np.array([[not pb[q, :, 2 * t * TS:(2 * t + 2) * TS].view(np.uint32).any() for t in range(nc)] for q in range(g.shape[0])]).reshape(g.shape[0], nc)
     if ragged_exception:
         zero &= (2 * np.arange(nc) + 1 < tile_columns(parent_w))[None, :]
     pad = np.pad(zero, ((0, 0), (1, 1)), constant_values=True)
@@ -58,12 +65,14 @@ def flagged_in_level(g, parent_w, ragged_exception=True):
 
 
 def flagged_columns(oracle, a, b, levels=2, ragged_exception=True):
-    """[count at level 1, count at level 2] under the rule (flagged_in_level), from the oracle's planes of the canvases a and b."""
+    """[count at level 1, count at level 2] under the rule (flagged_in_level, with the blurred planes of the level above: what the
+    producer reads), from the oracle's planes of the canvases a and b."""
     g = np.concatenate([a, b]).astype(np.float32)
     _, lw, lh = oracle.pyramid_levels(g.shape[2], g.shape[1], OPTS["level_rule"])
     counts = []
     for lv in range(1, levels + 1):
         parent_w = g.shape[2]
-        g = oracle.decimate(oracle.blur(g), lw[lv], lh[lv])
-        counts.append(flagged_in_level(g, parent_w, ragged_exception))
+        blurred = oracle.blur(g)
+        g = oracle.decimate(blurred, lw[lv], lh[lv])
+        counts.append(flagged_in_level(g, parent_w, ragged_exception, blurred))
     return counts
