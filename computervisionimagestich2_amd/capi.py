@@ -198,6 +198,16 @@ RIG_MONITOR_SIGNATURES = _signatures(
     ("stitch_residual_best_shift", i32, vp, i32, i32, vp, vp),
 )
 
+# The same for include/stitch_seam_path.h, path seams; tests/test_seam_path_host.py holds it to that header.
+# (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks them.)
+SEAM_PATH_SIGNATURES = _signatures(
+    ("stitch_seam_path_opts_default", None, vp), ("stitch_plan_create_masked", i32, i32, i32, vp, i32, vp), ("stitch_plan_is_masked", i32, vp),
+    ("stitch_dev_pairs_pathed_*", i32, vp, vp, i32, vp, vp, vp),
+    ("stitch_dev_pairs_seam_path_u8", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp),
+    ("stitch_rig_set_seam_paths", i32, vp, vp), ("stitch_rig_fix_seam_paths", i32, vp, vp, i32), ("stitch_rig_clear_seam_paths", i32, vp),
+    ("stitch_rig_seam_paths", i32, vp, vp, vp), ("stitch_rig_last_seam_paths", i32, vp, i32, i32, vp, i32, vp),
+)
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -243,9 +253,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h (likewise)
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h, stitch_seam_path.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
-                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()):
+                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1176,10 +1186,12 @@ class Plan(_Handle):
     """stitch_plan: the device workspace of one canvas size (pyramids, scratch, tables, seam record)."""
     _destroy = "stitch_plan_destroy"
 
-    def __init__(self, cw, ch, opts=None, max_pairs=1):
+    def __init__(self, cw, ch, opts=None, max_pairs=1, masked=False):
+        """masked=True: stitch_plan_create_masked (include/stitch_seam_path.h), the workspace of pairs(paths=..., branches=...)."""
         self._h = C.c_void_p()
-        self.cw, self.ch, self.max_pairs = int(cw), int(ch), int(max_pairs)
-        _chk(lib().stitch_plan_create_batched(self.cw, self.ch, C.byref(_opts(opts)), self.max_pairs, C.byref(self._h)))
+        self.cw, self.ch, self.max_pairs, self.masked = int(cw), int(ch), int(max_pairs), bool(masked)
+        create = lib().stitch_plan_create_masked if masked else lib().stitch_plan_create_batched
+        _chk(create(self.cw, self.ch, C.byref(_opts(opts)), self.max_pairs, C.byref(self._h)))
         lw, lh = (C.c_int * 32)(), (C.c_int * 32)()
         n = _chk(lib().stitch_plan_levels(self._h, lw, lh))
         self.level_w, self.level_h = list(lw[:n]), list(lh[:n])
@@ -1239,12 +1251,24 @@ class Plan(_Handle):
                                             mosaic.shape[2], mosaic.shape[1], int(ox), int(oy), _dp(out), _stream()))
         return out
 
-    def pairs(self, items, seams=None):
+    def pairs(self, items, seams=None, paths=None, branches=None):
         """Enqueue n <= max_pairs independent pairs as ONE launch sequence.  items: iterable of
         (frame, p, offx, offy, mosaic, ox, oy, out[, out_u8]) with device tensors; out_u8 (float frames only) receives the
         mosaic as unsigned char as well.  seams (stitch_dev_pairs_seamed_*): one Seam or (sum_a_x, n_a, sum_ov_x, n_ov, ...) tuple
-        per item, which replaces that pair's seam scan.  Returns the list of `out` tensors."""
+        per item, which replaces that pair's seam scan.  paths, branches (stitch_dev_pairs_pathed_*, a masked plan): per item a
+        contiguous int32 device tensor of ch seam columns and its branch, 0 or 1; the blend cuts along them and no seam is scanned.
+        Returns the list of `out` tensors."""
         items = list(items)
+        if (paths is None) != (branches is None) or (paths is not None and seams is not None):
+            raise ValueError("paths come with branches, and without seams")
+        if paths is not None:
+            import torch
+            paths, branches = list(paths), [int(b) for b in branches]
+            if len(paths) != len(items) or len(branches) != len(items):
+                raise ValueError("one path and one branch per item")
+            for t in paths:
+                if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.int32 or tuple(t.shape) != (self.ch,):
+                    raise ValueError(f"every path is a contiguous ({self.ch},) int32 device tensor")
         if seams is not None:
             seams = list(seams)
             if len(seams) != len(items):
@@ -1267,7 +1291,9 @@ class Plan(_Handle):
                 import torch
                 assert out8.is_cuda and out8.is_contiguous() and out8.dtype == torch.uint8 and tuple(out8.shape) == (3, self.ch, self.cw)
                 d.out_u8 = out8.data_ptr()
-        if seams is not None:
+        if paths is not None:
+            _chk(_fn("stitch_dev_pairs_pathed_", items[0][0])(self._h, arr, len(items), _ptr_table(paths), (C.c_int32 * len(items))(*branches), _stream()))
+        elif seams is not None:
             _chk(_fn("stitch_dev_pairs_seamed_", items[0][0])(self._h, arr, len(items), _seam_array(seams), _stream()))
         else:
             _chk(fn(self._h, arr, len(items), _stream()))
@@ -1833,6 +1859,46 @@ class Rig(_Handle):
         _chk(lib().stitch_dev_rig_residual_domain_u8(self._h, int(step), int(radius), _dp(out), _stream()))
         return out
 
+    def set_seam_paths(self, max_step=2, margin=8):
+        """stitch_rig_set_seam_paths (include/stitch_seam_path.h): from now on every stitch() finds, per set and step, the least-cost
+        seam column of every row over the step's coverage (steps of at most max_step columns per row, coverage eroded by margin) and
+        blends along it, with no host round trip.  The seams stitch() returns are the geometric records.  Returns self."""
+        _chk(lib().stitch_rig_set_seam_paths(self._h, C.byref(SeamPathOpts(int(max_step), int(margin)))))
+        return self
+
+    def fix_seam_paths(self, paths):
+        """stitch_rig_fix_seam_paths: one path per step -- the step's ch seam columns, any integer sequence -- shared by all sets.
+        Returns self."""
+        rows = [np.ascontiguousarray(np.asarray(p.cpu() if hasattr(p, "cpu") else p).astype(np.int32).reshape(-1)) for p in paths]
+        for k, r in enumerate(rows[:self.n_steps]):
+            cw, ch = C.c_int(), C.c_int()
+            _chk(lib().stitch_rig_step_canvas(self._h, k, C.byref(cw), C.byref(ch)))
+            if r.size != ch.value:
+                raise ValueError(f"the path of step {k} has {ch.value} rows, got {r.size}")
+        _chk(lib().stitch_rig_fix_seam_paths(self._h, (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows]), len(rows)))
+        return self
+
+    def clear_seam_paths(self):
+        """stitch_rig_clear_seam_paths: vertical seams again.  Returns self."""
+        _chk(lib().stitch_rig_clear_seam_paths(self._h))
+        return self
+
+    @property
+    def seam_paths(self):
+        """stitch_rig_seam_paths: None, ("found", max_step, margin) or ("fixed",)."""
+        mode, o = C.c_int(), SeamPathOpts()
+        _chk(lib().stitch_rig_seam_paths(self._h, C.byref(mode), C.byref(o)))
+        return None if mode.value == 0 else ("found", o.max_step, o.margin) if mode.value == 1 else ("fixed",)
+
+    def last_seam_paths(self, set=0, step=0):
+        """stitch_rig_last_seam_paths (host only): (path, cost) of `set` at `step` in the last stitch() along paths -- an int32 numpy
+        array of the step's ch columns and the path's cost (0 for fixed paths)."""
+        cost = C.c_uint64()
+        ch = _chk(lib().stitch_rig_last_seam_paths(self._h, int(set), int(step), None, 0, None))
+        out = np.zeros(ch, np.int32)
+        _chk(lib().stitch_rig_last_seam_paths(self._h, int(set), int(step), _p(out), ch, C.byref(cost)))
+        return out, cost.value
+
     def _stitch_fmt(self, sets, out, return_stats):
         """stitch() of a rig with a format set: stitch_dev_rig_stitch_fmt_u8."""
         in_fmt, out_fmt, _ = self.formats
@@ -2028,6 +2094,47 @@ def dev_pairs_residual(pairs, cw, ch, domains, radius):
     rec = torch.empty((len(pairs), max(words, 1)), dtype=torch.int64, device=pairs[0][0].device)
     _chk(lib().stitch_dev_pairs_residual_u8(arr, len(pairs), int(cw), int(ch), _ptr_table(domains), int(radius), _dp(rec), _stream()))
     return rec
+
+
+# ---- path seams: include/stitch_seam_path.h -----------------------------------------------------------------------------------
+class SeamPathOpts(C.Structure):
+    """stitch_seam_path_opts: the step bound K (1 .. 8) and the coverage margin m (0 .. 64) of the finder."""
+    _fields_ = [("max_step", C.c_int32), ("margin", C.c_int32)]
+
+    def __init__(self, max_step=2, margin=8):
+        super().__init__(max_step, margin)
+
+
+def dev_pairs_seam_path(pairs, cw, ch, cov_a, cov_b, branches, max_step=2, margin=8):
+    """stitch_dev_pairs_seam_path_u8 on torch's current stream, which it waits for.  pairs: (frame, p, offx, offy, mosaic, ox, oy)
+    with (3, H, W) uint8 device tensors -- the inputs of a blend; cov_a, cov_b: per pair a (ch, cw) uint8 device mask of where the
+    warped frame / the moved mosaic can have data (non-zero = covered; tensors may serve several pairs); branches: per pair 0 or 1.
+    Returns (paths, costs): an (n, ch) int32 and an (n,) int64 device tensor -- the least-cost seam column of every row, and its cost."""
+    import torch
+    pairs, cov_a, cov_b, branches = list(pairs), list(cov_a), list(cov_b), [int(b) for b in branches]
+    if not pairs or not len(cov_a) == len(cov_b) == len(branches) == len(pairs):
+        raise ValueError("two masks and a branch per pair, and at least one pair")
+    arr = (PairDesc * len(pairs))()
+    for d, it in zip(arr, pairs):
+        frame, p, offx, offy, mosaic, ox, oy = it[:7]
+        frame, mosaic = _timg(frame), _timg(mosaic)
+        if frame.dtype != torch.uint8 or mosaic.dtype != torch.uint8:
+            raise TypeError("expected uint8 images")
+        d.frame, d.fw, d.fh = frame.data_ptr(), frame.shape[2], frame.shape[1]
+        d.p = _map8(p)
+        d.offx, d.offy = float(offx), float(offy)
+        d.mosaic, d.mw, d.mh = mosaic.data_ptr(), mosaic.shape[2], mosaic.shape[1]
+        d.ox, d.oy = int(ox), int(oy)
+    for m in cov_a + cov_b:
+        if not m.is_cuda or not m.is_contiguous() or m.dtype != torch.uint8 or tuple(m.shape) != (ch, cw):
+            raise ValueError(f"every coverage mask is a contiguous ({ch}, {cw}) uint8 device mask")
+    dev = pairs[0][0].device
+    paths = torch.empty((len(pairs), ch), dtype=torch.int32, device=dev)
+    costs = torch.empty((len(pairs),), dtype=torch.int64, device=dev)
+    o = SeamPathOpts(int(max_step), int(margin))
+    _chk(lib().stitch_dev_pairs_seam_path_u8(arr, len(pairs), int(cw), int(ch), _ptr_table(cov_a), _ptr_table(cov_b), (C.c_int32 * len(pairs))(*branches),
+                                             C.byref(o), _dp(paths), _dp(costs), _stream()))
+    return paths, costs
 
 
 def residual_best_shift(record, radius, zero_mean=False):

@@ -197,6 +197,10 @@ struct PlanShape {
     // level 0 (a, b AND the mask plane) is handed in by the caller (the coarse levels of a band-split pair): no seam scan, and so neither
     // the implicit mask nor source fusion (mask_opt and src_fuse are off), no G column or mask-row flags.  An input of plan_shape.
     bool planes_in = false;
+    // level 0 is composed from the pairs' frames (k_compose) and its mask plane is written from a path per pair (k_mask_path,
+    // include/stitch_seam_path.h): the stored-mask shape of planes_in, for up to `cap` pairs.  An input of plan_shape.
+    bool masked = false;
+    bool mask_stored() const { return planes_in || masked; }  // the level-0 mask is plane 6 in memory, never the seam's step
     // fused anticausal-x + causal-y wavefront sweep (k_vv_xbyf) for the first `wf_levels` levels
     int wf_levels = 0;
     // The causal x sweep of a wavefront level keeps only its state in front of every tile and the fused sweep re-runs it
@@ -231,10 +235,10 @@ struct StampRequest {  // STITCH_WAVEFRONT_STAMP is Tuning::stamp
 // One pair whose level 0 alone fills the chip: a throughput case like a batch.
 inline bool chip_filling(int h0) { return 7L * tiles(h0) >= CHIP_BANDS; }
 
-// Fills the shape of a cw x ch plan for `cap` pairs; planes_in: see PlanShape.  Returns pyramid_sizes' answer: the level count, or <= 0
+// Fills the shape of a cw x ch plan for `cap` pairs; planes_in, masked: see PlanShape.  Returns pyramid_sizes' answer: the level count, or <= 0
 // and an untouched shape.  The ONE writer of a shape: nothing sets a field of it afterwards.
 inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, int cap, const Tuning& tn, const StampRequest& st = StampRequest{},
-                      bool planes_in = false) {
+                      bool planes_in = false, bool masked = false) {
     int lw[32], lh[32];
     const int L = pyramid_sizes(cw, ch, o.level_rule, lw, lh);
     if (L <= 0) return L;
@@ -242,6 +246,8 @@ inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, 
     s.cw = cw, s.ch = ch, s.L = L, s.cap = cap, s.opts = o, s.tune = tn;
     s.no_fuse = tn.no_fuse != 0;
     s.planes_in = planes_in;
+    s.masked = masked;
+    const bool stored = s.mask_stored();
     s.blur_skip = o.blur_kind == 0 ? (o.sigma < 0.5f) : (o.sigma < 0.1f);
     for (int l = 0; l < L; ++l) {
         Level& v = s.lv[l];
@@ -279,7 +285,7 @@ inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, 
     // (a plan without fused-sweep levels keeps the hand-off buffers for k_vv_xby_m: one pair in flight, from STITCH_XBYM_MPIX megapixels per level)
     s.has_wf = wf > 0 || (o.blur_kind == 0 && !tn.no_fuse && o.sigma >= 0.5f && L >= 2);
     s.has_zt = wf > 0;
-    for (int i = 0; i < 2; ++i) s.has_gz[i] = s.has_mr[i] = wf > 0 && i + 1 < L && !planes_in;  // (reads_flags: planes handed in know no flags)
+    for (int i = 0; i < 2; ++i) s.has_gz[i] = s.has_mr[i] = wf > 0 && i + 1 < L && !stored;  // (reads_flags: a stored level-0 mask knows no flags)
     // opt-in: level 0 re-run from the frames measured 3 % slower, the plane levels within noise
     if (tn.recompute >= 0 && wf > 0) s.recompute = std::min(2, tn.recompute);
     s.zero_tiles = wf > 0 && !tn.no_zero_tiles;
@@ -288,7 +294,7 @@ inline int plan_shape(PlanShape& s, int cw, int ch, const stitch_blend_opts& o, 
     s.stamp_d7_level = st.d7_level;
     // implicit level-0 mask: needs both Van Vliet sweeps at level 0 (the x sweeps then run per-plane bands at any height;
     // STITCH_GATE64=1 restores the old restriction to heights that are multiples of 64 for A/B runs)
-    s.mask_opt = !planes_in && !s.no_fuse && o.blur_kind == 0 && !s.blur_skip && L >= 2 && lw[0] > 1 && lh[0] > 1 && !(tn.gate64 && lh[0] % 64);
+    s.mask_opt = !stored && !s.no_fuse && o.blur_kind == 0 && !s.blur_skip && L >= 2 && lw[0] > 1 && lh[0] > 1 && !(tn.gate64 && lh[0] % 64);
     if (tn.crows_l0 >= 0) s.crows_l0 = std::max(1, tn.crows_l0);
     if (tn.crows_ln >= 0) s.crows_ln = std::max(1, tn.crows_ln);
     if (tn.collapse4 >= 0) s.collapse4 = tn.collapse4 != 0;
@@ -502,7 +508,7 @@ inline bool produces_flags(const PlanShape& s, int l, const LevelForm& f) { retu
 // and k_blend_top (levels from l_end on), the band path and the coarse levels of a split pair (planes_in) do not know the flags.
 inline bool reads_flags(const PlanShape& s, int n, int l, const LevelForm& f) {
     const Level& b = s.lv[l];
-    if (l >= s.l_end() || s.planes_in || s.recompute != 0 || s.stamp_wf || !f.do_x) return false;
+    if (l >= s.l_end() || s.mask_stored() || s.recompute != 0 || s.stamp_wf || !f.do_x) return false;
     if (f.sweep != SW_BATCH && (f.sweep != SW_LONE || chain3(s, 7L * n * f.NR))) return false;
     return 7ull * s.cap * b.ps + 64ull * b.pitch < (1ull << 32);  // (in samples)
 }

@@ -34,6 +34,7 @@
 #include "stitch_rig_crop.h"
 #include "stitch_rig_formats.h"
 #include "stitch_rig_monitor.h"
+#include "stitch_seam_path.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -602,7 +603,7 @@ int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hi
         const MaskRowsArg mra{mrz.flags, mrz.NC, mrz.NR};
         if (l == 0) {  // level 0: the mask is the seam's step function itself (never read from memory)
             CollapseArgs<OUT, true> A{a.g, a.w, a.h, a.pitch, a.ps, nx.g, nx.e, nx.w, nx.h, nx.pitch, nx.ps, {a.ix, a.ax, a.iy, a.ay}, outs,
-                                      a.w, (size_t)a.w * a.h, p->planes_in ? nullptr : p->d_seam, pa, c.src ? 1 : 0, f.crows, f.xa, f.xb, 1,
+                                      a.w, (size_t)a.w * a.h, p->mask_stored() ? nullptr : p->d_seam, pa, c.src ? 1 : 0, f.crows, f.xa, f.xb, 1,
                                       c.c4_lock, c.c4_swizzle};
             A.gzn = gzn.flags, A.gncn = gzn.NC, A.zon = (unsigned)(7 * (size_t)p->cap * nx.ps);
             launch_collapse(A, CollapseKind{c.src && c.a_dense, f.gen, false, false, false}, cols, strips, n, mra, s);
@@ -626,9 +627,16 @@ int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hi
 }
 
 template <typename PX>
-int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const SeamInts* given) {
+int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const SeamInts* given, const PathArgs* paths) {
     const Level& a = p->lv[0];
-    if (given) {  // include/stitch_rig_seams.h: the records from the caller's integers instead of the scan
+    if (paths) {  // include/stitch_seam_path.h (a masked plan): no scan -- zeroed records that carry the branch, and the mask plane from the paths
+        {
+            StageTimer t(p, s, STITCH_K_SEAM, 0);
+            k_seam_pathed<<<1, 64, 0, s>>>(*paths, n, p->d_seam);
+        }
+        StageTimer t(p, s, STITCH_K_MASK, 0);
+        k_mask_path<<<grid_xy(a.pitch / 4, a.h, n), 256, 0, s>>>(a.g, a.w, a.pitch, a.ps, *paths);
+    } else if (given) {  // include/stitch_rig_seams.h: the records from the caller's integers instead of the scan
         StageTimer t(p, s, STITCH_K_SEAM, 0);
         k_seam_given<<<1, 64, 0, s>>>(*given, n, a.w, p->opts.seam_rule, p->d_seam);
     } else {
@@ -639,7 +647,7 @@ int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, 
         // work-item -- 6 of them instead of 24 at 6144 columns)
         k_seam<PX><<<n, n == 1 ? 1024 : 256, 0, s>>>(a.g, a.w, a.h, a.pitch, a.ps, p->opts.seam_rule, p->d_seam, pa, src ? 1 : 0);
     }
-    if (!p->mask_opt) {
+    if (!p->mask_opt && !paths) {
         StageTimer t(p, s, STITCH_K_MASK, 0);
         k_mask<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(a.g, a.w, a.pitch, a.ps, p->d_seam);
     }
@@ -665,8 +673,10 @@ bool same_index_key(const PairArgs<PX>& pa, int i, int j) {
 
 // The launch sequence of n pairs (or of one dense-canvas blend, pa.a_dense): S1, seam scan, REDUCE, collapse.
 // given: the pairs' seams as their four integers (stitch_dev_pairs_seamed_*), or nullptr for the scan.
+// paths: the pairs' seam paths and branches (stitch_dev_pairs_pathed_*, a masked plan: src is false), which replace scan and step mask.
 template <typename PX>
-int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, int n, hipStream_t s, bool src, const SeamInts* given = nullptr) {
+int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, int n, hipStream_t s, bool src, const SeamInts* given = nullptr,
+              const PathArgs* paths = nullptr) {
     const Level& a = p->lv[0];
     int rc;
     const CallForm c = call_form(*p, n, src, pa.a_dense != 0);  // every kernel choice of REDUCE and the collapse, before the first launch
@@ -714,7 +724,7 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
     p->last_idx = src && !pa.a_dense;
     p->last_runs = sr.cls != nullptr;
     for (int i = 0; i < MAXB; ++i) p->last_owner[i] = pa.idx_pr[i];
-    if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given))) return rc;
+    if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given, paths))) return rc;
     p->last_form = c;
     if ((rc = run_reduce<PX>(p, c, s, pa, zi, sr))) return rc;
     if ((rc = run_collapse<PX>(p, c, outs, s, pa))) return rc;
@@ -736,6 +746,7 @@ template <typename PX>
 int dev_blend(stitch_plan* p, const PX* d_a, const PX* d_b, PX* d_out, void* stream) {
     int rc = check_plan_call(p, d_a, d_b, d_out);
     if (rc) return rc;
+    if (p->masked) return fail(STITCH_ERR_ARG, "blend: a masked plan takes stitch_dev_pairs_pathed_* alone (include/stitch_seam_path.h)");
     PairArgs<PX> pa{};
     pa.frame[0] = d_a;
     pa.mosaic[0] = d_b;
@@ -766,17 +777,9 @@ int seam_check_sums(long long sum_a_x, long long n_a, long long sum_ov_x, long l
     return STITCH_OK;
 }
 
-// n independent pairs (n <= plan capacity) through one launch sequence: every kernel covers all n pairs.
-// seams (stitch_dev_pairs_seamed_*): n host records whose four integers replace the scan, checked here before anything is enqueued.
+// the n descriptors of a call as the kernels' argument and the outputs' addresses
 template <typename PX>
-int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, const stitch_seam* seams = nullptr) {
-    if (!p || !d) return fail(STITCH_ERR_ARG, "null plan or descriptor array");
-    if (n < 1 || n > p->cap) return fail(STITCH_ERR_ARG, "pairs: n=%d outside 1..%d (plan capacity)", n, p->cap);
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != p->device) return fail(STITCH_ERR_ARG, "plan belongs to device %d, current device is %d", p->device, dev);
-    PairArgs<PX> pa{};
-    OutPtrs<PX> outs{};
+int pair_args_of(const stitch_pair_desc* d, int n, PairArgs<PX>& pa, OutPtrs<PX>& outs) {
     for (int i = 0; i < n; ++i) {
         if (!d[i].frame || !d[i].mosaic || !d[i].out || d[i].fw <= 0 || d[i].fh <= 0 || d[i].mw <= 0 || d[i].mh <= 0)
             return fail(STITCH_ERR_ARG, "pairs: descriptor %d has a null buffer or a non-positive size", i);
@@ -796,6 +799,23 @@ int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, co
         pa.offx[i] = d[i].offx;
         pa.offy[i] = d[i].offy;
     }
+    return STITCH_OK;
+}
+
+// n independent pairs (n <= plan capacity) through one launch sequence: every kernel covers all n pairs.
+// seams (stitch_dev_pairs_seamed_*): n host records whose four integers replace the scan, checked here before anything is enqueued.
+template <typename PX>
+int dev_pairs(stitch_plan* p, const stitch_pair_desc* d, int n, void* stream, const stitch_seam* seams = nullptr) {
+    if (!p || !d) return fail(STITCH_ERR_ARG, "null plan or descriptor array");
+    if (n < 1 || n > p->cap) return fail(STITCH_ERR_ARG, "pairs: n=%d outside 1..%d (plan capacity)", n, p->cap);
+    if (p->masked) return fail(STITCH_ERR_ARG, "pairs: a masked plan takes stitch_dev_pairs_pathed_* alone (include/stitch_seam_path.h)");
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != p->device) return fail(STITCH_ERR_ARG, "plan belongs to device %d, current device is %d", p->device, dev);
+    PairArgs<PX> pa{};
+    OutPtrs<PX> outs{};
+    int rc_args = pair_args_of<PX>(d, n, pa, outs);
+    if (rc_args) return rc_args;
     // one index plane per distinct key of the call: a pair's owner is the first pair with the same key
     int owner[MAXB];
     for (int i = 0; i < n; ++i) {
@@ -1549,7 +1569,7 @@ int stitch_dev_move_f32(const float* d_src, int sw, int sh, int ox, int oy, floa
     return dev_move(d_src, sw, sh, ox, oy, d_canvas, cw, ch, stream);
 }
 
-static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out);
+static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out, bool masked = false);
 int stitch_plan_create(int cw, int ch, const stitch_blend_opts* opts, stitch_plan** plan_out) {
     return stitch_plan_create_batched(cw, ch, opts, 1, plan_out);
 }
@@ -1559,8 +1579,8 @@ int stitch_plan_create_batched(int cw, int ch, const stitch_blend_opts* opts, in
 }
 
 // Fill the shape (plan_shape, stitch_call_form.h), carve one arena for it, upload the resize tables.  planes_in: the coarse levels of a
-// band-split pair (stitch_band_create).
-static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out) {
+// band-split pair (stitch_band_create); masked: include/stitch_seam_path.h.
+static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pairs, bool planes_in, stitch_plan** plan_out, bool masked) {
     if (!plan_out) return fail(STITCH_ERR_ARG, "plan_create: null plan_out");
     if (max_pairs < 1 || max_pairs > MAXB) return fail(STITCH_ERR_ARG, "plan_create: max_pairs must be 1..%d", MAXB);
     *plan_out = nullptr;
@@ -1581,7 +1601,7 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     stamps.xy = std::getenv("STITCH_XBYM_STAMP") != nullptr;
     stamps.co = std::getenv("STITCH_COARSE_STAMP") != nullptr;
     if (std::getenv("STITCH_D7_STAMP")) stamps.d7_level = atoi(std::getenv("STITCH_D7_STAMP"));
-    plan_shape(*p, cw, ch, o, max_pairs, tn, stamps, planes_in);
+    plan_shape(*p, cw, ch, o, max_pairs, tn, stamps, planes_in, masked);
     const size_t B = (size_t)max_pairs;
     p->vvk = make_vvk(o.sigma);
     p->drk = make_drk(o.sigma);
@@ -2575,3 +2595,5 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_rig_crop.inc"
 #include "stitch_rig_formats.inc"
 #include "stitch_rig_monitor.inc"
+#include "stitch_seam_path.inc"
+#include "stitch_rig_seam_paths.inc"

@@ -56,8 +56,26 @@ struct stitch_rig {
     unsigned long long* mon_rec = nullptr;   // the records of the sequence in flight: max_sets sets, set-major then step
     std::vector<uint64_t> mon_last;          // the records of the last monitored replay, and whose they are
     int mon_last_sets = 0, mon_last_radius = -1;
+    // ---- path seams (include/stitch_seam_path.h; stitch_rig_seam_paths.inc) ----
+    int sp_mode = 0;                          // 0: none, the replay as it is; 1: every set finds its own paths; 2: fixed paths
+    stitch_seam_path_opts sp_opts{2, 8};
+    std::vector<size_t> sp_row_at;            // per step: where its ch rows start among a set's rows; sp_rows: the rows of a set
+    size_t sp_rows = 0;
+    std::vector<int32_t> sp_fixed;            // mode 2: sp_rows columns, step after step
+    bool sp_fixed_up = false;                 // ... and whether sp_fixed_dev holds them
+    std::vector<stitch_plan*> sp_plans;       // the masked twins of `plans`, from the first replay with paths on
+    int32_t* sp_fixed_dev = nullptr;          // sp_rows columns
+    int32_t* sp_paths = nullptr;              // mode 1: the paths of the sequence in flight, max_sets sets of sp_rows columns
+    unsigned long long* sp_costs = nullptr;   // ... and their costs, max_sets sets of one word per step
+    void* sp_scratch = nullptr;               // ... and the finder's costs and predecessors of one step, sized for the largest
+    std::vector<int32_t> sp_last;             // the paths of the last replay with paths, set-major, and their costs
+    std::vector<uint64_t> sp_last_cost;
+    int sp_last_sets = 0;
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
+        for (stitch_plan* p : sp_plans) stitch_plan_destroy(p);  // waits for the plan's last call
+        for (void* p : {(void*)sp_fixed_dev, (void*)sp_paths, (void*)sp_costs, sp_scratch})
+            if (p) (void)hipFree(p);
         if (crop_full) (void)hipFree(crop_full);
         if (fmt_out) (void)hipFree(fmt_out);
         for (uint8_t* p : fmt_in)
@@ -113,6 +131,13 @@ int rig_mon_prepare(stitch_rig* R, hipStream_t s);
 int rig_mon_begin(stitch_rig* R, int m, hipStream_t s);
 int rig_mon_step(stitch_rig* R, const stitch_pair_desc* pd, int k, int m, hipStream_t s);
 int rig_mon_collect(stitch_rig* R, uint64_t* host, int m, hipStream_t s);
+
+// Path seams of a rig that has a mode (stitch_rig_seam_paths.inc): the masked plans, the coverage planes and the path buffers; step k's
+// blend over the m sets in flight -- behind the finder in mode 1 -- from the step's pair descriptors; the copy of a sequence's paths
+// and costs to the host.
+int rig_sp_prepare(stitch_rig* R, hipStream_t s);
+int rig_sp_step(stitch_rig* R, const stitch_pair_desc* pd, int k, int m, hipStream_t s);
+int rig_sp_collect(stitch_rig* R, int32_t* h_paths, uint64_t* h_costs, int m, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -242,8 +267,12 @@ struct RigOutcome {
     int hip_fault = STITCH_OK;
     std::string hip_text;
     std::vector<int> fail_step;  // per set: the first step whose seam scan failed, or n_steps
+    // a replay along paths (include/stitch_seam_path.h): the steps ran on the masked plans, and the records are the geometric ones
+    const std::vector<stitch_plan*>* plans;
+    bool pathed;
     RigOutcome(stitch_rig* r, int n_sets, int32_t* st, stitch_seam* sm)
-        : R(r), set_status(st), seams(sm), n_steps((int)r->steps.size()), pending_step(r->plans.size(), -1), fail_step((size_t)n_sets, (int)r->steps.size()) {}
+        : R(r), set_status(st), seams(sm), n_steps((int)r->steps.size()), pending_step(r->plans.size(), -1), fail_step((size_t)n_sets, (int)r->steps.size()),
+          plans(r->sp_mode ? &r->sp_plans : &r->plans), pathed(r->sp_mode != 0) {}
     // waits for the plan's last call
     void read(int pi) {
         const int k = pending_step[pi];
@@ -252,14 +281,15 @@ struct RigOutcome {
         for (int i = 0; i < m; ++i) {
             stitch_seam sm;
             std::memset(&sm, 0, sizeof sm);
-            const int rc = stitch_plan_status_at(R->plans[pi], i, &sm);
+            const int rc = stitch_plan_status_at((*plans)[pi], i, &sm);
+            if (pathed) seam_to_public(R->cover_seams[k], &sm);
             const int set = set0 + i;
             if (rc == STITCH_ERR_HIP) {  // a sticky hand-off time-out (or a failed wait): nothing of this call counts
                 if (!hip_fault) {
                     hip_fault = rc;
                     hip_text = g_err;
                 }
-                (void)stitch_plan_clear_fault(R->plans[pi]);
+                (void)stitch_plan_clear_fault((*plans)[pi]);
                 return;
             }
             if (seams) seams[(size_t)set * n_steps + k] = sm;
@@ -275,7 +305,7 @@ struct RigOutcome {
     // every return path: no plan keeps an unread call or an unacknowledged fault behind
     ~RigOutcome() {
         for (size_t pi = 0; pi < pending_step.size(); ++pi)
-            if (pending_step[pi] >= 0 && stitch_plan_status_at(R->plans[pi], 0, nullptr) == STITCH_ERR_HIP) (void)stitch_plan_clear_fault(R->plans[pi]);
+            if (pending_step[pi] >= 0 && stitch_plan_status_at((*plans)[pi], 0, nullptr) == STITCH_ERR_HIP) (void)stitch_plan_clear_fault((*plans)[pi]);
     }
 };
 
@@ -442,6 +472,16 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     if (monitored && (rc = rig_mon_prepare(R, s))) return rc;
     const size_t mon_words = monitored ? (size_t)(2 + 3 * (2 * R->mon_radius + 1) * (2 * R->mon_radius + 1)) * ns : 0;  // per set
     std::vector<uint64_t> h_mon(mon_words * n_sets);  // written by the records' copies: waited for like h_stats
+    // include/stitch_seam_path.h: likewise, a failed call leaves no paths behind
+    const bool pathed = R->sp_mode != 0 && ns > 0;
+    if (R->sp_mode) {
+        R->sp_last.clear();
+        R->sp_last_cost.clear();
+        R->sp_last_sets = 0;
+    }
+    if (pathed && (rc = rig_sp_prepare(R, s))) return rc;
+    std::vector<int32_t> h_paths(pathed ? R->sp_rows * n_sets : 0);
+    std::vector<uint64_t> h_pcost(pathed ? (size_t)ns * n_sets : 0);
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
 
     // ---- the pointer tables of the whole call, uploaded once: per sequence one slice per projected frame, then the outputs ----
@@ -543,7 +583,9 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             // include/stitch_rig_exposure.h: frame f of the m sets takes its template's colour statistics, in place
             if (ex_bytes && (rc = rig_ex_transfer(R, d_up + ex_at, k, m, s))) return rc;
             if (monitored && (rc = rig_mon_step(R, pd.data(), k, m, s))) return rc;  // the blend's own inputs, before it runs
-            if (!R->fixed.empty()) {  // include/stitch_rig_seams.h: the step's fixed record for each of the m sets
+            if (pathed) {  // include/stitch_seam_path.h: the blend along each set's own path, or along the step's fixed one
+                if ((rc = rig_sp_step(R, pd.data(), k, m, s))) return rc;
+            } else if (!R->fixed.empty()) {  // include/stitch_rig_seams.h: the step's fixed record for each of the m sets
                 const std::vector<stitch_seam> given((size_t)m, R->fixed[k]);
                 if ((rc = stitch_dev_pairs_seamed_u8(R->plans[pi], pd.data(), m, given.data(), s))) return rc;
             } else if ((rc = stitch_dev_pairs_u8(R->plans[pi], pd.data(), m, s)))
@@ -573,6 +615,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         if (!h_stats.empty())
             HIPCHK(hipMemcpyAsync(h_stats.data() + (size_t)16 * ns * set0, R->ex_stats, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
         if (monitored && (rc = rig_mon_collect(R, h_mon.data() + mon_words * set0, m, s))) return rc;  // likewise
+        if (pathed && (rc = rig_sp_collect(R, h_paths.data() + R->sp_rows * set0, h_pcost.data() + (size_t)ns * set0, m, s))) return rc;
         O.read_all();  // the next sequence uses the same workspaces
         if (O.hip_fault) break;
         set0 += m;
@@ -587,6 +630,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         R->mon_last.swap(h_mon);
         R->mon_last_sets = n_sets;
         R->mon_last_radius = R->mon_radius;
+    }
+    if (R->sp_mode) {
+        R->sp_last.swap(h_paths);
+        R->sp_last_cost.swap(h_pcost);
+        R->sp_last_sets = n_sets;
     }
     for (int i = 0; i < n_sets; ++i)
         if (set_status[i] != STITCH_OK)

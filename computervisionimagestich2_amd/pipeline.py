@@ -127,7 +127,7 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
 
 
 def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None,
-                 residuals=None):
+                 residuals=None, seam_paths=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -149,16 +149,23 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     measures every step's record by capi.dev_pairs_residual on the exact inputs of its blend -- after the transfer, where exposure
     is set -- and returns (mosaic, records), records an (n_steps, words) int64 device tensor: the single-set statement of a rig
     with a monitor.  With residuals=None the return value and every byte stay as they are.
+    seam_paths: dict(coverage=[(cov_a, cov_b) per step: (ch, cw) uint8 device masks], branches=[0 or 1 per step], max_step=2,
+    margin=8, paths=None) (include/stitch_seam_path.h): every step finds its least-cost seam path by capi.dev_pairs_seam_path on
+    the exact inputs of its blend -- after the transfer, where exposure is set -- and blends along it on a masked plan; with
+    paths=[one int32 sequence of ch columns per step] nothing is found and the step blends along the given path.  The return value
+    grows by `found`, a list of (path, cost) per step (an int32 device tensor; the cost is None for a given path): (mosaic, found),
+    or (mosaic, records, found) with residuals -- the single-set statement of a rig with path seams.  With seam_paths=None the
+    return value and every byte stay as they are.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     if formats is not None:
         in_fmt, out_fmt, matrix = formats
         if in_fmt != capi.PIX_PLANAR:
             used_frames = {steps[0]["start"]} | {st["src"] for st in steps}  # the rig reads no other frame either
             frames = [capi.dev_unpack_many([f], matrix)[0] if i in used_frames else None for i, f in enumerate(frames)]
-        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop, residuals=residuals)
-        result, records = result if residuals is not None else (result, None)
+        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop, residuals=residuals, seam_paths=seam_paths)
+        result, *extras = result if isinstance(result, tuple) else (result,)
         result = result if out_fmt == capi.PIX_PLANAR else capi.dev_pack_many([result], out_fmt, matrix)[0]
-        return result if residuals is None else (result, records)
+        return (result, *extras) if extras else result
     proj = {}
 
     def projected(i):
@@ -172,13 +179,20 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             raise ValueError("one seam per step")
     if residuals is not None and len(residuals["domains"]) != len(steps):
         raise ValueError("one residual domain per step")
+    if seam_paths is not None:
+        if seams is not None:
+            raise ValueError("seam_paths and seams exclude each other")
+        if len(seam_paths["coverage"]) != len(steps) or len(seam_paths["branches"]) != len(steps):
+            raise ValueError("one pair of coverage masks and one branch per step")
+        if seam_paths.get("paths") is not None and len(seam_paths["paths"]) != len(steps):
+            raise ValueError("one path per step")
     result = projected(steps[0]["start"])
-    used, records = [], []
+    used, records, found = [], [], []
     for k, st in enumerate(steps):
-        key = (st["cw"], st["ch"])
+        key = (st["cw"], st["ch"]) if seam_paths is None else (st["cw"], st["ch"], "masked")
         plan = plans.get(key) if plans is not None else None
         if plan is None:
-            plan = capi.Plan(st["cw"], st["ch"], opts)
+            plan = capi.Plan(st["cw"], st["ch"], opts, masked=seam_paths is not None)
             if plans is not None:
                 plans[key] = plan
         elif plan in used:  # the same workspace twice in one chain: its seam record must be read before it is overwritten
@@ -188,7 +202,23 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         if residuals is not None:
             records.append(capi.dev_pairs_residual([(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])], st["cw"], st["ch"],
                                                    [residuals["domains"][k]], residuals["radius"])[0])
-        result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"], seam=None if seams is None else seams[k])
+        if seam_paths is not None:
+            import torch
+            inputs = (projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])
+            branch = int(seam_paths["branches"][k])
+            if seam_paths.get("paths") is not None:
+                given = seam_paths["paths"][k]
+                path, cost = torch.as_tensor(given.cpu().numpy() if hasattr(given, "cpu") else given, dtype=torch.int32).to(result.device).contiguous(), None
+            else:
+                cov_a, cov_b = seam_paths["coverage"][k]
+                paths, costs = capi.dev_pairs_seam_path([inputs], st["cw"], st["ch"], [cov_a], [cov_b], [branch], seam_paths.get("max_step", 2),
+                                                        seam_paths.get("margin", 8))
+                path, cost = paths[0], int(costs[0])
+            found.append((path, cost))
+            out = torch.empty((3, st["ch"], st["cw"]), dtype=result.dtype, device=result.device)
+            result = plan.pairs([inputs + (out,)], paths=[path], branches=[branch])[0]
+        else:
+            result = plan.pair(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"], seam=None if seams is None else seams[k])
         used.append(plan)
     if crop is not None:
         (x0, y0, w, h), mode = crop
@@ -211,10 +241,12 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         if plans is None:
             for plan in used:
                 plan.close()
+    extras = () if seam_paths is None else (found,)
     if residuals is not None:
         import torch
-        return result, (torch.stack(records) if records else torch.empty((0, capi.residual_words(residuals["radius"])), dtype=torch.int64, device=result.device))
-    return result
+        return (result, (torch.stack(records) if records else torch.empty((0, capi.residual_words(residuals["radius"])), dtype=torch.int64, device=result.device)),
+                *extras)
+    return (result, *extras) if extras else result
 
 
 def close_plans(plans):
