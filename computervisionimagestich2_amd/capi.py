@@ -208,6 +208,15 @@ SEAM_PATH_SIGNATURES = _signatures(
     ("stitch_rig_seam_paths", i32, vp, vp, vp), ("stitch_rig_last_seam_paths", i32, vp, i32, i32, vp, i32, vp),
 )
 
+# The same for include/stitch_seam_anchor.h, temporally anchored path seams; tests/test_seam_anchor_host.py holds it to that header.
+# (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks them.)
+SEAM_ANCHOR_SIGNATURES = _signatures(
+    ("stitch_dev_pairs_seam_path_anchored_u8", i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    ("stitch_rig_set_seam_anchor", i32, vp, vp), ("stitch_rig_prime_seam_anchor", i32, vp, vp, i32),
+    ("stitch_rig_reset_seam_anchor stitch_rig_clear_seam_anchor", i32, vp), ("stitch_rig_seam_anchor", i32, vp, vp, vp),
+    ("stitch_rig_last_seam_moved", i32, vp, i32, i32, vp),
+)
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -253,9 +262,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h, stitch_seam_path.h (likewise)
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
-                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()):
+                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1899,6 +1908,47 @@ class Rig(_Handle):
         _chk(lib().stitch_rig_last_seam_paths(self._h, int(set), int(step), _p(out), ch, C.byref(cost)))
         return out, cost.value
 
+    def set_seam_anchor(self, weight, cap, policy="set"):
+        """stitch_rig_set_seam_anchor (include/stitch_seam_anchor.h): while found paths are set (set_seam_paths) every path also pays
+        weight * min(|s - r|, cap) per row for leaving the anchor r -- policy "set": the previous set's path, across sequences and
+        calls; "call": the path of the previous call's last set.  weight >= 0, cap >= 1, weight * cap <= 2055.  Returns self."""
+        pol = {"set": SEAM_ANCHOR_PER_SET, "call": SEAM_ANCHOR_PER_CALL}.get(policy, policy)
+        _chk(lib().stitch_rig_set_seam_anchor(self._h, C.byref(SeamAnchorOpts(int(weight), int(cap), int(pol)))))
+        return self
+
+    def prime_seam_anchor(self, paths):
+        """stitch_rig_prime_seam_anchor: one path per step -- the step's ch columns, any integers -- becomes the anchor.  Returns self."""
+        rows = [np.ascontiguousarray(np.asarray(p.cpu() if hasattr(p, "cpu") else p).astype(np.int32).reshape(-1)) for p in paths]
+        for k, r in enumerate(rows[:self.n_steps]):
+            cw, ch = C.c_int(), C.c_int()
+            _chk(lib().stitch_rig_step_canvas(self._h, k, C.byref(cw), C.byref(ch)))
+            if r.size != ch.value:
+                raise ValueError(f"the anchor of step {k} has {ch.value} rows, got {r.size}")
+        _chk(lib().stitch_rig_prime_seam_anchor(self._h, (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows]), len(rows)))
+        return self
+
+    def reset_seam_anchor(self):
+        """stitch_rig_reset_seam_anchor: forget the anchor, keep the options -- a scene cut.  Returns self."""
+        _chk(lib().stitch_rig_reset_seam_anchor(self._h))
+        return self
+
+    def clear_seam_anchor(self):
+        """stitch_rig_clear_seam_anchor: forget the anchor and the options.  Returns self."""
+        _chk(lib().stitch_rig_clear_seam_anchor(self._h))
+        return self
+
+    def seam_anchor(self):
+        """stitch_rig_seam_anchor: (options, has_anchor) -- options None where none are set, else (weight, cap, "set" | "call")."""
+        o, has = SeamAnchorOpts(), C.c_int()
+        _chk(lib().stitch_rig_seam_anchor(self._h, C.byref(o), C.byref(has)))
+        return (None if o.policy == 0 else (o.weight, o.cap, "set" if o.policy == SEAM_ANCHOR_PER_SET else "call")), bool(has.value)
+
+    def last_seam_moved(self, set=0, step=0):
+        """stitch_rig_last_seam_moved (host only): `moved` of `set` at `step` in the last stitch() along paths."""
+        moved = C.c_uint64()
+        _chk(lib().stitch_rig_last_seam_moved(self._h, int(set), int(step), C.byref(moved)))
+        return moved.value
+
     def _stitch_fmt(self, sets, out, return_stats):
         """stitch() of a rig with a format set: stitch_dev_rig_stitch_fmt_u8."""
         in_fmt, out_fmt, _ = self.formats
@@ -2105,11 +2155,22 @@ class SeamPathOpts(C.Structure):
         super().__init__(max_step, margin)
 
 
-def dev_pairs_seam_path(pairs, cw, ch, cov_a, cov_b, branches, max_step=2, margin=8):
+# ---- temporally anchored path seams: include/stitch_seam_anchor.h ---------------------------------------------------------------
+SEAM_ANCHOR_MAX, SEAM_ANCHOR_PER_SET, SEAM_ANCHOR_PER_CALL = 2055, 1, 2
+
+
+class SeamAnchorOpts(C.Structure):
+    """stitch_seam_anchor_opts: the weight w and the cap T of the temporal term w * min(|s - r|, T), and a rig's policy.  No defaults."""
+    _fields_ = [("weight", C.c_int32), ("cap", C.c_int32), ("policy", C.c_int32)]
+
+
+def dev_pairs_seam_path(pairs, cw, ch, cov_a, cov_b, branches, max_step=2, margin=8, anchors=None, weight=None, cap=None):
     """stitch_dev_pairs_seam_path_u8 on torch's current stream, which it waits for.  pairs: (frame, p, offx, offy, mosaic, ox, oy)
     with (3, H, W) uint8 device tensors -- the inputs of a blend; cov_a, cov_b: per pair a (ch, cw) uint8 device mask of where the
     warped frame / the moved mosaic can have data (non-zero = covered; tensors may serve several pairs); branches: per pair 0 or 1.
-    Returns (paths, costs): an (n, ch) int32 and an (n,) int64 device tensor -- the least-cost seam column of every row, and its cost."""
+    Returns (paths, costs): an (n, ch) int32 and an (n,) int64 device tensor -- the least-cost seam column of every row, and its cost.
+    anchors (with weight and cap): stitch_dev_pairs_seam_path_anchored_u8 (include/stitch_seam_anchor.h) -- per pair a (ch,) int32
+    device tensor or None (that pair is unanchored); returns (paths, costs, moved), moved an (n,) int64 device tensor."""
     import torch
     pairs, cov_a, cov_b, branches = list(pairs), list(cov_a), list(cov_b), [int(b) for b in branches]
     if not pairs or not len(cov_a) == len(cov_b) == len(branches) == len(pairs):
@@ -2132,6 +2193,18 @@ def dev_pairs_seam_path(pairs, cw, ch, cov_a, cov_b, branches, max_step=2, margi
     paths = torch.empty((len(pairs), ch), dtype=torch.int32, device=dev)
     costs = torch.empty((len(pairs),), dtype=torch.int64, device=dev)
     o = SeamPathOpts(int(max_step), int(margin))
+    if anchors is not None:
+        anchors = list(anchors)
+        if weight is None or cap is None or len(anchors) != len(pairs):
+            raise ValueError("anchors come with a weight and a cap, one entry (a tensor or None) per pair")
+        for a in anchors:
+            if a is not None and (not a.is_cuda or not a.is_contiguous() or a.dtype != torch.int32 or a.numel() != ch):
+                raise ValueError(f"every anchor is a contiguous ({ch},) int32 device tensor, or None")
+        moved = torch.empty((len(pairs),), dtype=torch.int64, device=dev)
+        tab = (C.c_void_p * len(pairs))(*[None if a is None else a.data_ptr() for a in anchors])
+        _chk(lib().stitch_dev_pairs_seam_path_anchored_u8(arr, len(pairs), int(cw), int(ch), _ptr_table(cov_a), _ptr_table(cov_b), (C.c_int32 * len(pairs))(*branches),
+                                                          C.byref(o), tab, C.byref(SeamAnchorOpts(int(weight), int(cap), 0)), _dp(paths), _dp(costs), _dp(moved), _stream()))
+        return paths, costs, moved
     _chk(lib().stitch_dev_pairs_seam_path_u8(arr, len(pairs), int(cw), int(ch), _ptr_table(cov_a), _ptr_table(cov_b), (C.c_int32 * len(pairs))(*branches),
                                              C.byref(o), _dp(paths), _dp(costs), _stream()))
     return paths, costs

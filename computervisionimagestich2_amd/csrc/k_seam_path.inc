@@ -180,14 +180,46 @@ __global__ __launch_bounds__(SP_CT) void k_seam_path_cost_step(SeamPathArgs a, i
     seam_path_cost<false>(a.p[blockIdx.y], cw, ch, wpr, margin, cost, lds);
 }
 
+// The temporal term of an anchored finder (include/stitch_seam_anchor.h): c_t(y, s) = c(y, s) + weight * min(|s - r[y]|, cap).
+struct SeamAnchor {
+    const int32_t* const* tab;  // a device table of one anchor per pair (a null entry: that pair is unanchored); or, where tab is null,
+    const int32_t* base;        // ... pair i anchors on base + i * stride (null: no pair is anchored)
+    size_t stride;
+    unsigned weight, cap;
+    unsigned long long* moved;  // pair i's `moved` goes to moved[i * moved_stride]
+    size_t moved_stride;
+};
+// An anchor's columns as the global memory they are: a pointer that was read from a table is a flat one to the compiler, and a flat load
+// waits for every LDS and memory operation in flight -- the next row's costs among them.
+typedef const int32_t __attribute__((address_space(1))) * SpAnchorCols;
+// r[y] folded into [-cap, cw + cap], once per row (it is uniform over the workgroup): min(|s - r|, cap) is the same for every
+// s in 0 .. cw, whatever 32-bit value r has, and the per-state term stays in 32 bits.
+__device__ __forceinline__ int sp_anchor_fold(int r, int cw, unsigned cap) {
+    const long long lo = -(long long)cap, hi = (long long)cw + (long long)cap, v = r;  // (cap <= INT32_MAX: lo fits an int; where hi does not, no v exceeds it)
+    return (int)(v < lo ? lo : v > hi ? hi : v);
+}
+// weight * min(|s - folded|, cap): the distance is below 2^32 (s <= 8192, folded >= -INT32_MAX), so unsigned arithmetic states it
+__device__ __forceinline__ unsigned sp_anchor_term(int s, int folded, unsigned weight, unsigned cap) {
+    const unsigned d = s >= folded ? (unsigned)s - (unsigned)folded : (unsigned)folded - (unsigned)s;
+    return weight * min(d, cap);
+}
+
 // One workgroup per pair walks the rows.  The states D(y, .) of two rows live in LDS (dynamic: 2 * (cw + 1) 64-bit words); work-item
 // t owns the states s = t, t + SP_DT, ...  Per row: the minimum of the previous row over [s - K, s + K], candidates taken in the
 // order t = s, s - 1, s + 1, s - 2, ... under a strict comparison -- ties to the smallest |t - s|, then to the smaller t -- one
 // byte t - s + K per state, one barrier (the row written is the one read two rows ago).  The next row's costs are loaded before
 // the minimum of this one.  Then the least final state (ties to the smallest s: a 64-bit minimum over D * 2^14 + s) and the walk
 // back along the bytes, by work-item 0.  Pair i's path goes to paths + i * path_stride, its cost to costs[i * cost_stride].
+// With one more argument, a SeamAnchor, the anchored form: every row's cost takes the pair's temporal term, its anchor column loaded
+// a row ahead like the costs, and work-item 0 sums `moved` along the walk back; a pair without an anchor runs with weight 0.  With
+// no such argument the kernel is the finder as it was, instruction for instruction.
+__device__ __forceinline__ SeamAnchor sp_anchor_of() { return SeamAnchor{}; }
+__device__ __forceinline__ const SeamAnchor& sp_anchor_of(const SeamAnchor& a) { return a; }
+template <typename... AN>
 __global__ __launch_bounds__(SP_DT) void k_seam_path_dp(const unsigned* __restrict__ cost, int cw, int ch, int K, uint8_t* pred, int32_t* __restrict__ paths,
-                                                        size_t path_stride, unsigned long long* __restrict__ costs, size_t cost_stride) {
+                                                        size_t path_stride, unsigned long long* __restrict__ costs, size_t cost_stride, AN... anchor) {
+    constexpr bool ANCH = sizeof...(AN) != 0;
+    const SeamAnchor an = sp_anchor_of(anchor...);
     extern __shared__ unsigned long long sp_state[];
     __shared__ unsigned long long best;
     const int t = threadIdx.x, ns = cw + 1;
@@ -195,11 +227,25 @@ __global__ __launch_bounds__(SP_DT) void k_seam_path_dp(const unsigned* __restri
     const unsigned* c = cost + pair * ch * (size_t)ns;
     uint8_t* pr = pred + pair * ch * (size_t)ns;
     unsigned long long *prev = sp_state, *cur = sp_state + ns;
+    SpAnchorCols r = nullptr;
+    unsigned aw = 0;
+    int r0 = 0, rn = 0;  // rn: the next row's column as loaded, folded where the row uses it
+    if constexpr (ANCH) {
+        r = (SpAnchorCols)(an.tab ? an.tab[pair] : an.base ? an.base + pair * an.stride : nullptr);
+        aw = r ? an.weight : 0;
+        r0 = r ? sp_anchor_fold(r[0], cw, an.cap) : 0;
+        rn = r && ch > 1 ? r[1] : 0;
+    }
     unsigned cn[SP_DPER];
 #pragma unroll
     for (int i = 0; i < SP_DPER; ++i) {
         const int s = t + i * SP_DT;
-        if (s < ns) prev[s] = c[s];
+        if (s < ns) {
+            if constexpr (ANCH)
+                prev[s] = c[s] + sp_anchor_term(s, r0, aw, an.cap);
+            else
+                prev[s] = c[s];
+        }
         cn[i] = s < ns && ch > 1 ? c[(size_t)ns + s] : 0;
     }
     if (t == 0) best = ~0ull;
@@ -212,6 +258,8 @@ __global__ __launch_bounds__(SP_DT) void k_seam_path_dp(const unsigned* __restri
             cy[i] = cn[i];
             cn[i] = s < ns && y + 1 < ch ? c[(size_t)(y + 1) * ns + s] : 0;
         }
+        const int ry = rn;
+        if constexpr (ANCH) rn = r && y + 1 < ch ? r[y + 1] : 0;
 #pragma unroll
         for (int i = 0; i < SP_DPER; ++i) {
             const int s = t + i * SP_DT;
@@ -228,7 +276,10 @@ __global__ __launch_bounds__(SP_DT) void k_seam_path_dp(const unsigned* __restri
                         if (v < m) m = v, at = k;
                     }
                 }
-                cur[s] = m + cy[i];
+                if constexpr (ANCH)
+                    cur[s] = m + cy[i] + sp_anchor_term(s, sp_anchor_fold(ry, cw, an.cap), aw, an.cap);
+                else
+                    cur[s] = m + cy[i];
                 pr[(size_t)y * ns + s] = (uint8_t)(at + K);
             }
         }
@@ -250,6 +301,23 @@ __global__ __launch_bounds__(SP_DT) void k_seam_path_dp(const unsigned* __restri
         costs[pair * cost_stride] = best >> 14;
         int32_t* path = paths + pair * path_stride;
         path[ch - 1] = s;
+        if constexpr (ANCH) {
+            if (r) {  // the row above's anchor column is loaded beside the byte that leads there: one wait per row, as without
+                unsigned long long mv = 0;
+                int ra = r[ch - 1];
+                for (int y = ch - 1; y >= 1; --y) {
+                    const int rb = r[y - 1];
+                    const int up = (int)pr[(size_t)y * ns + s] - K;
+                    mv += sp_anchor_term(s, sp_anchor_fold(ra, cw, an.cap), 1, an.cap);
+                    s += up;
+                    path[y - 1] = s;
+                    ra = rb;
+                }
+                an.moved[pair * an.moved_stride] = mv + sp_anchor_term(s, sp_anchor_fold(ra, cw, an.cap), 1, an.cap);
+                return;
+            }
+            an.moved[pair * an.moved_stride] = 0;
+        }
         for (int y = ch - 1; y >= 1; --y) {
             s += (int)pr[(size_t)y * ns + s] - K;
             path[y - 1] = s;

@@ -35,6 +35,7 @@
 #include "stitch_rig_formats.h"
 #include "stitch_rig_monitor.h"
 #include "stitch_seam_path.h"
+#include "stitch_seam_anchor.h"
 #include "stitch_kernels.hpp"
 
 #pragma clang fp contract(off)

@@ -71,10 +71,19 @@ struct stitch_rig {
     std::vector<int32_t> sp_last;             // the paths of the last replay with paths, set-major, and their costs
     std::vector<uint64_t> sp_last_cost;
     int sp_last_sets = 0;
+    // ---- anchored path seams (include/stitch_seam_anchor.h; stitch_rig_seam_paths.inc): at work while sp_mode == 1 and a policy is set ----
+    stitch_seam_anchor_opts sa_opts{0, 0, 0};  // policy 0: no options set
+    bool sa_has = false;                      // the rig has an anchor: sa_dev holds it, or sa_prime does until the next replay takes it up
+    bool sa_live = false;                     // ... during a replay: sa_dev holds the anchor of the next set to anchor on it
+    std::vector<int32_t> sa_prime;            // a primed anchor not yet on the device: sp_rows columns (empty: none is waiting)
+    int32_t* sa_dev = nullptr;                // the anchor: sp_rows columns, step after step
+    unsigned long long* sa_moved = nullptr;   // `moved` of the sequence in flight, max_sets sets of one word per step
+    std::vector<uint64_t> sa_last_moved;      // ... and of the last replay with paths, beside sp_last_cost
+    bool sa_active() const { return sp_mode == 1 && sa_opts.policy != 0; }
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
         for (stitch_plan* p : sp_plans) stitch_plan_destroy(p);  // waits for the plan's last call
-        for (void* p : {(void*)sp_fixed_dev, (void*)sp_paths, (void*)sp_costs, sp_scratch})
+        for (void* p : {(void*)sp_fixed_dev, (void*)sp_paths, (void*)sp_costs, sp_scratch, (void*)sa_dev, (void*)sa_moved})
             if (p) (void)hipFree(p);
         if (crop_full) (void)hipFree(crop_full);
         if (fmt_out) (void)hipFree(fmt_out);
@@ -137,7 +146,7 @@ int rig_mon_collect(stitch_rig* R, uint64_t* host, int m, hipStream_t s);
 // and costs to the host.
 int rig_sp_prepare(stitch_rig* R, hipStream_t s);
 int rig_sp_step(stitch_rig* R, const stitch_pair_desc* pd, int k, int m, hipStream_t s);
-int rig_sp_collect(stitch_rig* R, int32_t* h_paths, uint64_t* h_costs, int m, hipStream_t s);
+int rig_sp_collect(stitch_rig* R, int32_t* h_paths, uint64_t* h_costs, uint64_t* h_moved, int m, bool last, hipStream_t s);
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
@@ -478,10 +487,17 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         R->sp_last.clear();
         R->sp_last_cost.clear();
         R->sp_last_sets = 0;
+        R->sa_last_moved.clear();
+    }
+    // include/stitch_seam_anchor.h: the anchor is the replay's from here on, and the rig's again once the replay has completed
+    const bool anchored = pathed && R->sa_active();
+    if (anchored) {
+        R->sa_live = R->sa_has;
+        R->sa_has = false;
     }
     if (pathed && (rc = rig_sp_prepare(R, s))) return rc;
     std::vector<int32_t> h_paths(pathed ? R->sp_rows * n_sets : 0);
-    std::vector<uint64_t> h_pcost(pathed ? (size_t)ns * n_sets : 0);
+    std::vector<uint64_t> h_pcost(pathed ? (size_t)ns * n_sets : 0), h_moved(pathed ? (size_t)ns * n_sets : 0);
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
 
     // ---- the pointer tables of the whole call, uploaded once: per sequence one slice per projected frame, then the outputs ----
@@ -615,7 +631,8 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         if (!h_stats.empty())
             HIPCHK(hipMemcpyAsync(h_stats.data() + (size_t)16 * ns * set0, R->ex_stats, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
         if (monitored && (rc = rig_mon_collect(R, h_mon.data() + mon_words * set0, m, s))) return rc;  // likewise
-        if (pathed && (rc = rig_sp_collect(R, h_paths.data() + R->sp_rows * set0, h_pcost.data() + (size_t)ns * set0, m, s))) return rc;
+        if (pathed && (rc = rig_sp_collect(R, h_paths.data() + R->sp_rows * set0, h_pcost.data() + (size_t)ns * set0, h_moved.data() + (size_t)ns * set0, m, set0 + m == n_sets, s)))
+            return rc;
         O.read_all();  // the next sequence uses the same workspaces
         if (O.hip_fault) break;
         set0 += m;
@@ -634,7 +651,9 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     if (R->sp_mode) {
         R->sp_last.swap(h_paths);
         R->sp_last_cost.swap(h_pcost);
+        R->sa_last_moved.swap(h_moved);
         R->sp_last_sets = n_sets;
+        if (anchored) R->sa_has = true;  // the last set's paths, copied behind the last sequence
     }
     for (int i = 0; i < n_sets; ++i)
         if (set_status[i] != STITCH_OK)

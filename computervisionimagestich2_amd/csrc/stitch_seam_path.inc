@@ -4,15 +4,30 @@ namespace {
 
 inline bool seam_path_opts_ok(const stitch_seam_path_opts& o) { return o.max_step >= 1 && o.max_step <= SP_MAXK && o.margin >= 0 && o.margin <= SP_MAXM; }
 
+inline bool seam_anchor_opts_ok(const stitch_seam_anchor_opts& o) {
+    return o.weight >= 0 && o.cap >= 1 && (long long)o.weight * o.cap <= STITCH_SEAM_ANCHOR_MAX;
+}
+
 // the finder's second launch over the costs of n pairs: one workgroup per pair, its two rows of states in dynamic LDS
+// (an: include/stitch_seam_anchor.h, the anchored instantiation; null: the finder as it is)
 int seam_path_dp(const unsigned* d_cost, int n, int cw, int ch, int max_step, uint8_t* d_pred, int32_t* d_paths, size_t path_stride, uint64_t* d_costs,
-                 size_t cost_stride, hipStream_t s) {
+                 size_t cost_stride, hipStream_t s, const SeamAnchor* an = nullptr) {
+    const size_t lds = sizeof(unsigned long long) * 2 * (size_t)(cw + 1);
+    if (an) {
+        static std::once_flag once_anchored;
+        std::call_once(once_anchored, [] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seam_path_dp<SeamAnchor>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)(sizeof(unsigned long long) * 2 * (SP_MAXW + 1)));
+        });
+        k_seam_path_dp<SeamAnchor><<<(unsigned)n, SP_DT, lds, s>>>(d_cost, cw, ch, max_step, d_pred, d_paths, path_stride, reinterpret_cast<unsigned long long*>(d_costs),
+                                                               cost_stride, *an);
+        return launch_check("k_seam_path_dp (anchored)");
+    }
     static std::once_flag once;  // more than 64 KB of dynamic LDS is opt-in per function
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_seam_path_dp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * 2 * (SP_MAXW + 1)));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seam_path_dp<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * 2 * (SP_MAXW + 1)));
     });
-    const size_t lds = sizeof(unsigned long long) * 2 * (size_t)(cw + 1);
-    k_seam_path_dp<<<(unsigned)n, SP_DT, lds, s>>>(d_cost, cw, ch, max_step, d_pred, d_paths, path_stride, reinterpret_cast<unsigned long long*>(d_costs), cost_stride);
+    k_seam_path_dp<><<<(unsigned)n, SP_DT, lds, s>>>(d_cost, cw, ch, max_step, d_pred, d_paths, path_stride, reinterpret_cast<unsigned long long*>(d_costs), cost_stride);
     return launch_check("k_seam_path_dp");
 }
 
@@ -82,8 +97,14 @@ int stitch_dev_pairs_pathed_f32(stitch_plan* plan, const stitch_pair_desc* pairs
     return dev_pairs_pathed<float>(plan, pairs, n, d_paths, branches, stream);
 }
 
-int stitch_dev_pairs_seam_path_u8(const stitch_pair_desc* pairs, int n, int cw, int ch, const uint8_t* const* d_cov_a, const uint8_t* const* d_cov_b,
-                                  const int32_t* branches, const stitch_seam_path_opts* opts, int32_t* d_paths, uint64_t* d_costs, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// the finder of n pairs; d_anchors, ao, d_moved: all null, or the anchored call's (include/stitch_seam_anchor.h), checked by it
+int pairs_seam_path(const stitch_pair_desc* pairs, int n, int cw, int ch, const uint8_t* const* d_cov_a, const uint8_t* const* d_cov_b, const int32_t* branches,
+                    const stitch_seam_path_opts* opts, int32_t* d_paths, uint64_t* d_costs, void* stream, const int32_t* const* d_anchors,
+                    const stitch_seam_anchor_opts* ao, uint64_t* d_moved) {
     if (!pairs || !d_cov_a || !d_cov_b || !branches || !d_paths || !d_costs) return fail(STITCH_ERR_ARG, "pairs_seam_path: null argument");
     stitch_seam_path_opts o;
     stitch_seam_path_opts_default(&o);
@@ -109,11 +130,34 @@ int stitch_dev_pairs_seam_path_u8(const stitch_pair_desc* pairs, int n, int cw, 
     unsigned* d_cost = nullptr;
     uint8_t* d_pred = nullptr;
     if ((rc = A.take(&d_tab, sizeof(SeamPathPair) * n)) || (rc = A.take(&d_cost, sizeof(unsigned) * states)) || (rc = A.take(&d_pred, states))) return rc;
-    PanoWait wait{s};  // `tab` is read by its upload
+    const int32_t** d_atab = nullptr;
+    if (d_anchors && (rc = A.take(&d_atab, sizeof(int32_t*) * n))) return rc;
+    PanoWait wait{s};  // `tab` (and the caller's anchor table) is read by its upload
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(SeamPathPair) * n, hipMemcpyHostToDevice, s));
+    if (d_anchors) HIPCHK(hipMemcpyAsync(d_atab, d_anchors, sizeof(int32_t*) * n, hipMemcpyHostToDevice, s));
     k_seam_path_cost<<<dim3((unsigned)ch, (unsigned)n), SP_CT, 0, s>>>(d_tab, cw, ch, o.margin, d_cost);
     if ((rc = launch_check("k_seam_path_cost"))) return rc;
-    return seam_path_dp(d_cost, n, cw, ch, o.max_step, d_pred, d_paths, (size_t)ch, d_costs, 1, s);
+    if (!d_anchors) return seam_path_dp(d_cost, n, cw, ch, o.max_step, d_pred, d_paths, (size_t)ch, d_costs, 1, s);
+    const SeamAnchor an{d_atab, nullptr, 0, (unsigned)ao->weight, (unsigned)ao->cap, reinterpret_cast<unsigned long long*>(d_moved), 1};
+    return seam_path_dp(d_cost, n, cw, ch, o.max_step, d_pred, d_paths, (size_t)ch, d_costs, 1, s, &an);
+}
+
+}  // namespace
+
+extern "C" {
+
+int stitch_dev_pairs_seam_path_u8(const stitch_pair_desc* pairs, int n, int cw, int ch, const uint8_t* const* d_cov_a, const uint8_t* const* d_cov_b,
+                                  const int32_t* branches, const stitch_seam_path_opts* opts, int32_t* d_paths, uint64_t* d_costs, void* stream) {
+    return pairs_seam_path(pairs, n, cw, ch, d_cov_a, d_cov_b, branches, opts, d_paths, d_costs, stream, nullptr, nullptr, nullptr);
+}
+
+int stitch_dev_pairs_seam_path_anchored_u8(const stitch_pair_desc* pairs, int n, int cw, int ch, const uint8_t* const* d_cov_a, const uint8_t* const* d_cov_b,
+                                           const int32_t* branches, const stitch_seam_path_opts* opts, const int32_t* const* d_anchors,
+                                           const stitch_seam_anchor_opts* aopts, int32_t* d_paths, uint64_t* d_costs, uint64_t* d_moved, void* stream) {
+    if (!d_anchors || !aopts || !d_moved) return fail(STITCH_ERR_ARG, "pairs_seam_path_anchored: null anchor table, anchor options or moved array");
+    if (!seam_anchor_opts_ok(*aopts))
+        return fail(STITCH_ERR_ARG, "pairs_seam_path_anchored: weight %d below 0, cap %d below 1, or weight * cap above %d", aopts->weight, aopts->cap, STITCH_SEAM_ANCHOR_MAX);
+    return pairs_seam_path(pairs, n, cw, ch, d_cov_a, d_cov_b, branches, opts, d_paths, d_costs, stream, d_anchors, aopts, d_moved);
 }
 
 }  // extern "C"

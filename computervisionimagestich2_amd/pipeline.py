@@ -155,7 +155,10 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     paths=[one int32 sequence of ch columns per step] nothing is found and the step blends along the given path.  The return value
     grows by `found`, a list of (path, cost) per step (an int32 device tensor; the cost is None for a given path): (mosaic, found),
     or (mosaic, records, found) with residuals -- the single-set statement of a rig with path seams.  With seam_paths=None the
-    return value and every byte stay as they are.
+    return value and every byte stay as they are.  With anchors=[per step an int32 sequence of ch columns, or None], weight= and
+    cap= in the dict (include/stitch_seam_anchor.h) every step's finder takes the temporal term towards its anchor and `found`
+    holds (path, cost, moved) per step; a caller that feeds a set's found paths into the next set's call as anchors states a rig
+    that anchors per set.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     if formats is not None:
         in_fmt, out_fmt, matrix = formats
@@ -186,6 +189,8 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             raise ValueError("one pair of coverage masks and one branch per step")
         if seam_paths.get("paths") is not None and len(seam_paths["paths"]) != len(steps):
             raise ValueError("one path per step")
+        if seam_paths.get("anchors") is not None and len(seam_paths["anchors"]) != len(steps):
+            raise ValueError("one anchor (or None) per step")
     result = projected(steps[0]["start"])
     used, records, found = [], [], []
     for k, st in enumerate(steps):
@@ -205,16 +210,23 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         if seam_paths is not None:
             import torch
             inputs = (projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])
-            branch = int(seam_paths["branches"][k])
+            branch, tail = int(seam_paths["branches"][k]), ()
             if seam_paths.get("paths") is not None:
                 given = seam_paths["paths"][k]
                 path, cost = torch.as_tensor(given.cpu().numpy() if hasattr(given, "cpu") else given, dtype=torch.int32).to(result.device).contiguous(), None
             else:
                 cov_a, cov_b = seam_paths["coverage"][k]
-                paths, costs = capi.dev_pairs_seam_path([inputs], st["cw"], st["ch"], [cov_a], [cov_b], [branch], seam_paths.get("max_step", 2),
-                                                        seam_paths.get("margin", 8))
+                extra = {}
+                if seam_paths.get("anchors") is not None:
+                    given = seam_paths["anchors"][k]
+                    if given is not None:
+                        given = torch.as_tensor(given.cpu().numpy() if hasattr(given, "cpu") else given, dtype=torch.int32).to(result.device).contiguous()
+                    extra = dict(anchors=[given], weight=seam_paths["weight"], cap=seam_paths["cap"])
+                paths, costs, *moved = capi.dev_pairs_seam_path([inputs], st["cw"], st["ch"], [cov_a], [cov_b], [branch], seam_paths.get("max_step", 2),
+                                                                seam_paths.get("margin", 8), **extra)
                 path, cost = paths[0], int(costs[0])
-            found.append((path, cost))
+                tail = (int(moved[0][0]),) if moved else ()
+            found.append((path, cost, *tail))
             out = torch.empty((3, st["ch"], st["cw"]), dtype=result.dtype, device=result.device)
             result = plan.pairs([inputs + (out,)], paths=[path], branches=[branch])[0]
         else:

@@ -36,7 +36,7 @@ from bench_rig import timeit  # noqa: E402
 from computervisionimagestich2_amd import bmp, capi  # noqa: E402
 
 # One state of k_seam_path_dp's row, counted in its gfx950 ISA (make -C computervisionimagestich2_amd/csrc asm; the row loop is the
-# block of _ZN2sk14k_seam_path_dpEPKjiiiPhPimPym that ends in its one s_barrier, 644 instructions for the nine unrolled states).
+# block of _ZN2sk14k_seam_path_dpIJEEEvPKjiiiPhPimPymDpT_, the instantiation without an anchor, that ends in its one s_barrier, 644 instructions for the nine unrolled states).
 # The loop over k = 1 .. K of one state is 32 instructions per pass where both candidates s - k and s + k are inside the row: 2
 # ds_read_b64, 2 v_cmp_lt_u64 and 6 v_cndmask_b32 (value low, value high, offset, per candidate), 2 bounds compares, 2 s_waitcnt, and
 # 16 of address arithmetic, exec masking and the back edge (25 per pass at the row's ends, where one side is left).  Around it a
