@@ -189,6 +189,12 @@ RIG_FORMAT_SIGNATURES = _signatures(
     ("stitch_dev_rig_stitch_fmt_u8", i32, vp, vp, i32, vp, vp, vp, vp, vp),
 )
 
+# The same for include/stitch_rig_formats_yuv.h, the 4:2:2 layouts and NV21 (which the calls above take as further codes) and the query of
+# the form a frame index took; tests/test_pixfmt_yuv_host.py holds it to that header.  (Bound where the library exports it, likewise.)
+RIG_FORMAT_YUV_SIGNATURES = _signatures(
+    ("stitch_rig_input_form", i32, vp, i32, vp),
+)
+
 # The same for include/stitch_rig_monitor.h, a rig's alignment monitor; tests/test_rig_monitor_host.py holds it to that header.
 # (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the eight.)
 RIG_MONITOR_SIGNATURES = _signatures(
@@ -262,9 +268,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h (likewise)
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_formats_yuv.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
-                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()):
+                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_FORMAT_YUV_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1543,6 +1549,11 @@ def dev_largest_rect(mask):
 # ---- camera layouts: include/stitch_rig_formats.h ---------------------------------------------------------------------------
 PIX_PLANAR, PIX_RGB24, PIX_BGR24, PIX_RGBX32, PIX_BGRX32, PIX_NV12 = range(6)
 _PIX_BPP = {PIX_RGB24: 3, PIX_BGR24: 3, PIX_RGBX32: 4, PIX_BGRX32: 4, PIX_NV12: 1}
+# include/stitch_rig_formats_yuv.h: the 4:2:2 layouts and NV21, and the forms Rig.input_form answers with
+PIX_YUYV, PIX_UYVY, PIX_NV21, PIX_NV16 = range(16, 20)
+_PIX_TWO_PLANES = (PIX_NV12, PIX_NV21, PIX_NV16)
+_PIX_ALL = tuple(range(6)) + tuple(range(16, 20))
+RIG_INPUT_NONE, RIG_INPUT_FUSED, RIG_INPUT_CONVERTED = range(3)
 
 
 class ImageDesc(C.Structure):
@@ -1554,13 +1565,16 @@ def tight_pitches(fmt, w):
     """(pitch, pitch2) of rows without padding; (0, 0) for PIX_PLANAR, which has none."""
     if fmt == PIX_PLANAR:
         return 0, 0
-    return _PIX_BPP[fmt] * w, (2 * ((w + 1) // 2) if fmt == PIX_NV12 else 0)
+    pairs = 2 * ((w + 1) // 2)
+    if fmt in (PIX_YUYV, PIX_UYVY):  # groups of 4 bytes, two pixels each
+        return 2 * pairs, 0
+    return (w if fmt in _PIX_TWO_PLANES else _PIX_BPP[fmt] * w), (pairs if fmt in _PIX_TWO_PLANES else 0)
 
 
 def image_bytes(fmt, w, h, pitch=None, pitch2=None):
     """stitch_image_bytes (host only): the extent of each plane in bytes, (bytes, bytes2); a pitch of None is the tight one.  Raises
     StitchError(ERR_ARG) for a bad format, size or pitch."""
-    tight = tight_pitches(fmt, w) if 0 <= fmt <= PIX_NV12 else (0, 0)
+    tight = tight_pitches(fmt, w) if fmt in _PIX_ALL else (0, 0)
     b1, b2 = C.c_size_t(), C.c_size_t()
     _chk(lib().stitch_image_bytes(int(fmt), int(w), int(h), int(tight[0] if pitch is None else pitch), int(tight[1] if pitch2 is None else pitch2),
                                   C.byref(b1), C.byref(b2)))
@@ -1568,9 +1582,10 @@ def image_bytes(fmt, w, h, pitch=None, pitch2=None):
 
 
 class Image:
-    """One image in a layout of include/stitch_rig_formats.h: uint8 device tensors plus pitches.  `data` (and for PIX_NV12 `data2`, the
-    CbCr plane) are contiguous uint8 tensors that start at the plane's first byte and hold at least image_bytes(...) bytes -- any shape,
-    so a view into a larger buffer gives an odd base; for PIX_PLANAR `data` is the dense (3, h, w) tensor of every other call."""
+    """One image in a layout of include/stitch_rig_formats.h or include/stitch_rig_formats_yuv.h: uint8 device tensors plus pitches.
+    `data` (and for PIX_NV12, PIX_NV21 and PIX_NV16 `data2`, the chroma plane) are contiguous uint8 tensors that start at the plane's
+    first byte and hold at least image_bytes(...) bytes -- any shape, so a view into a larger buffer gives an odd base; for PIX_PLANAR
+    `data` is the dense (3, h, w) tensor of every other call."""
 
     def __init__(self, fmt, width, height, data, data2=None, pitch=None, pitch2=None):
         tight = tight_pitches(fmt, width)
@@ -1802,7 +1817,7 @@ class Rig(_Handle):
 
     def set_formats(self, in_fmt, out_fmt, matrix=0):
         """stitch_rig_set_formats (host only): every later stitch() takes its frames as Images of in_fmt and returns Images of
-        out_fmt (include/stitch_rig_formats.h); matrix: the NV12 matrix of both sides.  Returns self."""
+        out_fmt (include/stitch_rig_formats.h, include/stitch_rig_formats_yuv.h); matrix: the Y Cb Cr matrix of both sides.  Returns self."""
         _chk(lib().stitch_rig_set_formats(self._h, int(in_fmt), int(out_fmt), int(matrix)))
         return self
 
@@ -1819,6 +1834,14 @@ class Rig(_Handle):
         v = [C.c_int() for _ in range(3)]
         _chk(lib().stitch_rig_formats(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def input_form(self, frame):
+        """stitch_rig_input_form (host only): how the last completed stitch() with a format set read frame index `frame` --
+        RIG_INPUT_NONE (no such call yet, a planar in_fmt, or a frame no step uses), RIG_INPUT_FUSED (the tiled projection staged the
+        packed frames itself) or RIG_INPUT_CONVERTED (one conversion launch into planar scratch, then the planar projection)."""
+        form = C.c_int()
+        _chk(lib().stitch_rig_input_form(self._h, int(frame), C.byref(form)))
+        return form.value
 
     def set_monitor(self, radius):
         """stitch_rig_set_monitor (host only): every later stitch() also measures, per set and step, the residuals of the blend's

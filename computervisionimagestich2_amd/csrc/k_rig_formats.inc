@@ -1,13 +1,15 @@
 // Part of stitch_kernels.hpp (included there, inside namespace sk): a rig's frames and mosaics in camera layouts
-// (include/stitch_rig_formats.h, which states every rule restated here) -- packed RGB / BGR with or without a fourth byte, and NV12 --
-// to and from the dense planar layout of every other kernel, many same-size images per launch.
+// (include/stitch_rig_formats.h and include/stitch_rig_formats_yuv.h, which state every rule restated here) -- packed RGB / BGR with or
+// without a fourth byte, NV12 and NV21 (4:2:0), YUYV, UYVY and NV16 (4:2:2) -- to and from the dense planar layout of every other
+// kernel, many same-size images per launch.
 //
-// blockIdx.z = image, blockIdx.y = row (NV12 pack: row PAIR; in turn where the grid is smaller), and a work-item owns four pixels of
-// the row (NV12 pack: two 2 x 2 blocks, so the chroma average needs no second pass).  A row whose addresses on both sides are
-// multiples of four moves its full groups as dwords (a row of four-byte pixels on a 16-byte boundary as one 16-byte access per
-// group); the pixels behind the last full group, and every row of any other alignment, move as bytes.  Both forms run the same
-// per-pixel functions, so they give the same bytes.  Integers only; wave64, plain C++.
+// blockIdx.z = image, blockIdx.y = row (NV12 / NV21 pack: row PAIR; in turn where the grid is smaller), and a work-item owns four
+// pixels of the row (NV12 / NV21 pack: two 2 x 2 blocks; 4:2:2 pack: two 2 x 1 pairs -- the chroma average needs no second pass).
+// A row whose addresses on both sides are multiples of four moves its full groups as dwords (a row of four-byte pixels on a 16-byte
+// boundary as one 16-byte access per group); the pixels behind the last full group, and every row of any other alignment, move as
+// bytes.  Both forms run the same per-pixel functions, so they give the same bytes.  Integers only; wave64, plain C++.
 constexpr int PIX_PLANAR = 0, PIX_RGB24 = 1, PIX_BGR24 = 2, PIX_RGBX32 = 3, PIX_BGRX32 = 4, PIX_NV12 = 5;
+constexpr int PIX_YUYV = 16, PIX_UYVY = 17, PIX_NV21 = 18, PIX_NV16 = 19;
 
 struct FmtImage {  // one entry of the device table: the packed image and the dense planar one
     uint8_t* data;
@@ -25,9 +27,27 @@ struct Nv12K {  // the 16.16 coefficients of one matrix, both directions
 
 template <int FMT>
 struct FmtTraits {
-    static constexpr int bpp = FMT == PIX_RGB24 || FMT == PIX_BGR24 ? 3 : FMT == PIX_NV12 ? 1 : 4;
+    static constexpr bool yuv = FMT == PIX_NV12 || FMT >= PIX_YUYV;                 // Y Cb Cr through one of the matrices
+    static constexpr bool two_planes = FMT == PIX_NV12 || FMT == PIX_NV21 || FMT == PIX_NV16;
+    static constexpr bool c422 = FMT == PIX_YUYV || FMT == PIX_UYVY || FMT == PIX_NV16;  // a chroma pair per 2 x 1 pixels (else, yuv: per 2 x 2)
+    // bytes from one pixel of plane 0 to the next (YUYV, UYVY: from one Y to the next)
+    static constexpr int bpp = FMT == PIX_RGB24 || FMT == PIX_BGR24 ? 3 : two_planes ? 1 : FMT == PIX_YUYV || FMT == PIX_UYVY ? 2 : 4;
     static constexpr int ro = FMT == PIX_BGR24 || FMT == PIX_BGRX32 ? 2 : 0;  // the byte of a pixel that holds R; G is byte 1, B is 2 - ro
+    // yuv: a chroma pair's place is cstep bytes after the one before it; Cb and Cr are its bytes cbo and cro.  In YUYV and UYVY that
+    // place is the 4-byte group itself, and pixel 2i's Y is byte yo of the group, pixel 2i+1's is byte yo + 2.
+    static constexpr int cstep = two_planes ? 2 : 4;
+    static constexpr int yo = FMT == PIX_UYVY ? 1 : 0;
+    static constexpr int cbo = FMT == PIX_YUYV || FMT == PIX_NV21 ? 1 : 0;
+    static constexpr int cro = FMT == PIX_YUYV ? 3 : FMT == PIX_UYVY ? 2 : FMT == PIX_NV21 ? 0 : 1;
 };
+// the chroma row of row y (srow: its row of plane 0): the second plane's, or for one plane the row itself
+template <int FMT, typename P>
+__device__ __forceinline__ P* fmt_crow(const FmtImage& e, int y, P* srow) {
+    if constexpr (FmtTraits<FMT>::two_planes)
+        return e.data2 + (size_t)(FmtTraits<FMT>::c422 ? y : y / 2) * e.pitch2;
+    else
+        return srow;
+}
 
 __device__ __forceinline__ unsigned fmt_clip(int v) { return (unsigned)max(0, min(v, 255)); }
 __device__ __forceinline__ void nv12_decode(const Nv12K& k, int Y, int Cb, int Cr, unsigned& r, unsigned& g, unsigned& b) {
@@ -53,23 +73,45 @@ __device__ __forceinline__ bool fmt_aligned(const void* a, const void* b, const 
 }
 
 // ---- to planar -----------------------------------------------------------------------------------------------------------------
-// One pixel of a packed row (p = its first byte), or of an NV12 row (p = its Y byte, q = its CbCr pair).
+// One pixel of a packed row (p = its first byte), or of a Y Cb Cr row (p = its Y byte, q = the place of its chroma pair).
 template <int FMT>
 __device__ __forceinline__ void fmt_load_px(const uint8_t* p, const uint8_t* q, const Nv12K& k, unsigned& r, unsigned& g, unsigned& b) {
-    if constexpr (FMT == PIX_NV12)
-        nv12_decode(k, p[0], q[0], q[1], r, g, b);
+    if constexpr (FmtTraits<FMT>::yuv)
+        nv12_decode(k, p[FmtTraits<FMT>::yo], q[FmtTraits<FMT>::cbo], q[FmtTraits<FMT>::cro], r, g, b);
     else
         r = p[FmtTraits<FMT>::ro], g = p[1], b = p[2 - FmtTraits<FMT>::ro];
+}
+// The Y of four pixels and their two chroma pairs from a 4-byte-aligned row: one dword of Y and one of chroma (two planes), or the
+// two dwords of two groups (YUYV, UYVY).  p, q as above, of the four's first pixel.
+template <int FMT>
+__device__ __forceinline__ void fmt_yuv_4(const uint8_t* p, const uint8_t* q, int Y[4], int Cb[2], int Cr[2]) {
+    using T = FmtTraits<FMT>;
+    if constexpr (T::two_planes) {
+        const unsigned y4 = *reinterpret_cast<const unsigned*>(p), uv = *reinterpret_cast<const unsigned*>(q);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Y[i] = (int)fmt_byte(y4, i);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) Cb[j] = (int)fmt_byte(uv, 2 * j + T::cbo), Cr[j] = (int)fmt_byte(uv, 2 * j + T::cro);
+    } else {
+        const unsigned* s = reinterpret_cast<const unsigned*>(p);
+        const unsigned v[2] = {s[0], s[1]};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            Y[2 * j] = (int)fmt_byte(v[j], T::yo), Y[2 * j + 1] = (int)fmt_byte(v[j], T::yo + 2);
+            Cb[j] = (int)fmt_byte(v[j], T::cbo), Cr[j] = (int)fmt_byte(v[j], T::cro);
+        }
+    }
 }
 // Four pixels of an aligned row as one dword per plane (byte i = pixel i).  p, q as above, of the group's first pixel.
 template <int FMT>
 __device__ __forceinline__ void fmt_load_4(const uint8_t* p, const uint8_t* q, bool by16, const Nv12K& k, unsigned& R, unsigned& G, unsigned& B) {
     unsigned c[3] = {0u, 0u, 0u};
-    if constexpr (FMT == PIX_NV12) {
-        const unsigned y4 = *reinterpret_cast<const unsigned*>(p), uv = *reinterpret_cast<const unsigned*>(q);
+    if constexpr (FmtTraits<FMT>::yuv) {
+        int Y[4], Cb[2], Cr[2];
+        fmt_yuv_4<FMT>(p, q, Y, Cb, Cr);
         unsigned r[4], g[4], b[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) nv12_decode(k, (int)fmt_byte(y4, i), (int)fmt_byte(uv, 2 * (i / 2)), (int)fmt_byte(uv, 2 * (i / 2) + 1), r[i], g[i], b[i]);
+        for (int i = 0; i < 4; ++i) nv12_decode(k, Y[i], Cb[i / 2], Cr[i / 2], r[i], g[i], b[i]);
         c[0] = fmt_pack4(r[0], r[1], r[2], r[3]), c[1] = fmt_pack4(g[0], g[1], g[2], g[3]), c[2] = fmt_pack4(b[0], b[1], b[2], b[3]);
     } else if constexpr (FmtTraits<FMT>::bpp == 4) {
         uint4 v;
@@ -92,7 +134,7 @@ __device__ __forceinline__ void fmt_load_4(const uint8_t* p, const uint8_t* q, b
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) c[ch] |= fmt_byte(v[(3 * i + ch) / 4], (3 * i + ch) % 4) << (8 * i);
     }
-    if constexpr (FMT == PIX_NV12) {
+    if constexpr (FmtTraits<FMT>::yuv) {
         R = c[0], G = c[1], B = c[2];
     } else {
         R = c[FmtTraits<FMT>::ro], G = c[1], B = c[2 - FmtTraits<FMT>::ro];
@@ -107,7 +149,7 @@ __global__ __launch_bounds__(256) void k_unpack_many(const FmtImage* __restrict_
     const int groups = (w + 3) / 4;
     for (int y = blockIdx.y; y < h; y += gridDim.y) {
         const uint8_t* srow = e.data + (size_t)y * e.pitch;
-        const uint8_t* crow = FMT == PIX_NV12 ? e.data2 + (size_t)(y / 2) * e.pitch2 : srow;
+        const uint8_t* crow = fmt_crow<FMT>(e, y, srow);
         uint8_t* d0 = e.planar + (size_t)y * w;
         const bool wide = fmt_aligned(srow, crow, d0, d0 + pl, 3u) && fmt_aligned(d0 + 2 * pl, nullptr, nullptr, nullptr, 3u);  // block-uniform
         const bool by16 = bpp == 4 && (reinterpret_cast<uintptr_t>(srow) & 15u) == 0;
@@ -115,14 +157,14 @@ __global__ __launch_bounds__(256) void k_unpack_many(const FmtImage* __restrict_
             const int x = 4 * gi, npx = min(4, w - x);
             if (wide && npx == 4) {
                 unsigned R, G, B;
-                fmt_load_4<FMT>(srow + (size_t)x * bpp, crow + x, by16, k, R, G, B);  // (NV12: pair x / 2 is at byte x, x a multiple of 4)
+                fmt_load_4<FMT>(srow + (size_t)x * bpp, crow + x, by16, k, R, G, B);  // (two planes: pair x / 2 is at byte x, x a multiple of 4)
                 *reinterpret_cast<unsigned*>(d0 + x) = R;
                 *reinterpret_cast<unsigned*>(d0 + pl + x) = G;
                 *reinterpret_cast<unsigned*>(d0 + 2 * pl + x) = B;
             } else {
                 for (int i = 0; i < npx; ++i) {
                     unsigned r, g, b;
-                    fmt_load_px<FMT>(srow + (size_t)(x + i) * bpp, crow + 2 * ((x + i) / 2), k, r, g, b);
+                    fmt_load_px<FMT>(srow + (size_t)(x + i) * bpp, crow + FmtTraits<FMT>::cstep * ((x + i) / 2), k, r, g, b);
                     d0[x + i] = (uint8_t)r;
                     d0[pl + x + i] = (uint8_t)g;
                     d0[2 * pl + x + i] = (uint8_t)b;
@@ -207,7 +249,7 @@ __global__ __launch_bounds__(256) void k_pack_many(const FmtImage* __restrict__ 
     const FmtImage e = img[blockIdx.z];
     const size_t pl = (size_t)rc.W * rc.H;
     const int w = rc.w, h = rc.h, groups = (w + 3) / 4;
-    if constexpr (FMT != PIX_NV12) {
+    if constexpr (!FmtTraits<FMT>::yuv) {
         constexpr int bpp = FmtTraits<FMT>::bpp;
         for (int y = blockIdx.y; y < h; y += gridDim.y) {
             const uint8_t* s0 = e.planar + (size_t)(rc.y0 + y) * rc.W + rc.x0;
@@ -225,6 +267,51 @@ __global__ __launch_bounds__(256) void k_pack_many(const FmtImage* __restrict__ 
                         unsigned r, g, b;
                         fmt_src_px<FINISH>(s0 + x + i, pl, slut, mk, r, g, b);
                         fmt_store_px<FMT>(drow + (size_t)(x + i) * bpp, r, g, b);
+                    }
+                }
+            }
+        }
+    } else if constexpr (FmtTraits<FMT>::c422) {
+        using T = FmtTraits<FMT>;
+        for (int y = blockIdx.y; y < h; y += gridDim.y) {
+            const uint8_t* s0 = e.planar + (size_t)(rc.y0 + y) * rc.W + rc.x0;
+            uint8_t* drow = e.data + (size_t)y * e.pitch;
+            uint8_t* crow = fmt_crow<FMT>(e, y, drow);
+            const bool wide = fmt_aligned(s0, s0 + pl, s0 + 2 * pl, drow, 3u) && fmt_aligned(crow, nullptr, nullptr, nullptr, 3u);  // block-uniform
+            for (int gi = blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += gridDim.x * blockDim.x) {
+                const int x = 4 * gi, npx = min(4, w - x);
+                if (wide && npx == 4) {
+                    unsigned r[4], g[4], b[4], Y[4], cb[4], cr[4];
+                    fmt_src_4<FINISH>(s0 + x, pl, slut, mk, r, g, b);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) nv12_encode(k, (int)r[i], (int)g[i], (int)b[i], Y[i], cb[i], cr[i]);
+                    const unsigned u0 = (cb[0] + cb[1] + 1u) >> 1, v0 = (cr[0] + cr[1] + 1u) >> 1, u1 = (cb[2] + cb[3] + 1u) >> 1, v1 = (cr[2] + cr[3] + 1u) >> 1;
+                    if constexpr (T::two_planes) {
+                        *reinterpret_cast<unsigned*>(drow + x) = fmt_pack4(Y[0], Y[1], Y[2], Y[3]);
+                        *reinterpret_cast<unsigned*>(crow + x) = fmt_pack4(u0, v0, u1, v1);
+                    } else {
+                        unsigned* d = reinterpret_cast<unsigned*>(drow + 2 * (size_t)x);  // two groups: byte 2 x of the row on
+                        d[0] = FMT == PIX_YUYV ? fmt_pack4(Y[0], u0, Y[1], v0) : fmt_pack4(u0, Y[0], v0, Y[1]);
+                        d[1] = FMT == PIX_YUYV ? fmt_pack4(Y[2], u1, Y[3], v1) : fmt_pack4(u1, Y[2], v1, Y[3]);
+                    }
+                } else {
+                    for (int i0 = 0; i0 < npx; i0 += 2) {  // one 2 x 1 pair: columns xa, xb (xb == xa on the clamped last column of an odd width)
+                        const int xa = x + i0, xb = min(xa + 1, w - 1);
+                        unsigned r, g, b, Ya, Yb, ua, ub, va, vb;
+                        fmt_src_px<FINISH>(s0 + xa, pl, slut, mk, r, g, b);
+                        nv12_encode(k, (int)r, (int)g, (int)b, Ya, ua, va);
+                        fmt_src_px<FINISH>(s0 + xb, pl, slut, mk, r, g, b);
+                        nv12_encode(k, (int)r, (int)g, (int)b, Yb, ub, vb);
+                        uint8_t* c = crow + T::cstep * (xa / 2);  // the pair's place; one plane: the group, whose Y1 byte is a pixel byte
+                        if constexpr (T::two_planes) {
+                            drow[xa] = (uint8_t)Ya;
+                            drow[xb] = (uint8_t)Yb;  // a clamped coordinate writes its own pixel's value again
+                        } else {
+                            c[T::yo] = (uint8_t)Ya;
+                            c[T::yo + 2] = (uint8_t)Yb;  // ... and here the luma of pixel w - 1 into the last group's Y1
+                        }
+                        c[T::cbo] = (uint8_t)((ua + ub + 1u) >> 1);
+                        c[T::cro] = (uint8_t)((va + vb + 1u) >> 1);
                     }
                 }
             }
@@ -261,8 +348,12 @@ __global__ __launch_bounds__(256) void k_pack_many(const FmtImage* __restrict__ 
                     }
                     *reinterpret_cast<unsigned*>(da + x) = ya4;
                     *reinterpret_cast<unsigned*>(db + x) = yb4;
-                    *reinterpret_cast<unsigned*>(dc + x) = ((cb[0] + cb[1] + 2u) >> 2) | (((cr[0] + cr[1] + 2u) >> 2) << 8) | (((cb[2] + cb[3] + 2u) >> 2) << 16) |
-                                                           (((cr[2] + cr[3] + 2u) >> 2) << 24);
+                    if constexpr (FMT == PIX_NV21)  // every pair Cr Cb
+                        *reinterpret_cast<unsigned*>(dc + x) =
+                            fmt_pack4((cr[0] + cr[1] + 2u) >> 2, (cb[0] + cb[1] + 2u) >> 2, (cr[2] + cr[3] + 2u) >> 2, (cb[2] + cb[3] + 2u) >> 2);
+                    else
+                        *reinterpret_cast<unsigned*>(dc + x) = ((cb[0] + cb[1] + 2u) >> 2) | (((cr[0] + cr[1] + 2u) >> 2) << 8) | (((cb[2] + cb[3] + 2u) >> 2) << 16) |
+                                                               (((cr[2] + cr[3] + 2u) >> 2) << 24);
                 } else {
                     for (int i0 = 0; i0 < npx; i0 += 2) {  // one 2 x 2 block: columns xa, xb (xb == xa on the clamped last column of an odd width)
                         const int xa = x + i0, xb = min(xa + 1, w - 1);
@@ -277,8 +368,8 @@ __global__ __launch_bounds__(256) void k_pack_many(const FmtImage* __restrict__ 
                             su += u, sv += v;
                             (second_row ? db : da)[xx] = (uint8_t)Y;  // a clamped coordinate writes its own pixel's value again
                         }
-                        dc[2 * (xa / 2)] = (uint8_t)((su + 2u) >> 2);
-                        dc[2 * (xa / 2) + 1] = (uint8_t)((sv + 2u) >> 2);
+                        dc[2 * (xa / 2) + FmtTraits<FMT>::cbo] = (uint8_t)((su + 2u) >> 2);
+                        dc[2 * (xa / 2) + FmtTraits<FMT>::cro] = (uint8_t)((sv + 2u) >> 2);
                     }
                 }
             }
@@ -289,17 +380,19 @@ __global__ __launch_bounds__(256) void k_pack_many(const FmtImage* __restrict__ 
 // ---- the projection that stages a packed source itself -----------------------------------------------------------------------------
 // Four pixels of a 4-byte-aligned row as the LDS dwords pj_stage_rgbx builds (R | G << 8 | B << 16; pj_bilinear2 never reads bits
 // 24 .. 31, which hold X or a neighbour's byte here): no perm for RGBX32, one per pixel for BGRX32 and the three-byte formats, the
-// decode for NV12.  p, q as for fmt_load_4.
+// decode for the Y Cb Cr formats (fmt_yuv_4's dwords: a width that is a multiple of 4 keeps every 4:2:2 group whole).  p, q as for
+// fmt_load_4.
 template <int FMT>
 __device__ __forceinline__ uint4 fmt_lds_4(const uint8_t* p, const uint8_t* q, const Nv12K& k) {
     const unsigned* s = reinterpret_cast<const unsigned*>(p);
-    if constexpr (FMT == PIX_NV12) {
-        const unsigned y4 = s[0], uv = *reinterpret_cast<const unsigned*>(q);
+    if constexpr (FmtTraits<FMT>::yuv) {
+        int Y[4], Cb[2], Cr[2];
+        fmt_yuv_4<FMT>(p, q, Y, Cb, Cr);
         unsigned px[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             unsigned r, g, b;
-            nv12_decode(k, (int)fmt_byte(y4, i), (int)fmt_byte(uv, 2 * (i / 2)), (int)fmt_byte(uv, 2 * (i / 2) + 1), r, g, b);
+            nv12_decode(k, Y[i], Cb[i / 2], Cr[i / 2], r, g, b);
             px[i] = fmt_pack4(r, g, b, 0u);
         }
         return uint4{px[0], px[1], px[2], px[3]};
@@ -332,7 +425,7 @@ struct PjStageFmt {
         for (int rr = lr; rr < nrow; rr += 4) {
             const int y = r0 + rr;
             const uint8_t* srow = e.data + (size_t)y * e.pitch;
-            const uint8_t* crow = FMT == PIX_NV12 ? e.data2 + (size_t)(y / 2) * e.pitch2 : srow;
+            const uint8_t* crow = fmt_crow<FMT>(e, y, srow);
             for (int g = lc; g < gpr; g += 64) {
                 const int x = c0a + 4 * g;
                 uint4 v = uint4{0u, 0u, 0u, 0u};

@@ -33,6 +33,7 @@
 #include "stitch_rig_seams.h"
 #include "stitch_rig_crop.h"
 #include "stitch_rig_formats.h"
+#include "stitch_rig_formats_yuv.h"
 #include "stitch_rig_monitor.h"
 #include "stitch_seam_path.h"
 #include "stitch_seam_anchor.h"

@@ -46,6 +46,7 @@ struct stitch_rig {
     std::vector<uint8_t*> fmt_in;  // per projected frame: max_sets planar frames the input is converted to; from the first such call on
     uint8_t* fmt_out = nullptr;    // max_sets planar outputs the last step (or the crop copy) writes, `fmt_out_bytes` apart; likewise
     size_t fmt_out_bytes = 0;
+    std::vector<char> fmt_form;    // per frame index: STITCH_RIG_INPUT_* of the last completed call with images (empty: none yet)
     // ---- the alignment monitor (include/stitch_rig_monitor.h; stitch_rig_monitor.inc) ----
     int mon_radius = -1;                     // -1: no monitor, the replay as it is
     int mon_dom_radius = -1;                 // the radius the domains below were computed at, -1: not computed yet
@@ -643,6 +644,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     }
     HIPCHK(hipStreamSynchronize(s));  // the finish pass of the last sequence (read_all waited for the steps only)
     for (size_t j = 0; j < h_stats.size() / 16; ++j) std::memcpy(stats + 12 * j, h_stats.data() + 16 * j, sizeof(float) * 12);
+    if (fc) {  // include/stitch_rig_formats_yuv.h: the form each frame index took, kept once the replay has completed
+        R->fmt_form.assign((size_t)n, (char)STITCH_RIG_INPUT_NONE);
+        if (fin)
+            for (int f : R->needed) R->fmt_form[f] = (char)(fc->fused[f] ? STITCH_RIG_INPUT_FUSED : STITCH_RIG_INPUT_CONVERTED);
+    }
     if (R->mon_radius >= 0) {
         R->mon_last.swap(h_mon);
         R->mon_last_sets = n_sets;

@@ -1,6 +1,7 @@
-// stitch_rig_formats.inc -- a rig's frames and mosaics in camera layouts (include/stitch_rig_formats.h; kernels in
-// k_rig_formats.inc, DESIGN.md 19).  Included at the end of stitch_hip.hip (one translation unit), behind stitch_rig_crop.inc.  The
-// replay itself is rig_stitch of stitch_rig.inc, which calls the rig_fmt_* functions below for a call with images.
+// stitch_rig_formats.inc -- a rig's frames and mosaics in camera layouts (include/stitch_rig_formats.h and, for the 4:2:2 layouts
+// and NV21, include/stitch_rig_formats_yuv.h; kernels in k_rig_formats.inc, DESIGN.md 19 and 23).  Included at the end of
+// stitch_hip.hip (one translation unit), behind stitch_rig_crop.inc.  The replay itself is rig_stitch of stitch_rig.inc, which calls
+// the rig_fmt_* functions below for a call with images.
 namespace {
 
 // include/stitch_rig_formats.h's two tables, one row per matrix
@@ -10,8 +11,14 @@ const Nv12K kNv12[3] = {
     {0, 65536, 91881, 22553, 46802, 116130, 19595, 38470, 7471, 11058, 21710, 32768, 32768, 27439, 5329},
 };
 
-bool fmt_ok(int fmt) { return fmt >= STITCH_PIX_PLANAR && fmt <= STITCH_PIX_NV12; }
-int fmt_bpp(int fmt) { return fmt == STITCH_PIX_RGB24 || fmt == STITCH_PIX_BGR24 ? 3 : fmt == STITCH_PIX_NV12 ? 1 : 4; }
+bool fmt_ok(int fmt) { return (fmt >= STITCH_PIX_PLANAR && fmt <= STITCH_PIX_NV12) || (fmt >= STITCH_PIX_YUYV && fmt <= STITCH_PIX_NV16); }
+bool fmt_two_planes(int fmt) { return fmt == STITCH_PIX_NV12 || fmt == STITCH_PIX_NV21 || fmt == STITCH_PIX_NV16; }
+bool fmt_420(int fmt) { return fmt == STITCH_PIX_NV12 || fmt == STITCH_PIX_NV21; }
+// the pixel bytes of a row of plane 0
+long long fmt_row_bytes(int fmt, long long w) {
+    if (fmt == STITCH_PIX_YUYV || fmt == STITCH_PIX_UYVY) return 4 * ((w + 1) / 2);
+    return (fmt == STITCH_PIX_RGB24 || fmt == STITCH_PIX_BGR24 ? 3 : fmt_two_planes(fmt) ? 1 : 4) * w;
+}
 
 // The extents of an image's planes, or false for a bad format, size or pitch.
 bool fmt_extents(int fmt, long long w, long long h, long long pitch, long long pitch2, size_t* b1, size_t* b2) {
@@ -20,13 +27,13 @@ bool fmt_extents(int fmt, long long w, long long h, long long pitch, long long p
     if (fmt == STITCH_PIX_PLANAR) {
         e1 = (size_t)3 * (size_t)w * (size_t)h;
     } else {
-        const long long row = fmt_bpp(fmt) * w;
+        const long long row = fmt_row_bytes(fmt, w);
         if (pitch < row) return false;
         e1 = (size_t)((h - 1) * pitch + row);
-        if (fmt == STITCH_PIX_NV12) {
-            const long long row2 = 2 * ((w + 1) / 2);
+        if (fmt_two_planes(fmt)) {
+            const long long row2 = 2 * ((w + 1) / 2), rows2 = fmt_420(fmt) ? (h + 1) / 2 : h;
             if (pitch2 < row2) return false;
-            e2 = (size_t)(((h + 1) / 2 - 1) * pitch2 + row2);
+            e2 = (size_t)((rows2 - 1) * pitch2 + row2);
         }
     }
     if (b1) *b1 = e1;
@@ -37,7 +44,7 @@ bool fmt_extents(int fmt, long long w, long long h, long long pitch, long long p
 // One image of a call: its size against (w, h), its pointers, its pitches.
 int fmt_check_image(int fmt, const stitch_image& im, int w, int h, const char* who, const char* what, int index) {
     if (im.width != w || im.height != h) return fail(STITCH_ERR_ARG, "%s: %s %d is %d x %d, expected %d x %d", who, what, index, im.width, im.height, w, h);
-    if (!im.data || (fmt == STITCH_PIX_NV12 && !im.data2)) return fail(STITCH_ERR_ARG, "%s: %s %d has a null plane", who, what, index);
+    if (!im.data || (fmt_two_planes(fmt) && !im.data2)) return fail(STITCH_ERR_ARG, "%s: %s %d has a null plane", who, what, index);
     if (!fmt_extents(fmt, w, h, im.pitch, im.pitch2, nullptr, nullptr))
         return fail(STITCH_ERR_ARG, "%s: %s %d has a pitch (%d, %d) below its %d x %d rows", who, what, index, im.pitch, im.pitch2, w, h);
     return STITCH_OK;
@@ -62,6 +69,10 @@ int fmt_launch_unpack(int fmt, int matrix, const FmtImage* d_tab, int count, int
         case STITCH_PIX_RGBX32: k_unpack_many<PIX_RGBX32><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
         case STITCH_PIX_BGRX32: k_unpack_many<PIX_BGRX32><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
         case STITCH_PIX_NV12: k_unpack_many<PIX_NV12><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
+        case STITCH_PIX_YUYV: k_unpack_many<PIX_YUYV><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
+        case STITCH_PIX_UYVY: k_unpack_many<PIX_UYVY><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
+        case STITCH_PIX_NV21: k_unpack_many<PIX_NV21><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
+        case STITCH_PIX_NV16: k_unpack_many<PIX_NV16><<<g, 256, 0, s>>>(d_tab, w, h, k); break;
         default: return fail(STITCH_ERR_ARG, "unpack_many: format %d", fmt);
     }
     return launch_check("k_unpack_many");
@@ -69,7 +80,7 @@ int fmt_launch_unpack(int fmt, int matrix, const FmtImage* d_tab, int count, int
 
 template <bool FINISH>
 int fmt_launch_pack_as(int fmt, int matrix, const FmtImage* d_tab, int count, const FmtRect& rc, const int32_t* d_eq, const MixK& mk, hipStream_t s) {
-    const dim3 g = fmt_grid(rc.w, fmt == STITCH_PIX_NV12 ? (rc.h + 1) / 2 : rc.h, count);
+    const dim3 g = fmt_grid(rc.w, fmt_420(fmt) ? (rc.h + 1) / 2 : rc.h, count);  // row pairs for 4:2:0; rows for 4:2:2 and the rest
     const Nv12K k = kNv12[matrix];
     switch (fmt) {
         case STITCH_PIX_RGB24: k_pack_many<PIX_RGB24, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
@@ -77,13 +88,17 @@ int fmt_launch_pack_as(int fmt, int matrix, const FmtImage* d_tab, int count, co
         case STITCH_PIX_RGBX32: k_pack_many<PIX_RGBX32, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
         case STITCH_PIX_BGRX32: k_pack_many<PIX_BGRX32, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
         case STITCH_PIX_NV12: k_pack_many<PIX_NV12, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
+        case STITCH_PIX_YUYV: k_pack_many<PIX_YUYV, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
+        case STITCH_PIX_UYVY: k_pack_many<PIX_UYVY, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
+        case STITCH_PIX_NV21: k_pack_many<PIX_NV21, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
+        case STITCH_PIX_NV16: k_pack_many<PIX_NV16, FINISH><<<g, 256, 0, s>>>(d_tab, rc, d_eq, mk, k); break;
         default: return fail(STITCH_ERR_ARG, "pack_many: format %d", fmt);
     }
     return launch_check("k_pack_many");
 }
 
 int fmt_many_args(int fmt, int matrix, const void* a, const void* b, int count, const char* who) {
-    if (!fmt_ok(fmt) || fmt == STITCH_PIX_PLANAR) return fail(STITCH_ERR_ARG, "%s: format %d is not one of the packed formats 1 .. 5", who, fmt);
+    if (!fmt_ok(fmt) || fmt == STITCH_PIX_PLANAR) return fail(STITCH_ERR_ARG, "%s: format %d is not one of the packed formats 1 .. 5, 16 .. 19", who, fmt);
     if (matrix < 0 || matrix > 2) return fail(STITCH_ERR_ARG, "%s: matrix %d outside 0 .. 2", who, matrix);
     if (!a || !b || count < 1 || count > kRigMaxImages) return fail(STITCH_ERR_ARG, "%s: null table or %d images (1 .. %d)", who, count, kRigMaxImages);
     return STITCH_OK;
@@ -113,7 +128,7 @@ bool rig_fmt_fused(const stitch_rig* R, const RigFmtCall& fc, int f, int n_sets)
     for (int i = 0; i < n_sets; ++i) {
         const stitch_image& im = fc.frames[(size_t)i * R->n + f];
         uintptr_t bits = reinterpret_cast<uintptr_t>(im.data) | (uintptr_t)im.pitch;
-        if (R->in_fmt == STITCH_PIX_NV12) bits |= reinterpret_cast<uintptr_t>(im.data2) | (uintptr_t)im.pitch2;
+        if (fmt_two_planes(R->in_fmt)) bits |= reinterpret_cast<uintptr_t>(im.data2) | (uintptr_t)im.pitch2;
         if (bits & 3u) return false;
     }
     return true;
@@ -185,6 +200,10 @@ int rig_fmt_project(const stitch_rig* R, const FmtImage* d_tab, int m, int w, in
         case STITCH_PIX_BGR24: rig_fmt_project_as<PIX_BGR24>(d_tab, m, w, h, pp, lds, k, s); break;
         case STITCH_PIX_RGBX32: rig_fmt_project_as<PIX_RGBX32>(d_tab, m, w, h, pp, lds, k, s); break;
         case STITCH_PIX_BGRX32: rig_fmt_project_as<PIX_BGRX32>(d_tab, m, w, h, pp, lds, k, s); break;
+        case STITCH_PIX_YUYV: rig_fmt_project_as<PIX_YUYV>(d_tab, m, w, h, pp, lds, k, s); break;
+        case STITCH_PIX_UYVY: rig_fmt_project_as<PIX_UYVY>(d_tab, m, w, h, pp, lds, k, s); break;
+        case STITCH_PIX_NV21: rig_fmt_project_as<PIX_NV21>(d_tab, m, w, h, pp, lds, k, s); break;
+        case STITCH_PIX_NV16: rig_fmt_project_as<PIX_NV16>(d_tab, m, w, h, pp, lds, k, s); break;
         default: rig_fmt_project_as<PIX_NV12>(d_tab, m, w, h, pp, lds, k, s); break;
     }
     return launch_check("k_project_fmt_lds_many");
@@ -223,7 +242,7 @@ extern "C" {
 
 int stitch_image_bytes(int fmt, int w, int h, int pitch, int pitch2, size_t* bytes, size_t* bytes2) {
     if (!fmt_extents(fmt, w, h, pitch, pitch2, bytes, bytes2))
-        return fail(STITCH_ERR_ARG, "image_bytes: format %d (0 .. 5), size %d x %d or pitches (%d, %d) below a row", fmt, w, h, pitch, pitch2);
+        return fail(STITCH_ERR_ARG, "image_bytes: format %d (0 .. 5, 16 .. 19), size %d x %d or pitches (%d, %d) below a row", fmt, w, h, pitch, pitch2);
     return STITCH_OK;
 }
 
@@ -260,7 +279,7 @@ int stitch_dev_pack_many_u8(int fmt, int matrix, const uint8_t* const* d_planar,
 
 int stitch_rig_set_formats(stitch_rig* rig, int in_fmt, int out_fmt, int matrix) {
     if (!rig) return fail(STITCH_ERR_ARG, "rig_set_formats: null handle");
-    if (!fmt_ok(in_fmt) || !fmt_ok(out_fmt)) return fail(STITCH_ERR_ARG, "rig_set_formats: formats (%d, %d) outside 0 .. 5", in_fmt, out_fmt);
+    if (!fmt_ok(in_fmt) || !fmt_ok(out_fmt)) return fail(STITCH_ERR_ARG, "rig_set_formats: formats (%d, %d) outside 0 .. 5, 16 .. 19", in_fmt, out_fmt);
     if (matrix < 0 || matrix > 2) return fail(STITCH_ERR_ARG, "rig_set_formats: matrix %d outside 0 .. 2", matrix);
     rig->in_fmt = in_fmt;
     rig->out_fmt = out_fmt;
@@ -273,6 +292,13 @@ int stitch_rig_formats(const stitch_rig* rig, int* in_fmt, int* out_fmt, int* ma
     if (in_fmt) *in_fmt = rig->in_fmt;
     if (out_fmt) *out_fmt = rig->out_fmt;
     if (matrix) *matrix = rig->matrix;
+    return STITCH_OK;
+}
+
+int stitch_rig_input_form(const stitch_rig* rig, int frame, int* form) {
+    if (!rig || !form) return fail(STITCH_ERR_ARG, "rig_input_form: null argument");
+    if (frame < 0 || frame >= rig->n) return fail(STITCH_ERR_ARG, "rig_input_form: frame %d outside 0 .. %d", frame, rig->n - 1);
+    *form = rig->fmt_form.empty() ? STITCH_RIG_INPUT_NONE : rig->fmt_form[(size_t)frame];
     return STITCH_OK;
 }
 

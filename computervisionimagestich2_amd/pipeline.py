@@ -142,7 +142,7 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     (include/stitch_rig_seams.h): the single-set chain with given seams, the yardstick of a rig with fixed seams.
     crop: a pair ((x0, y0, w, h), mode) (include/stitch_rig_crop.h), applied with plain slicing: mode 1 the slice of the finished
     mosaic, mode 2 the finish pass on the slice of the unfinished one -- the single-set statement of a cropped rig.
-    formats: (in_fmt, out_fmt, matrix) (include/stitch_rig_formats.h), through the conversions on their own: the frames are
+    formats: (in_fmt, out_fmt, matrix) (include/stitch_rig_formats.h; the codes of include/stitch_rig_formats_yuv.h too), through the conversions on their own: the frames are
     capi.Images of in_fmt, unpacked first (capi.dev_unpack_many); the result is packed last (capi.dev_pack_many) and returned as a
     capi.Image of out_fmt at tight pitch.  A planar side stays a tensor -- the single-set statement of a rig with formats.
     residuals: dict(radius=r, domains=[one (ch, cw) uint8 device mask per step]) (include/stitch_rig_monitor.h): the chain also
