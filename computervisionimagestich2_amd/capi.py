@@ -223,6 +223,17 @@ SEAM_ANCHOR_SIGNATURES = _signatures(
     ("stitch_rig_last_seam_moved", i32, vp, i32, i32, vp),
 )
 
+# The same for include/stitch_rig_exposure_temporal.h, smoothed or fixed transfer statistics for a rig; tests/test_exposure_temporal_host.py
+# holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks them.)
+RIG_EXPOSURE_TEMPORAL_SIGNATURES = _signatures(
+    ("stitch_dev_transfer_given_many_u8", i32, vp, vp, i32, i32, i32, vp, i32, vp), ("stitch_dev_stats_filter_f32", i32, vp, i32, i32, vp, vp, vp, vp),
+    ("stitch_rig_set_exposure_smoothing", i32, vp, i32),
+    ("stitch_rig_clear_exposure_smoothing stitch_rig_reset_exposure_state stitch_rig_clear_fixed_exposure", i32, vp),
+    ("stitch_rig_prime_exposure_state stitch_rig_exposure_state stitch_rig_fix_exposure", i32, vp, vp, i32),
+    ("stitch_rig_exposure_smoothing stitch_rig_fixed_exposure", i32, vp, vp, vp), ("stitch_rig_last_used_stats", i32, vp, vp, sz, vp, vp),
+)
+EXPOSURE_KEEP_MAX = 255  # STITCH_EXPOSURE_KEEP_MAX
+
 # The same for include/stitch_collapse_sides.h, the level-0 collapse that reads one image per column block; tests/test_collapse_sides_host.py
 # holds it to that header.  (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the two.)
 COLLAPSE_SIDES_SIGNATURES = _signatures(
@@ -268,8 +279,9 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
-        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_formats_yuv.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h (likewise)
-        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) \
+        # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_formats_yuv.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h,
+        # stitch_rig_exposure_temporal.h (likewise)
+        for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) + list(RIG_EXPOSURE_TEMPORAL_SIGNATURES.items()) \
                 + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_FORMAT_YUV_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
@@ -1972,6 +1984,80 @@ class Rig(_Handle):
         _chk(lib().stitch_rig_last_seam_moved(self._h, int(set), int(step), C.byref(moved)))
         return moved.value
 
+    # ---- temporal exposure: include/stitch_rig_exposure_temporal.h (host only; the rig was made with exposure 1 or 2) ----
+    def _records(self, stats, what):
+        a = np.ascontiguousarray(np.asarray(stats.cpu() if hasattr(stats, "cpu") else stats, dtype=np.float32))
+        if a.size % 12:
+            raise ValueError(f"{what}: one record of 12 floats per step")
+        return a.reshape(-1, 12)
+
+    def set_exposure_smoothing(self, keep):
+        """stitch_rig_set_exposure_smoothing: from the next stitch() on every step's transfer applies filtered statistics
+        u = m + (keep / 256) * (p - m), p the step's state, carried from set to set across sequences and calls.  keep 0 .. 255.
+        Returns self."""
+        _chk(lib().stitch_rig_set_exposure_smoothing(self._h, int(keep)))
+        return self
+
+    def clear_exposure_smoothing(self):
+        """stitch_rig_clear_exposure_smoothing: forget the option and the state.  Returns self."""
+        _chk(lib().stitch_rig_clear_exposure_smoothing(self._h))
+        return self
+
+    def reset_exposure_state(self):
+        """stitch_rig_reset_exposure_state: forget the state, keep the option -- a scene cut.  Returns self."""
+        _chk(lib().stitch_rig_reset_exposure_state(self._h))
+        return self
+
+    def prime_exposure_state(self, stats):
+        """stitch_rig_prime_exposure_state: (n_steps, 12) float32, one valid record per step, becomes the state.  Returns self."""
+        a = self._records(stats, "prime_exposure_state")
+        _chk(lib().stitch_rig_prime_exposure_state(self._h, _p(a), a.shape[0]))
+        return self
+
+    def exposure_smoothing(self):
+        """stitch_rig_exposure_smoothing: (keep, has) -- keep None where no smoothing is set, has a list of one bool per step."""
+        keep, has = C.c_int(), (C.c_int32 * max(self.n_steps, 1))()
+        _chk(lib().stitch_rig_exposure_smoothing(self._h, C.byref(keep), has))
+        return (None if keep.value < 0 else keep.value), [bool(v) for v in has[:self.n_steps]]
+
+    def exposure_state(self):
+        """stitch_rig_exposure_state: (n_steps, 12) float32, the state as the last completed stitch() or a later prime left it."""
+        out = np.zeros((self.n_steps, 12), np.float32)
+        _chk(lib().stitch_rig_exposure_state(self._h, _p(out), self.n_steps))
+        return out
+
+    def fix_exposure(self, stats):
+        """stitch_rig_fix_exposure: (n_steps, 12) float32, one valid record per step, applied to every set from now on: nothing is
+        measured and the smoothing state rests.  Returns self."""
+        a = self._records(stats, "fix_exposure")
+        _chk(lib().stitch_rig_fix_exposure(self._h, _p(a), a.shape[0]))
+        return self
+
+    def clear_fixed_exposure(self):
+        """stitch_rig_clear_fixed_exposure: measured statistics again.  Returns self."""
+        _chk(lib().stitch_rig_clear_fixed_exposure(self._h))
+        return self
+
+    def fixed_exposure(self):
+        """stitch_rig_fixed_exposure: None, or the (n_steps, 12) float32 fixed statistics."""
+        n = C.c_int()
+        _chk(lib().stitch_rig_fixed_exposure(self._h, None, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, 12), np.float32)
+        _chk(lib().stitch_rig_fixed_exposure(self._h, _p(out), C.byref(n)))
+        return out
+
+    def last_used_stats(self):
+        """stitch_rig_last_used_stats: (n_sets, n_steps, 12) float32, what the apply passes of the last stitch() with smoothing or
+        fixed statistics read (n_sets = 0 where there is none)."""
+        n_sets, n_steps = C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_last_used_stats(self._h, None, 0, C.byref(n_sets), C.byref(n_steps)))
+        out = np.zeros((n_sets.value, n_steps.value, 12), np.float32)
+        if out.size:
+            _chk(lib().stitch_rig_last_used_stats(self._h, _p(out), out.size, C.byref(n_sets), C.byref(n_steps)))
+        return out
+
     def _stitch_fmt(self, sets, out, return_stats):
         """stitch() of a rig with a format set: stitch_dev_rig_stitch_fmt_u8."""
         in_fmt, out_fmt, _ = self.formats
@@ -2285,3 +2371,35 @@ def dev_transfer_many(srcs, tems, out=None, stats_form=2, keep_black=False, want
     _chk(lib().stitch_dev_transfer_many_u8(_ptr_table(srcs), _ptr_table(tems), _ptr_table(out), n, sw, sh, tw, th, int(stats_form), int(bool(keep_black)),
                                            _dp(stats), _dp(diag), _stream()))
     return (out,) + ((stats,) if want_stats else ()) + ((diag,) if want_diag else ()) if (want_stats or want_diag) else out
+
+
+# ---- temporal exposure: include/stitch_rig_exposure_temporal.h ------------------------------------------------------------------
+def dev_transfer_given_many(srcs, stats, out=None, keep_black=False):
+    """stitch_dev_transfer_given_many_u8: the colour transfer's apply pass with GIVEN statistics on same-size (3, H, W) uint8 device
+    tensors in one launch -- image i recoloured with stats[i], a (count, 12) float32 device tensor; out[i] may be srcs[i].  No
+    template and no float plane is involved.  Returns the outputs."""
+    import torch
+    srcs = [_timg(t) for t in srcs]
+    out = [torch.empty_like(t) for t in srcs] if out is None else list(out)
+    _, h, w = srcs[0].shape
+    if any(tuple(t.shape) != (3, h, w) or t.dtype != torch.uint8 for t in srcs + out) or len(out) != len(srcs):
+        raise ValueError("expected uint8 images of one size, and one output per image")
+    if not stats.is_cuda or stats.dtype != torch.float32 or not stats.is_contiguous() or tuple(stats.shape) != (len(srcs), 12):
+        raise ValueError("expected a contiguous (count, 12) float32 tensor of statistics on the HIP device")
+    _chk(lib().stitch_dev_transfer_given_many_u8(_ptr_table(srcs), _ptr_table(out), len(srcs), w, h, _dp(stats), int(bool(keep_black)), _stream()))
+    return out
+
+
+def dev_stats_filter(measured, keep, state, has, out=None):
+    """stitch_dev_stats_filter_f32: the first-order filter over the (count, 12) float32 device tensor `measured`, record after record;
+    state: (12,) float32 and has: (1,) int32 device tensors, read and rewritten.  Returns the (count, 12) used records (`out`, which
+    may be `measured`).  Enqueued on torch's current stream."""
+    import torch
+    out = torch.empty_like(measured) if out is None else out
+    for t, shape, dt in ((measured, None, torch.float32), (out, tuple(measured.shape), torch.float32), (state, (12,), torch.float32), (has, (1,), torch.int32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError("expected contiguous device tensors: measured and out (count, 12) float32, state (12,) float32, has (1,) int32")
+    if measured.dim() != 2 or measured.shape[1] != 12:
+        raise ValueError("measured: (count, 12)")
+    _chk(lib().stitch_dev_stats_filter_f32(_dp(measured), measured.shape[0], int(keep), _dp(state), _dp(has), _dp(out), _stream()))
+    return out

@@ -29,6 +29,7 @@
 #include "stitch_rig.h"
 #include "stitch_exposure.h"
 #include "stitch_rig_exposure.h"
+#include "stitch_rig_exposure_temporal.h"
 #include "stitch_calibrate.h"
 #include "stitch_rig_seams.h"
 #include "stitch_rig_crop.h"

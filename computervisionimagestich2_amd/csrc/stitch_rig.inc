@@ -30,6 +30,14 @@ struct stitch_rig {
     float* ex_stats = nullptr;            // 16 floats per set and step, set-major
     double* ex_sums = nullptr;            // form 2: per span of 6 * max_sets planes of the longest plane
     void* ex_table = nullptr;             // form 2: the span table (ExSpanEntry)
+    // ---- temporal exposure (include/stitch_rig_exposure_temporal.h; stitch_rig_exposure.inc): nothing below is at work in mode 0 ----
+    int et_keep = -1;                     // smoothing: the filter keeps et_keep / 256 of its state; -1: no smoothing
+    std::vector<float> et_state;          // ... its state between replays, 12 floats per step, and per step whether it has one
+    std::vector<int32_t> et_has;          //     (both empty: no step has; a replay takes them up and a completed one leaves them)
+    float* ex_used = nullptr;             // ... the records the apply passes read, laid out as ex_stats; from the first smoothed replay on
+    std::vector<float> et_fixed;          // fixed statistics, 12 floats per step (empty: none); they win over smoothing
+    std::vector<float> et_last_used;      // what the apply passes of the last replay with an option read: 12 floats per set and step
+    int et_last_sets = 0;
     // ---- fixed seams and coverage (include/stitch_rig_seams.h; stitch_rig_seams.inc) ----
     std::vector<stitch_seam> fixed;  // one record per step, or empty: content seams
     int cover_device = -1;           // the device of the coverage planes, -1: not computed yet
@@ -93,7 +101,7 @@ struct stitch_rig {
         if (cover) (void)hipFree(cover);
         if (mon_dom) (void)hipFree(mon_dom);
         if (mon_rec) (void)hipFree(mon_rec);
-        for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table})
+        for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table, (void*)ex_used})
             if (p) (void)hipFree(p);
         for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
         for (uint8_t* p : proj)
@@ -111,8 +119,15 @@ constexpr int kRigMaxSets = 16, kRigMaxImages = 65535;
 // call, valid for every sequence, since it names the rig's own buffers only -- and step k's transfer over the m sets in flight.
 int rig_ex_workspaces(stitch_rig* R);
 size_t rig_ex_table_bytes(const stitch_rig* R);
-void rig_ex_fill_tables(const stitch_rig* R, unsigned char* host);
-int rig_ex_transfer(stitch_rig* R, const unsigned char* d_tables, int k, int m, hipStream_t s);
+// include/stitch_rig_exposure_temporal.h: with fixed statistics the block holds the step's records and step k's transfer is one launch
+// that measures nothing; under smoothing it also holds the filter's states -- the ones the replay starts from go up in it, the
+// filter launches between a step's statistics and its apply pass rewrite them there, and rig_et_collect copies them back.
+void rig_ex_fill_tables(const stitch_rig* R, unsigned char* host, const std::vector<float>& state, const std::vector<int32_t>& has);
+int rig_ex_transfer(stitch_rig* R, unsigned char* d_tables, int k, int m, hipStream_t s);
+bool rig_et_fixed(const stitch_rig* R);
+bool rig_et_smoothed(const stitch_rig* R);
+int rig_et_workspaces(stitch_rig* R);
+int rig_et_collect(const stitch_rig* R, const unsigned char* d_tables, std::vector<float>* state, std::vector<int32_t>* has, hipStream_t s);
 
 // The crop of a rig that has one (stitch_rig_crop.inc): the full-canvas buffers its last step writes, and the copy of the rectangle
 // out of the m buffers of a sequence (the src entries of the table) to the caller's (the dst entries), one launch.
@@ -258,7 +273,7 @@ int rig_workspaces(stitch_rig* R) {
     for (int k = 0; k + 1 < ns; ++k) R->mosaic_bytes = std::max(R->mosaic_bytes, align256((size_t)3 * R->steps[k].geom.cw * R->steps[k].geom.ch));
     for (int b = 0; b < std::min(2, ns - 1); ++b)
         if (!R->mosaic[b]) HIPCHK(hipMalloc((void**)&R->mosaic[b], (size_t)R->max_sets * R->mosaic_bytes));
-    if (R->ex.mode && ns) {
+    if (R->ex.mode && ns && !rig_et_fixed(R)) {  // (fixed statistics need none of it: rig_et_workspaces takes it once they are cleared)
         const int rc = rig_ex_workspaces(R);
         if (rc) return rc;
     }
@@ -470,6 +485,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
             if (ranges_overlap(d_out[j], out_bytes, d_out[i], out_bytes)) return fail(STITCH_ERR_ARG, "rig_stitch: the outputs of sets %d and %d overlap", j, i);
     }
     if ((rc = rig_workspaces(R))) return rc;
+    if ((rc = rig_et_workspaces(R))) return rc;
     if (cropped && (rc = rig_crop_workspace(R))) return rc;
     if ((fin || fout) && (rc = rig_fmt_workspace(R, fc, n_sets))) return rc;
     hipStream_t s = as_stream(stream);
@@ -497,6 +513,19 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         R->sa_has = false;
     }
     if (pathed && (rc = rig_sp_prepare(R, s))) return rc;
+    // include/stitch_rig_exposure_temporal.h: the filter's states are the replay's from here on, and the rig's again once it has
+    // completed with every set's status STITCH_OK; a failed call leaves no used statistics behind
+    const bool ex_fixed = ns > 0 && rig_et_fixed(R), smoothed = ns > 0 && rig_et_smoothed(R);
+    std::vector<float> et_state, h_used(smoothed ? (size_t)16 * ns * n_sets : 0);
+    std::vector<int32_t> et_has;
+    if (R->ex.mode) {
+        R->et_last_used.clear();
+        R->et_last_sets = 0;
+    }
+    if (smoothed) {
+        et_state.swap(R->et_state);
+        et_has.swap(R->et_has);
+    }
     std::vector<int32_t> h_paths(pathed ? R->sp_rows * n_sets : 0);
     std::vector<uint64_t> h_pcost(pathed ? (size_t)ns * n_sets : 0), h_moved(pathed ? (size_t)ns * n_sets : 0);
     for (int i = 0; i < n_sets; ++i) set_status[i] = STITCH_OK;
@@ -534,11 +563,11 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
     if (ex_bytes) {
         up.resize(ex_at + ex_bytes);
         std::memcpy(up.data(), tab.data(), tab_bytes);
-        rig_ex_fill_tables(R, up.data() + ex_at);
+        rig_ex_fill_tables(R, up.data() + ex_at, et_state, et_has);
     }
     const size_t up_bytes = ex_bytes ? up.size() : tab_bytes;
     const void* up_from = ex_bytes ? (const void*)up.data() : (const void*)tab.data();
-    std::vector<float> h_stats(stats ? (size_t)16 * ns * n_sets : 0);  // 16 floats per set and step, as on the device
+    std::vector<float> h_stats(stats && !ex_fixed ? (size_t)16 * ns * n_sets : 0);  // 16 floats per set and step, as on the device
     if (fc) rig_fmt_tables(R, fc, tab.data(), n_sets);
     PanoArena A(s);
     unsigned char* d_up = nullptr;
@@ -631,6 +660,8 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         // the sequence's statistics leave the device in one copy, behind its last transfer; the next sequence overwrites them
         if (!h_stats.empty())
             HIPCHK(hipMemcpyAsync(h_stats.data() + (size_t)16 * ns * set0, R->ex_stats, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
+        if (smoothed)  // ... and so do the records its apply passes read
+            HIPCHK(hipMemcpyAsync(h_used.data() + (size_t)16 * ns * set0, R->ex_used, sizeof(float) * 16 * ns * m, hipMemcpyDeviceToHost, s));
         if (monitored && (rc = rig_mon_collect(R, h_mon.data() + mon_words * set0, m, s))) return rc;  // likewise
         if (pathed && (rc = rig_sp_collect(R, h_paths.data() + R->sp_rows * set0, h_pcost.data() + (size_t)ns * set0, h_moved.data() + (size_t)ns * set0, m, set0 + m == n_sets, s)))
             return rc;
@@ -642,8 +673,20 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         for (int i = 0; i < n_sets; ++i) set_status[i] = O.hip_fault;
         return fail(O.hip_fault, "rig_stitch: %s", O.hip_text.c_str());
     }
+    if (smoothed && (rc = rig_et_collect(R, d_up + ex_at, &et_state, &et_has, s))) return rc;  // behind the last sequence's filters
     HIPCHK(hipStreamSynchronize(s));  // the finish pass of the last sequence (read_all waited for the steps only)
     for (size_t j = 0; j < h_stats.size() / 16; ++j) std::memcpy(stats + 12 * j, h_stats.data() + 16 * j, sizeof(float) * 12);
+    if (ex_fixed || smoothed) {  // include/stitch_rig_exposure_temporal.h: what the apply passes read, kept once the replay has completed
+        R->et_last_used.resize((size_t)12 * ns * n_sets);
+        for (size_t j = 0; j < (size_t)ns * n_sets; ++j)
+            std::memcpy(R->et_last_used.data() + 12 * j, ex_fixed ? R->et_fixed.data() + 12 * (j % ns) : h_used.data() + 16 * j, sizeof(float) * 12);
+        R->et_last_sets = n_sets;
+        if (ex_fixed && stats) std::memcpy(stats, R->et_last_used.data(), sizeof(float) * R->et_last_used.size());  // nothing was measured
+    }
+    if (smoothed && std::all_of(set_status, set_status + n_sets, [](int32_t v) { return v == STITCH_OK; })) {
+        R->et_state.swap(et_state);
+        R->et_has.swap(et_has);
+    }
     if (fc) {  // include/stitch_rig_formats_yuv.h: the form each frame index took, kept once the replay has completed
         R->fmt_form.assign((size_t)n, (char)STITCH_RIG_INPUT_NONE);
         if (fin)

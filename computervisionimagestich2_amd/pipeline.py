@@ -6,6 +6,8 @@ Nothing here computes pixels: every per-pixel operation is a HIP kernel reached 
 """
 import math
 
+import numpy as np
+
 from . import capi
 
 SEED_MAP = (1.0, 0.002, 1e-6, -2048.0, -0.001, 1.0, 5e-7, 1.5)  # config-2 backward map, SURVEY.md 8(d)
@@ -126,8 +128,50 @@ def exposure_match(proj_dst, proj_src, result, exposure, keep_black=True, stats_
     return proj_dst
 
 
+def exposure_stats_valid(m):
+    """include/stitch_rig_exposure_temporal.h: a record the filter takes up -- twelve finite values, the six sds above 0."""
+    m = np.asarray(m, np.float32)
+    return bool(np.isfinite(m).all() and (m[[3, 4, 5, 9, 10, 11]] > 0).all())
+
+
+def exposure_filter(m, keep, p):
+    """The first-order filter of include/stitch_rig_exposure_temporal.h on ONE record, in float32 with every operation rounded:
+    m the measured twelve statistics, p the state (12 floats) or None -> (used, state).  Not valid: (m, p).  Valid, no state:
+    (m, m).  Valid, a state: u = m + (keep / 256) * (p - m), (u, u)."""
+    m = np.asarray(m, np.float32).copy()
+    if not exposure_stats_valid(m):
+        return m, p
+    if p is None:
+        return m, m.copy()
+    kf = np.float32(int(keep)) / np.float32(256)
+    with np.errstate(all="ignore"):
+        u = (m + (kf * (np.asarray(p, np.float32) - m).astype(np.float32)).astype(np.float32)).astype(np.float32)
+    return u, u.copy()
+
+
+def exposure_match_temporal(proj_dst, proj_src, result, exposure, keep_black, option, temporal, k):
+    """exposure_match with the statistics it applies taken from `option` (stitch_chain's exposure_temporal) instead of measured:
+    step k's record of fixed=, or the measured twelve filtered against temporal["state"][k].  Updates temporal in place."""
+    import torch
+    if option.get("fixed") is not None:
+        u = np.asarray(option["fixed"][k], np.float32).reshape(12).copy()
+    else:
+        keep = int(option["keep"])
+        if not 0 <= keep <= 255:
+            raise ValueError(f"keep {keep} (0 .. 255)")
+        s12 = torch.zeros(12, dtype=torch.float32, device=proj_dst.device)
+        capi.dev_transfer(proj_dst, proj_src if exposure == 1 else result, out=torch.empty_like(proj_dst), stats=s12, stats_form=2, keep_black=keep_black)
+        m = s12.cpu().numpy()
+        p = temporal["state"][k]
+        u, temporal["state"][k] = exposure_filter(m, keep, None if p is None else np.asarray(p, np.float32).reshape(12))
+        temporal["measured"][k] = m
+    temporal["used"][k] = u
+    capi.dev_transfer_given_many([proj_dst], torch.from_numpy(u.reshape(1, 12)).to(proj_dst.device), out=[proj_dst], keep_black=keep_black)
+    return proj_dst
+
+
 def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None,
-                 residuals=None, seam_paths=None):
+                 residuals=None, seam_paths=None, exposure_temporal=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -159,13 +203,21 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     cap= in the dict (include/stitch_seam_anchor.h) every step's finder takes the temporal term towards its anchor and `found`
     holds (path, cost, moved) per step; a caller that feeds a set's found paths into the next set's call as anchors states a rig
     that anchors per set.
+    exposure_temporal: dict(keep=0 .. 255, state=None or [per step 12 floats or None]) or dict(fixed=[per step 12 floats])
+    (include/stitch_rig_exposure_temporal.h), with exposure 1 or 2: the statistics a step's transfer applies are not the ones it
+    measures.  keep/state: the step measures with capi.dev_transfer into a scratch output, filters the twelve statistics against
+    the step's state by exposure_filter (numpy float32) and applies the result with capi.dev_transfer_given_many; fixed: the step
+    applies the given record and measures nothing.  The return value grows by a last element, dict(state=[per step 12 floats or
+    None], measured=[...], used=[...]) (measured None per step with fixed=): a caller that feeds a set's state into the next
+    set's call states a rig that smooths.  With exposure_temporal=None the return value and every byte stay as they are.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
     if formats is not None:
         in_fmt, out_fmt, matrix = formats
         if in_fmt != capi.PIX_PLANAR:
             used_frames = {steps[0]["start"]} | {st["src"] for st in steps}  # the rig reads no other frame either
             frames = [capi.dev_unpack_many([f], matrix)[0] if i in used_frames else None for i, f in enumerate(frames)]
-        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop, residuals=residuals, seam_paths=seam_paths)
+        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop, residuals=residuals, seam_paths=seam_paths,
+                              exposure_temporal=exposure_temporal)
         result, *extras = result if isinstance(result, tuple) else (result,)
         result = result if out_fmt == capi.PIX_PLANAR else capi.dev_pack_many([result], out_fmt, matrix)[0]
         return (result, *extras) if extras else result
@@ -191,6 +243,16 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
             raise ValueError("one path per step")
         if seam_paths.get("anchors") is not None and len(seam_paths["anchors"]) != len(steps):
             raise ValueError("one anchor (or None) per step")
+    temporal = None
+    if exposure_temporal is not None:
+        if exposure not in (1, 2):
+            raise ValueError("exposure_temporal needs exposure 1 or 2")
+        fixed, state = exposure_temporal.get("fixed"), exposure_temporal.get("state")
+        if (fixed is None) == ("keep" not in exposure_temporal):
+            raise ValueError("exposure_temporal: either keep= (with state=) or fixed=")
+        if len(fixed if fixed is not None else state if state is not None else steps) != len(steps):
+            raise ValueError("one record (or None) per step")
+        temporal = dict(state=list(state) if state is not None else [None] * len(steps), measured=[None] * len(steps), used=[None] * len(steps))
     result = projected(steps[0]["start"])
     used, records, found = [], [], []
     for k, st in enumerate(steps):
@@ -202,7 +264,10 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
                 plans[key] = plan
         elif plan in used:  # the same workspace twice in one chain: its seam record must be read before it is overwritten
             plan.status()
-        if exposure:
+        if temporal is not None:
+            exposure_match_temporal(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black, exposure_temporal,
+                                    temporal, k)
+        elif exposure:
             exposure_match(projected(st["src"]), projected(st["mosaic_src"]) if exposure == 1 else None, result, exposure, keep_black)
         if residuals is not None:
             records.append(capi.dev_pairs_residual([(projected(st["src"]), st["p"], st["offx"], st["offy"], result, st["ox"], st["oy"])], st["cw"], st["ch"],
@@ -253,7 +318,7 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
         if plans is None:
             for plan in used:
                 plan.close()
-    extras = () if seam_paths is None else (found,)
+    extras = (() if seam_paths is None else (found,)) + (() if temporal is None else (temporal,))
     if residuals is not None:
         import torch
         return (result, (torch.stack(records) if records else torch.empty((0, capi.residual_words(residuals["radius"])), dtype=torch.int64, device=result.device)),
