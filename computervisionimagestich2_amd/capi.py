@@ -32,6 +32,7 @@ class StitchError(RuntimeError):
 
 OK, ERR_ARG, ERR_EMPTY_MIDROW, ERR_ZERO_OVERLAP, ERR_PYRAMID, ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6
 ERR_NO_MAP, ERR_CAPACITY = -7, -8  # the whole-panorama calls (include/stitch_panorama.h)
+CALL_MASK_KEEP = 64  # STITCH_CALL_MASK_KEEP (include/stitch_mask_keep.h): a bit of stitch_plan_call_forms beside the STITCH_FAST_* values 1 .. 32
 
 
 class BlendOpts(C.Structure):
@@ -279,6 +280,8 @@ def lib():
             L.stitch_plan_mask_row_counts.restype, L.stitch_plan_mask_row_counts.argtypes = i32, [vp, vp]
         if hasattr(L, "stitch_plan_index_counts"):  # include/stitch_index_plane.h (likewise)
             L.stitch_plan_index_counts.restype, L.stitch_plan_index_counts.argtypes = i32, [vp, vp]
+        if hasattr(L, "stitch_plan_mask_keep_counts"):  # include/stitch_mask_keep.h (likewise)
+            L.stitch_plan_mask_keep_counts.restype, L.stitch_plan_mask_keep_counts.argtypes = i32, [vp, vp]
         # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_formats_yuv.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h,
         # stitch_rig_exposure_temporal.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) + list(RIG_EXPOSURE_TEMPORAL_SIGNATURES.items()) \
@@ -1242,7 +1245,7 @@ class Plan(_Handle):
     def call_forms(self, n_pairs=1):
         """stitch_plan_call_forms: the per-call forms ("source_fused", "fused_sweep") a call with n_pairs pairs runs."""
         f = lib().stitch_plan_call_forms(self._h, int(n_pairs))
-        return {n for b, n in ((2, "source_fused"), (4, "fused_sweep")) if f & b}
+        return {n for b, n in ((2, "source_fused"), (4, "fused_sweep")) if f & b}  # (and CALL_MASK_KEEP: mask_keep_form)
 
     @property
     def workspace_bytes(self):
@@ -1364,6 +1367,17 @@ class Plan(_Handle):
         out = (C.c_uint32 * 3)()
         _chk(lib().stitch_plan_index_counts(self._h, out))
         return tuple(int(v) for v in out)
+
+    def mask_keep_counts(self):
+        """-> (computed, stood): slots whose mask planes the plan's last call computed, slots whose mask pyramid stood from an earlier
+        call with the same seam record and form (stitch_plan_mask_keep_counts)."""
+        out = (C.c_uint32 * 2)()
+        _chk(lib().stitch_plan_mask_keep_counts(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def mask_keep_form(self, n_pairs=1):
+        """A call with n_pairs pairs is of a form under which mask pyramids stand (stitch_plan_call_forms, STITCH_CALL_MASK_KEEP)."""
+        return bool(lib().stitch_plan_call_forms(self._h, int(n_pairs)) & CALL_MASK_KEEP)
 
     def src_run_counts(self):
         """-> (outside, no patch, 1..64 patches, general): 64 x 64 tiles of the index planes the last call's causal x sweep gathered

@@ -206,6 +206,48 @@ __global__ __launch_bounds__(64) void k_index_keys(PairArgs<PX> pa, int n, Index
 __global__ __launch_bounds__(64) void k_index_forget(IndexKey* __restrict__ keys, int n) {
     if ((int)threadIdx.x < n) keys[threadIdx.x].valid = 0u;
 }
+// What the mask pyramid in a plan's slot was computed from (include/stitch_mask_keep.h): the seam record's step and the call's form word
+// (mask_keep_word, stitch_call_form.h).  The mask plane of every level is a function of exactly these and the plan; no pixel reaches
+// it except through the seam scan's integers.  Kept on the device for the same reason as IndexKey.
+constexpr int WF_STAND_WORD = 8;  // Wavefront::sticky[WF_STAND_WORD] (k_fused_sweep.inc): bit i set = the mask pyramid of slot i stands in this call; 0 in a band's block
+struct MaskKey {
+    unsigned long long thr;  // SeamDev::thr by bit pattern
+    int branch, start;
+    unsigned form;
+    unsigned valid;  // 0 at creation and after stitch_plan_clear_fault
+};
+// Behind the launch that writes the call's seam records, one wavefront: lane i compares slot i's record with the call's SeamDev and form
+// word, leaves todo[i] = 1 where the slot's mask planes have to be computed and 0 where they stand, and takes the record over.  A pyramid
+// stands only under an identical word that has MK_KEEP_OK, and never where the scan failed (status != 0: the record is forgotten).
+// A fused sweep that gave up on a hand-off leaves planes nobody may trust, and a healthy call may be queued right behind it: the count
+// of timed-out waits (sticky[0], which only grows) is compared with the count this kernel saw last (counts[2]); where it has grown, no
+// record of the plan holds, in this call or for the slots it does not use.
+// sticky[WF_STAND_WORD]: the same answer as one word, bit i set = slot i stands, for k_vv_xbyf; counts: slots computed, slots that stood.
+__global__ __launch_bounds__(64) void k_mask_keys(const SeamDev* __restrict__ seam, int n, int cap, unsigned form, MaskKey* __restrict__ keys,
+                                                  unsigned* __restrict__ todo, unsigned* __restrict__ sticky, unsigned* __restrict__ counts) {
+    const int i = threadIdx.x;
+    const bool in = i < n;
+    const unsigned timeouts = sticky ? sticky[0] : 0u;
+    const bool trusted = timeouts == counts[2];
+    bool same = false;
+    if (in) {
+        const SeamDev sd = seam[i];
+        MaskKey k;
+        k.thr = (unsigned long long)__double_as_longlong(sd.thr);
+        k.branch = sd.branch, k.start = sd.start;
+        k.form = form, k.valid = sd.status == 0 ? 1u : 0u;
+        const MaskKey r = keys[i];
+        same = trusted && (form & MK_KEEP_OK) != 0 && k.valid != 0 && r.valid != 0 && r.form == form && r.thr == k.thr && r.branch == k.branch && r.start == k.start;
+        if (!same) keys[i] = k;
+    } else if (!trusted && i < cap)
+        keys[i].valid = 0u;
+    if (i < MAXB) todo[i] = in && same ? 0u : 1u;
+    const unsigned long long stood = __ballot(in && same);
+    if (i == 0) {
+        counts[0] = (unsigned)(n - __popcll(stood)), counts[1] = (unsigned)__popcll(stood), counts[2] = timeouts;
+        if (sticky) sticky[WF_STAND_WORD] = (unsigned)stood;
+    }
+}
 // the preset of the `zi` bytes ("outside" until k_src_index finds a sample) of the slots whose plane is computed in this call
 __global__ __launch_bounds__(256) void k_zi_preset(uint8_t* __restrict__ flags, int per_slot, const unsigned* __restrict__ todo) {
     if (!todo[blockIdx.y]) return;

@@ -181,8 +181,20 @@ __global__ __launch_bounds__(64, (MODE == 0 && !STAMP) ? 3 : 2) void k_vv_xbyf(f
     bool dead = false;
     while (!dead) {
         unsigned q = 0;
-        if (lane == 0) q = atomicAdd(wf.counter, 1u);
-        q = __builtin_amdgcn_readfirstlane(__shfl(q, 0, 64));  // provably wave-uniform: band, plane and every branch on them stay scalar
+        // A mask plane that stands (mask_stands, k_sweeps.inc): its bands are claimed and dropped, here in the claim itself.  The slots'
+        // bits come through a pointer the kernel holds anyway (word WF_STAND_WORD behind the sticky count; one more scalar argument costs
+        // this instance its tier).  Nobody waits for a dropped band: only band (R+1, p) polls the granules of band (R, p), it is dropped
+        // under the same bit, and the bit was written by a kernel earlier in stream order (k_mask_keys) -- it cannot change while this
+        // launch runs.
+        for (;;) {
+            if (lane == 0) q = atomicAdd(wf.counter, 1u);
+            q = __builtin_amdgcn_readfirstlane(__shfl(q, 0, 64));  // provably wave-uniform: band, plane and every branch on them stay scalar
+            if constexpr (MODE == 0 && !BANDED) {
+                const unsigned pc = q % (unsigned)wf.NP;
+                if (q < nbands && pc % 7u == 6u && ((__builtin_amdgcn_readfirstlane(wf.sticky[WF_STAND_WORD]) >> (pc / 7u)) & 1u) != 0) continue;
+            }
+            break;
+        }
         if (q >= nbands) break;
         const int R = (int)(q / wf.NP), p = (int)(q % wf.NP);  // every plane's band R before any band R+1
         const int r0 = R * TS, nrows = min(TS, h - r0);

@@ -41,9 +41,10 @@ __global__ __launch_bounds__(64) void k_deriche(float* __restrict__ data, float*
 // yoff / soff: level row of the destination's / source's row 0 (0 for a whole level; a row band of a split pair passes its
 // first rows, and the LEVEL's heights as h, h2, so that the overlap weights are the level's)
 __global__ __launch_bounds__(256) void k_decimate(const float* __restrict__ src, int w, int h, int spitch, size_t sps,
-                                                  float* __restrict__ dst, int w2, int h2, int dpitch, size_t dps, int yoff, int soff) {
+                                                  float* __restrict__ dst, int w2, int h2, int dpitch, size_t dps, int yoff, int soff,
+                                                  const unsigned* __restrict__ keep = nullptr) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, pl = blockIdx.z;
-    if (x >= dpitch) return;
+    if (x >= dpitch || mask_stands(keep, pl)) return;  // (a mask plane that stands is left as an earlier call wrote it)
     float out = 0.f;
     if (x < w2) {
         const Taps tx = make_taps(x, w, w2), ty = make_taps(y + yoff, h, h2);

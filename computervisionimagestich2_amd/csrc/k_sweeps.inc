@@ -50,7 +50,16 @@ struct MaskL0 {
     float* side;          // [pairs][pitch]: the x-blurred mask row
     int h;                // level height = lines per plane
     int enabled;
+    const unsigned* keep; // any level: the slots' mask_todo words (k_mask_keys, mask_stands), or nullptr
 };
+// The mask pyramid of a slot stands (k_mask_keys, k_compose.inc): an earlier call of the same form and the same seam record wrote plane 6
+// of every G_l >= 1 and its row-repeat flags, and this call leaves them as they are, bit for bit.  Every kernel between G_l and G_{l+1}
+// drops the work of such a plane under the SAME word, which a kernel earlier in stream order wrote: the scratch of that plane (T, the sweep
+// states, its T flags, the side row) is then neither written nor read by anyone.  todo == nullptr (a band, a call that does not take
+// part): every plane is computed.
+__device__ __forceinline__ bool mask_stands(const unsigned* __restrict__ todo, long plane) {
+    return todo != nullptr && plane % 7 == 6 && todo[plane / 7] == 0u;
+}
 __device__ __forceinline__ float mask_step(const SeamDev& sd, int x) {
     return sd.branch == 0 ? ((double)x < sd.thr ? 1.f : 0.f) : (x >= sd.start ? 1.f : 0.f);
 }
@@ -157,6 +166,9 @@ __global__ __launch_bounds__(64) void k_vv_x_fwd(const float* __restrict__ in, f
     float* ob = out + (size_t)line0 * pitch;
     const int ntiles = (w + TS - 1) / TS;
     const bool live = lane < nrows && line < lines;
+    // A block whose lines all belong to mask planes that stand has nothing to do (mask_stands): its plane with per-plane bands, every
+    // line's plane with stacked lines -- one wave-uniform answer; a block that mixes planes runs as before
+    if (mk.keep != nullptr && (bd.nr > 0 ? mask_stands(mk.keep, plane) : __all(line >= lines || mask_stands(mk.keep, line / mk.h)))) return;
     // Row-repeat flags of this level's mask plane (mask_rows; per-plane bands): a flagged tile of a band below the first was not stored
     // and its 64 rows are taken from row 0 of the plane -- an address select, the loads stay unconditional.  At a fused level (T flags:
     // k_vv_xbyf knows the flags too) a band whose tiles are ALL flagged has nothing to do here, like the level-0 step below its first band.
@@ -430,6 +442,8 @@ __global__ __launch_bounds__(64) void k_vv_x_bwd(float* __restrict__ data, int w
     const int nrows = bd.nr > 0 ? min(TS, bd.h - band_y0) : TS;
     const long line0 = bd.nr > 0 ? plane * bd.h + band_y0 : blk * TS, line = line0 + lane;
     float* side_row = nullptr;  // level-0 mask plane: row 0 of this block is also left in the side buffer
+    // (as in k_vv_x_fwd: nothing to do where every line is a line of a mask plane that stands)
+    if (mk.keep != nullptr && (bd.nr > 0 ? mask_stands(mk.keep, plane) : __all(line >= lines || mask_stands(mk.keep, line / mk.h)))) return;
     if (mk.enabled) {
         if (plane % 7 == 6) {
             if (band_y0 >= TS) return;
@@ -639,7 +653,7 @@ template <bool XCH = false>
 __global__ __launch_bounds__(64) void k_vv_y_fwd(float* __restrict__ data, int h, int pitch, size_t ps, VVK k,
                                                   double* __restrict__ state, MaskL0 mk, const double* __restrict__ resume, int x_base = 0) {
     const int xl = (blockIdx.x * WAVE + threadIdx.x) * 2, x = XCH ? xl + x_base : xl;
-    if (x >= pitch) return;
+    if (x >= pitch || mask_stands(mk.keep, blockIdx.y)) return;  // (a mask plane that stands: nothing is touched)
     const int sp = XCH ? (int)gridDim.x * YCOLS : pitch, sx = XCH ? xl : x;  // the state arrays' pitch and this lane's place in them
     float* p = data + blockIdx.y * ps + x;
     // level-0 mask plane: every input row is the one x-blurred row kept in the side buffer (row stride 0)
@@ -678,6 +692,7 @@ __global__ __launch_bounds__(64) void k_vv_y_fwd(float* __restrict__ data, int h
 __global__ __launch_bounds__(64) void k_vv_y_fwd1(float* __restrict__ data, int h, int pitch, size_t ps, VVK k,
                                                    double* __restrict__ state, MaskL0 mk, const double* __restrict__ resume) {
     const int x = blockIdx.x * WAVE + threadIdx.x;  // pitch is a multiple of 64
+    if (mask_stands(mk.keep, blockIdx.y)) return;  // (a mask plane that stands: nothing is touched)
     float* p = data + blockIdx.y * ps + x;
     const bool side = mk.enabled && (blockIdx.y % 7 == 6);
     const float* src = side ? mk.side + (size_t)(blockIdx.y / 7) * pitch + x : p;
@@ -801,8 +816,13 @@ __global__ __launch_bounds__(128) void k_vv_y_bwd_dec(const float* __restrict__ 
                                                       VVK k, const double* __restrict__ state, float* __restrict__ dst,
                                                       int w2, int h2, int dpitch, size_t dps, ZeroTiles zt,
                                                       const double* __restrict__ resume, double* __restrict__ state_out, int wh, int wh2,
-                                                      int x_base = 0, int fill_l0 = 0, ZeroTiles gz = ZeroTiles{}, ZeroTiles mr = ZeroTiles{}) {
+                                                      int x_base = 0, int fill_l0 = 0, ZeroTiles gz = ZeroTiles{}, ZeroTiles mr = ZeroTiles{},
+                                                      const unsigned* __restrict__ keep = nullptr) {
     static_assert(!(XCH && ODD), "column chunks: even widths");
+    // keep (mask_stands): the workgroups of a mask plane that stands return before they touch anything -- plane 6 of G_{l+1}, its `mr`
+    // bytes and whatever the memory holds where they say "not stored" are an earlier call's, left bit for bit (a mask plane has neither
+    // G column flags nor a state_out)
+    if (mask_stands(keep, blockIdx.y)) return;
     // wh, wh2: the heights the decimation's overlap weights are taken from (CImg.h:29557-29575 weights by the LEVEL's
     // heights): h, h2 for a whole level; for a row band of a split pair the level's, not the band's (the quotient is the same
     // number, but (x*32 + y*32)/64 and (x*96 + y*96)/192 round differently)

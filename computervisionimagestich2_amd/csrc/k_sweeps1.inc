@@ -34,6 +34,7 @@ template <int NST>
 __global__ __launch_bounds__(64) void k_vv_y_fwd1s(float* __restrict__ data, int h, int pitch, size_t ps, VVK k,
                                                     double* __restrict__ state, MaskL0 mk, const double* __restrict__ resume) {
     const int x = blockIdx.x * WAVE + threadIdx.x;  // pitch is a multiple of 64
+    if (mask_stands(mk.keep, blockIdx.y)) return;  // (a mask plane that stands: nothing is touched)
     // level-0 mask plane: every input row is the one x-blurred row kept in the side buffer (row step 0)
     const bool side = mk.enabled && (blockIdx.y % 7 == 6);
     const float* sp = side ? mk.side + (size_t)(blockIdx.y / 7) * pitch : data + blockIdx.y * ps;
@@ -210,6 +211,8 @@ __global__ __launch_bounds__(192) void k_vv_x_m(const float* __restrict__ in, fl
     bool gen_mask = false;       // FWD: this block's lines are rows of a level-0 mask plane, generated instead of loaded
     float* side_row = nullptr;  // !FWD: row 0 of the mask plane's first band is also left in the side buffer (see MaskL0)
     SeamDev sd;
+    // (as in k_vv_x_fwd: nothing to do where every line is a line of a mask plane that stands; the whole workgroup, before any barrier)
+    if (mk.keep != nullptr && (bd.nr > 0 ? mask_stands(mk.keep, plane) : __all(line >= lines || mask_stands(mk.keep, line / mk.h)))) return;
     if (mk.enabled && plane % 7 == 6) {
         if (band_y0 >= TS) return;  // rows 64.. of the step are copies of rows 0..63 and are never read (whole workgroup)
         if (FWD) {
@@ -372,6 +375,7 @@ __global__ __launch_bounds__(192) void k_vv_y_m(float* __restrict__ data, int h,
     __shared__ __attribute__((aligned(16))) float ring[YM_SLOTS][YM_ROWS][WAVE];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int x0 = blockIdx.x * WAVE;  // pitch is a multiple of 64
+    if (mask_stands(mk.keep, blockIdx.y)) return;  // (a mask plane that stands: nothing is touched; the whole workgroup, before any barrier)
     float* p = data + blockIdx.y * ps + x0;
     // level-0 mask plane, causal sweep: every input row is the one x-blurred row kept in the side buffer (row stride 0)
     const bool side = FWD && mk.enabled && (blockIdx.y % 7 == 6);
@@ -568,9 +572,11 @@ typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));  // 16 bytes
 template <bool ODD>
 __global__ __launch_bounds__(D7_THREADS) void k_vv_y_bwd_dec7(const float* __restrict__ data, int w, int h, int pitch, size_t ps, VVK k,
                                                              const double* __restrict__ state, float* __restrict__ dst, int w2, int h2,
-                                                             int dpitch, size_t dps, unsigned long long* dbg = nullptr, int dbg_mode = 0) {
+                                                             int dpitch, size_t dps, unsigned long long* dbg = nullptr, int dbg_mode = 0,
+                                                             const unsigned* __restrict__ keep = nullptr) {
     __shared__ __attribute__((aligned(16))) float ring[D7_SLOTS][YCH][YCOLS];
     __shared__ int cnt_loaded, cnt_chain[2], cnt_cons[D7_CONS];
+    if (mask_stands(keep, blockIdx.y)) return;  // (as k_vv_y_bwd_dec: plane 6 of G_{l+1} stays as an earlier call wrote it)
     // Which wavefront plays which stage: the wavefronts of a workgroup go to the CU's four SIMDs in rotation (0, 2, 1, 3, 0, ...
     // from some start: scripts/experiments/simd_place.hip), so hardware wavefronts i and i + 4 share a SIMD and number 3 has one to
     // itself.  A chain issues one dependent instruction at a time; next to a consumer -- a wavefront full of independent vector

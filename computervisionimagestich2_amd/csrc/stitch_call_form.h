@@ -605,6 +605,45 @@ inline CallForm call_form(const PlanShape& s, int n, bool src, bool a_dense) {
     return c;
 }
 
+// ---- the mask pyramid that stands (include/stitch_mask_keep.h) --------------------------------------------------------------------
+// The mask planes of G_1 .. G_{l_end} of a slot, their row-repeat flags and the level-0 blur handed down to them are a function of the
+// slot's seam record, the plan and the call's FORM: which tiles of a mask plane are stored at all (under mr_out a flagged tile is not, and
+// the memory keeps what an earlier call left), which flags exist.  The form word states that part of a call; a slot's pyramid stands only
+// under the word it was written under, and only where the word has MK_KEEP_OK: every kernel between G_l and G_{l+1} that the call's
+// LevelForms select knows the skip (mask_stands, k_sweeps.inc).  A call without MK_KEEP_OK computes every mask plane and, because it
+// stores everything its own form stores, takes the slots' records over with its own word -- under which nothing ever stands.
+constexpr uint32_t MK_KEEP_OK = 1u, MK_MASK_L0 = 2u;
+constexpr int MK_LEVEL_BIT = 2, MK_LEVELS = 8, MK_LEND_BIT = MK_LEVEL_BIT + 3 * MK_LEVELS;  // three bits per level below MK_LEVELS, then l_end (< 32)
+constexpr uint32_t mask_keep_level_bits(bool mr_out, bool mr_in, bool fill_mask) { return (mr_out ? 1u : 0u) | (mr_in ? 2u : 0u) | (fill_mask ? 4u : 0u); }
+// REDUCE of a level runs only kernels that know the skip: the batch's k_vv_x_fwd + k_vv_xbyf MODE 0 (plain and STAMP) + k_vv_y_bwd_dec, or
+// the separate sweeps -- k_vv_x_fwd / k_vv_x_bwd or k_vv_x_m, k_vv_y_fwd / k_vv_y_fwd1 / k_vv_y_fwd1s / k_vv_y_m, k_vv_y_bwd_dec /
+// k_vv_y_bwd_dec7 or k_vv_y_bwd + k_decimate: the coarser levels of a large batch take the few-workgroup forms too (a copy in place of
+// an x sweep and k_vv_y_bwd touch the scratch T alone).  Not the five-wavefront sweep of one pair in flight (k_vv_xby_m), not the
+// STITCH_RECOMPUTE modes, not Deriche.
+inline bool mask_keep_level(const LevelForm& f) {
+    if (f.sweep == SW_BATCH) return !f.rcmp && f.x_fwd == XF_FWD && (f.y_bwd == YB_DEC || f.y_bwd == YB_BWD);
+    return f.sweep == SW_LONE && !f.xby && !f.rcmp;
+}
+// The form word of a call.  pathed: the mask plane comes from seam paths (k_mask_path), by another rule than the record's.
+inline uint32_t mask_keep_word(const PlanShape& s, const CallForm& c, bool pathed) {
+    uint32_t w = ((uint32_t)c.l_end & 31u) << MK_LEND_BIT;
+    bool ok = !pathed && !s.mask_stored() && c.l_end >= 1 && c.lv[0].mask_l0;  // the implicit level-0 mask: no k_mask, nothing of the mask at level 0 in memory
+    if (c.l_end >= 1 && c.lv[0].mask_l0) w |= MK_MASK_L0;
+    for (int l = 0; l < c.l_end; ++l) {
+        const LevelForm& f = c.lv[l];
+        const uint32_t b = mask_keep_level_bits(f.mr_out, f.mr_in, f.fill_mask);
+        if (l < MK_LEVELS)
+            w |= b << (MK_LEVEL_BIT + 3 * l);
+        else if (b)
+            ok = false;  // (call_form sets these bits below level 4 only: the flags of levels 1 and 2, T flags of the fused levels)
+        ok = ok && mask_keep_level(f);
+    }
+#ifdef STITCH_NO_MASK_KEEP  // (the A/B library: every mask plane on every call)
+    ok = false;
+#endif
+    return ok ? w | MK_KEEP_OK : w;
+}
+
 // ---- the band path: ONE pair split into row bands over ranks (stitch_band.inc) ---------------------------------------------------
 // What a band of a cw x ch canvas holds (BandShape, band_shape) and what each entry point launches at each level (BandForm, band_form).
 // The split levels l < Ls are reduced and collapsed band by band by the caller's sequence of operations (pipeline.BandStitcher.steps);

@@ -21,6 +21,7 @@
 #include "stitch.h"
 #include "stitch_g_flags.h"
 #include "stitch_index_plane.h"
+#include "stitch_mask_keep.h"
 #include "stitch_collapse_sides.h"
 #include "stitch_src_runs.h"
 #include "stitch_handoff.h"
@@ -162,7 +163,8 @@ int pyramid_levels(int w, int h, int level_rule, int* lw, int* lh) {
 }
 
 constexpr int WF_CTRL_WORDS = 4 * 16 + 16;  // band-queue heads of up to 4 levels (64 bytes apart) + the abort word
-constexpr int IDX_HEAD_WORDS = 32, IDX_TODO_WORD = 16;  // in front of a plan's seam records: three counts, from word 16 the slots' todo words (k_index_keys)
+constexpr int IDX_HEAD_WORDS = 64, IDX_TODO_WORD = 16;  // in front of a plan's seam records: three counts, from word 16 the slots' todo words (k_index_keys)
+constexpr int MK_COUNT_WORD = 32, MK_TODO_WORD = 48;    // in the same head: the mask pyramids' two counts, the time-out count k_mask_keys saw last, and the slots' mask_todo words
 constexpr int WF_STICKY_WORDS = 16;         // behind them, outside what a launch sequence clears: the plan's count of timed-out waits and,
                                             // from word 2, its three 64-bit hand-off counts (stitch_plan_handoff_counts)
 
@@ -215,6 +217,9 @@ struct stitch_plan : PlanShape {
     unsigned* idx_head = nullptr;    // device: IDX_HEAD_WORDS words in front of d_seam
     unsigned* h_idx_head = nullptr;  // pinned: the same words in front of h_seam (the allocation h_seam lives in)
     bool last_idx = false;           // the last call went through k_index_keys (stitch_plan_index_counts)
+    // The mask pyramids in the plan's slots (k_mask_keys, include/stitch_mask_keep.h): per slot the seam record and the form word its mask
+    // planes were computed under; in the head, the last call's two counts and per slot "compute the mask planes in this call".
+    MaskKey* mask_keys = nullptr;
     // The same planes in 16-byte runs (SrcRuns, k_compose.inc), [cap][bands][tiles] of level 0: written by k_src_runs behind k_src_index,
     // valid exactly where the slot's IndexKey is.  last_runs: the last call's sweep was handed them; last_owner: that call's idx_pr.
     SrcRuns runs{};
@@ -368,11 +373,12 @@ struct DecPlanes {
 // k_vv_y_bwd_dec<rowz, YST, zt, odd, xch> of the record, every instance either path has (the odd one: three-tap x decimation,
 // workgroups overlap by two columns; xch: columns from x0 with the chunk's own state arrays, `cols` of them)
 void launch_y_bwd_dec(const DecInstance& i, int np, hipStream_t s, const DecPlanes& a, const DecPlanes& b, const VVK& k, const double* ystate, const ZeroTiles& zt,
-                      const double* resume, double* state_out, int x0, int cols, int fill_l0, const ZeroTiles& gout, const ZeroTiles& mout) {
+                      const double* resume, double* state_out, int x0, int cols, int fill_l0, const ZeroTiles& gout, const ZeroTiles& mout,
+                      const unsigned* keep = nullptr) {
     const dim3 g = i.odd ? dim3((b.w + WAVE - 2) / (WAVE - 1), np) : dim3((cols + YCOLS - 1) / YCOLS, np);
     auto go = [&](auto R, auto Z, auto O, auto X) {
         k_vv_y_bwd_dec<decltype(R)::value, YST, decltype(Z)::value, decltype(O)::value, decltype(X)::value>
-            <<<g, 128, 0, s>>>(a.p, a.w, a.h, a.pitch, a.ps, k, ystate, b.p, b.w, b.h, b.pitch, b.ps, zt, resume, state_out, a.h_full, b.h_full, x0, fill_l0, gout, mout);
+            <<<g, 128, 0, s>>>(a.p, a.w, a.h, a.pitch, a.ps, k, ystate, b.p, b.w, b.h, b.pitch, b.ps, zt, resume, state_out, a.h_full, b.h_full, x0, fill_l0, gout, mout, keep);
     };
     const std::true_type y{};
     const std::false_type no{};
@@ -444,7 +450,7 @@ void launch_collapse(CollapseArgs<OUT, L0>& A, const CollapseKind& kd, int cols,
 // REDUCE for every level (ImageProcess.cpp:705-715): blur(G_l) into T, decimate T into G_{l+1}.  Which kernels: the call's form
 // (stitch_call_form.h); here are their arguments.
 template <typename PX>
-int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<PX>& pa, const ZeroTiles& zi, const SrcRuns& sr = SrcRuns{}) {
+int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<PX>& pa, const ZeroTiles& zi, const SrcRuns& sr = SrcRuns{}, const unsigned* keep = nullptr) {
     const int n = c.n, np = 7 * n;  // planes in flight: every launch covers all pairs of the batch
     if (c.wf_ctrl) k_clear_words<<<1, 256, 0, s>>>((u64*)p->wf_ctrl, WF_CTRL_WORDS / 2);  // band-queue heads + abort flag
     for (int l = 0; l < c.l_end; ++l) {
@@ -454,6 +460,7 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
         const long lines = (long)np * a.h;
         MaskL0 mk{};
         if (f.mask_l0) mk = MaskL0{p->d_seam, p->side, a.h, 1};
+        mk.h = a.h, mk.keep = keep;  // the slots' mask_todo words, for every kernel of the level that takes MaskL0 (mask_stands)
         const ZeroTiles none{};
         const ZeroTiles zt = f.zt ? ZeroTiles{p->zt, a.h, f.NR, f.NC} : none;
         // G column flags and row-repeat flags of the mask plane: of this level for its readers, of the next for the sweep that produces them
@@ -542,20 +549,20 @@ int run_reduce(stitch_plan* p, const CallForm& c, hipStream_t s, const PairArgs<
             StageTimer t(p, s, STITCH_K_VV_Y_BWD, l);
             if (f.y_bwd == YB_DEC)
                 launch_y_bwd_dec(DecInstance{f.rowz, f.dec_zt, f.dec_odd, false}, np, s, DecPlanes{p->T, a.w, a.h, a.pitch, a.ps, a.h}, DecPlanes{b.g, b.w, b.h, b.pitch, b.ps, b.h},
-                                 p->vvk, ystate, zt, nullptr, nullptr, 0, a.pitch, fill_l0, gout, mout);
+                                 p->vvk, ystate, zt, nullptr, nullptr, 0, a.pitch, fill_l0, gout, mout, keep);
             else if (f.y_bwd == YB_BWD)
                 k_vv_y_bwd<<<gy, 64, 0, s>>>(p->T, a.h, a.pitch, a.ps, p->vvk, ystate, nullptr, nullptr);
             else if (f.dec_odd)
-                k_vv_y_bwd_dec7<true><<<dim3((b.w + WAVE - 2) / (WAVE - 1), np), D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps);
+                k_vv_y_bwd_dec7<true><<<dim3((b.w + WAVE - 2) / (WAVE - 1), np), D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, nullptr, 0, keep);
             else {
                 unsigned long long* dbg = p->d7_dbg && l == p->stamp_d7_level ? p->d7_dbg : nullptr;
                 if (dbg) p->d7_dbg_chunks = (a.h + YCH - 1) / YCH;
-                k_vv_y_bwd_dec7<false><<<gy, D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, dbg, dbg ? Tuning::env_int("STITCH_D7_STAMP_MODE") : 0);
+                k_vv_y_bwd_dec7<false><<<gy, D7_THREADS, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, p->vvk, ystate, b.g, b.w, b.h, b.pitch, b.ps, dbg, dbg ? Tuning::env_int("STITCH_D7_STAMP_MODE") : 0, keep);
             }
         }
         if (f.decimate) {
             StageTimer t(p, s, STITCH_K_DECIMATE, l);
-            k_decimate<<<grid_xy(b.pitch, b.h, np), 256, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, b.g, b.w, b.h, b.pitch, b.ps, 0, 0);
+            k_decimate<<<grid_xy(b.pitch, b.h, np), 256, 0, s>>>(p->T, a.w, a.h, a.pitch, a.ps, b.g, b.w, b.h, b.pitch, b.ps, 0, 0, keep);
         }
     }
     if (c.coarse) {  // every remaining level in one launch, one workgroup per pair; leaves E of level coarse_from
@@ -630,7 +637,7 @@ int run_collapse(stitch_plan* p, const CallForm& c, const OutPtrs<OUT>& outs, hi
 }
 
 template <typename PX>
-int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const SeamInts* given, const PathArgs* paths) {
+int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, bool src, const SeamInts* given, const PathArgs* paths, unsigned mask_form) {
     const Level& a = p->lv[0];
     if (paths) {  // include/stitch_seam_path.h (a masked plan): no scan -- zeroed records that carry the branch, and the mask plane from the paths
         {
@@ -654,7 +661,10 @@ int run_seam_mask(stitch_plan* p, int n, hipStream_t s, const PairArgs<PX>& pa, 
         StageTimer t(p, s, STITCH_K_MASK, 0);
         k_mask<<<grid_xy(a.pitch, a.h, n), 256, 0, s>>>(a.g, a.w, a.pitch, a.ps, p->d_seam);
     }
-    // (with the words in front of them: the index planes' counts of this call)
+    // whose mask pyramid stands: decided behind the records, in stream order (a captured sequence decides again on every replay)
+    k_mask_keys<<<1, 64, 0, s>>>(p->d_seam, n, p->cap, mask_form, p->mask_keys, p->idx_head + MK_TODO_WORD, p->wf_ctrl ? p->wf_ctrl + WF_CTRL_WORDS : nullptr,
+                                 p->idx_head + MK_COUNT_WORD);
+    // (with the words in front of them: the index planes' and the mask pyramids' counts of this call)
     HIPCHK(hipMemcpyAsync(p->h_idx_head, p->idx_head, sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * n, hipMemcpyDeviceToHost, s));
     return launch_check("seam/mask");
 }
@@ -727,9 +737,12 @@ int run_pairs(stitch_plan* p, const PairArgs<PX>& pa, const OutPtrs<PX>& outs, i
     p->last_idx = src && !pa.a_dense;
     p->last_runs = sr.cls != nullptr;
     for (int i = 0; i < MAXB; ++i) p->last_owner[i] = pa.idx_pr[i];
-    if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given, paths))) return rc;
+    // the mask planes of a slot are computed where the slot's record (MaskKey) does not describe this call's seam and form already
+    // (k_mask_keys); a call whose form does not know the skip hands no words on: its kernels compute every plane
+    const unsigned mask_form = mask_keep_word(*p, c, paths != nullptr);
+    if ((rc = run_seam_mask<PX>(p, n, s, pa, src, given, paths, mask_form))) return rc;
     p->last_form = c;
-    if ((rc = run_reduce<PX>(p, c, s, pa, zi, sr))) return rc;
+    if ((rc = run_reduce<PX>(p, c, s, pa, zi, sr, (mask_form & MK_KEEP_OK) ? p->idx_head + MK_TODO_WORD : nullptr))) return rc;
     if ((rc = run_collapse<PX>(p, c, outs, s, pa))) return rc;
     p->last_stream = s;
     p->pending = true;
@@ -1648,9 +1661,13 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     // x-sweep state [4][lines] followed by the y state the wavefront kernel leaves [4][planes][pitch]
     const size_t state_n = 4 * 7 * B * (size_t)(v0.h + 64) + 4 * 7 * B * (size_t)std::max(v0.h + 64, v0.pitch);
     const size_t st_off = take(sizeof(double) * state_n);
-    static_assert(sizeof(unsigned) * IDX_HEAD_WORDS % alignof(SeamDev) == 0 && MAXB <= IDX_HEAD_WORDS - IDX_TODO_WORD, "the words in front of the seam records");
+    static_assert(sizeof(unsigned) * IDX_HEAD_WORDS % alignof(SeamDev) == 0 && IDX_TODO_WORD + MAXB <= MK_COUNT_WORD && MK_COUNT_WORD + 3 <= MK_TODO_WORD &&
+                      MK_TODO_WORD + MAXB <= IDX_HEAD_WORDS,
+                  "the words in front of the seam records: three counts, the index planes' todo words, the mask pyramids' counts and todo words");
+    static_assert(MAXB <= 32 && WF_STAND_WORD >= 8 && WF_STAND_WORD < WF_STICKY_WORDS, "one bit per slot in a word behind the sticky count and its three 64-bit counts");
     const size_t seam_off = take(sizeof(unsigned) * IDX_HEAD_WORDS + sizeof(SeamDev) * B);
     const size_t ik_off = take(sizeof(IndexKey) * B);  // zero at creation: no slot holds a plane
+    const size_t mk_off = take(sizeof(MaskKey) * B);   // zero at creation: no slot holds a mask pyramid
     const size_t side_off = take(sizeof(float) * B * v0.pitch);
     const size_t zp_off = take(4096);  // zeros for good (k_vv_xby_m's loader reads a flagged tile from here)
     // the index planes in 16-byte runs: per tile 4 KB of bases, 512 B of patch records, one class byte (a plan that can be source-fused)
@@ -1681,6 +1698,7 @@ static int plan_create(int cw, int ch, const stitch_blend_opts* opts, int max_pa
     p->idx_head = reinterpret_cast<unsigned*>(base + seam_off);
     p->d_seam = reinterpret_cast<SeamDev*>(p->idx_head + IDX_HEAD_WORDS);
     p->idx_keys = reinterpret_cast<IndexKey*>(base + ik_off);
+    p->mask_keys = reinterpret_cast<MaskKey*>(base + mk_off);
     p->side = reinterpret_cast<float*>(base + side_off);
     p->zero_page = reinterpret_cast<const float*>(base + zp_off);
     if (sr_tiles) p->runs = SrcRuns{reinterpret_cast<unsigned*>(base + sr_base_off), reinterpret_cast<uint2*>(base + sr_patch_off), reinterpret_cast<uint8_t*>(base + sr_cls_off), reinterpret_cast<uint8_t*>(base + sr_live_off), NR0, NC0, 1};
@@ -1932,6 +1950,16 @@ int stitch_plan_index_counts(stitch_plan* p, uint32_t out[3]) {
     return STITCH_OK;
 }
 
+int stitch_plan_mask_keep_counts(stitch_plan* p, uint32_t out[2]) {
+    if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
+    if (p->pending) {
+        HIPCHK(hipStreamSynchronize(p->last_stream));
+        p->pending = false;
+    }
+    for (int i = 0; i < 2; ++i) out[i] = p->last_n > 0 && !p->planes_in ? p->h_idx_head[MK_COUNT_WORD + i] : 0u;
+    return STITCH_OK;
+}
+
 int stitch_plan_src_run_counts(stitch_plan* p, uint32_t out[4]) {
     if (!p || !out) return fail(STITCH_ERR_ARG, "null plan or output");
     if (p->pending) {
@@ -2008,6 +2036,7 @@ int stitch_plan_clear_fault(stitch_plan* p) {
     if (p->h_wf_abort) p->wf_abort_seen = *p->h_wf_abort;
     // no slot's index plane is taken on trust after a fault
     HIPCHK(hipMemsetAsync(p->idx_keys, 0, sizeof(IndexKey) * p->cap, p->last_stream));
+    HIPCHK(hipMemsetAsync(p->mask_keys, 0, sizeof(MaskKey) * p->cap, p->last_stream));  // nor does a mask pyramid stand
     HIPCHK(hipStreamSynchronize(p->last_stream));
     return STITCH_OK;
 }
@@ -2030,6 +2059,7 @@ int stitch_plan_call_forms(const stitch_plan* p, int n_pairs) {
     int f = 0;
     if (c.src) f |= STITCH_FAST_SOURCE_FUSED;
     if (c.lv[0].sweep == SW_BATCH || c.lv[0].xby) f |= STITCH_FAST_FUSED_SWEEP;  // k_vv_xbyf; one pair in flight: k_vv_xby_m
+    if (mask_keep_word(*p, c, false) & MK_KEEP_OK) f |= STITCH_CALL_MASK_KEEP;  // include/stitch_mask_keep.h
     return f;
 }
 

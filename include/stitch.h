@@ -182,7 +182,7 @@ enum {
     STITCH_FAST_ZERO_TILES = 8,
     STITCH_FAST_FUSED_DECIMATE = 16,
     STITCH_FAST_COARSE_LEVELS = 32
-};
+};  /* (64 is STITCH_CALL_MASK_KEEP of stitch_mask_keep.h, an answer of stitch_plan_call_forms alone: the next value here is 128) */
 int stitch_plan_fast_paths(const stitch_plan *plan);
 /* stitch_plan_fast_paths is a CAPABILITY mask: what the workspace was built for.  Which of SOURCE_FUSED / FUSED_SWEEP a call
  * actually runs is decided per call from its number of pairs (a launch sequence with at least two pairs and 8 MPix of canvas,
