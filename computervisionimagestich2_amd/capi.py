@@ -205,6 +205,14 @@ RIG_MONITOR_SIGNATURES = _signatures(
     ("stitch_residual_best_shift", i32, vp, i32, i32, vp, vp),
 )
 
+# The same for include/stitch_rig_scale.h, a rig's output scale; tests/test_rig_scale_host.py holds it to that header.
+# (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks the four.)
+RIG_SCALE_SIGNATURES = _signatures(
+    ("stitch_dev_scale_pack_many_u8", i32, i32, i32, vp, i32, i32, vp, vp, i32, vp),
+    ("stitch_rig_set_output_scale", i32, vp, i32, i32), ("stitch_rig_clear_output_scale", i32, vp), ("stitch_rig_output_scale", i32, vp, vp, vp),
+)
+SCALE_MAX_FACTOR = 8  # STITCH_SCALE_MAX_FACTOR
+
 # The same for include/stitch_seam_path.h, path seams; tests/test_seam_path_host.py holds it to that header.
 # (Bound where the library exports it: an A/B build of an earlier tree, STITCH_LIB, lacks them.)
 SEAM_PATH_SIGNATURES = _signatures(
@@ -283,9 +291,9 @@ def lib():
         if hasattr(L, "stitch_plan_mask_keep_counts"):  # include/stitch_mask_keep.h (likewise)
             L.stitch_plan_mask_keep_counts.restype, L.stitch_plan_mask_keep_counts.argtypes = i32, [vp, vp]
         # include/stitch_collapse_sides.h, stitch_src_runs.h, stitch_rig_crop.h, stitch_rig_formats.h, stitch_rig_formats_yuv.h, stitch_rig_monitor.h, stitch_seam_path.h, stitch_seam_anchor.h,
-        # stitch_rig_exposure_temporal.h (likewise)
+        # stitch_rig_exposure_temporal.h, stitch_rig_scale.h (likewise)
         for name, (res, args) in list(COLLAPSE_SIDES_SIGNATURES.items()) + list(SRC_RUNS_SIGNATURES.items()) + list(RIG_CROP_SIGNATURES.items()) + list(RIG_EXPOSURE_TEMPORAL_SIGNATURES.items()) \
-                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_FORMAT_YUV_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()):
+                + list(RIG_FORMAT_SIGNATURES.items()) + list(RIG_FORMAT_YUV_SIGNATURES.items()) + list(RIG_MONITOR_SIGNATURES.items()) + list(SEAM_PATH_SIGNATURES.items()) + list(SEAM_ANCHOR_SIGNATURES.items()) + list(RIG_SCALE_SIGNATURES.items()):
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
@@ -1684,6 +1692,26 @@ def dev_pack_many(planar, fmt=None, matrix=0, out=None, pitch=None, pitch2=None)
     return out
 
 
+def dev_scale_pack_many(planar, size, fmt=PIX_PLANAR, matrix=0, rect=None, out=None, pitch=None, pitch2=None):
+    """stitch_dev_scale_pack_many_u8 on torch's current stream, which it waits for: of every dense planar (3, h, w) tensor the
+    rectangle rect = (x0, y0, w, h) (None: the whole image) scaled to size = (ow, oh) by the exact area average of
+    include/stitch_rig_scale.h and written as an Image of `fmt`, one launch; into `out` (Images of that size; their format is the
+    call's) or fresh images of the given pitches (None: tight).  Returns the Images (PIX_PLANAR: their .data is the (3, oh, ow) tensor)."""
+    planar = list(planar)
+    _, h, w = planar[0].shape
+    planar = _planar_list(planar, w, h)
+    ow, oh = int(size[0]), int(size[1])
+    if out is None:
+        out = [Image.empty(fmt, ow, oh, planar[0].device, pitch, pitch2) for _ in planar]
+    out = list(out)
+    if len(out) != len(planar) or any(im.fmt != fmt for im in out):
+        raise ValueError("one image of the call's format per planar input")
+    ptrs = (C.c_void_p * max(len(planar), 1))(*[t.data_ptr() for t in planar])
+    _chk(lib().stitch_dev_scale_pack_many_u8(int(fmt), int(matrix), ptrs, w, h, C.byref(_rect(rect)) if rect is not None else None, _image_array(out),
+                                             len(planar), _stream()))
+    return out
+
+
 class Rig(_Handle):
     """stitch_rig: the recorded stitch order, maps and canvases of a panorama, replayed on many frame sets -- step k of all the
     sets of a call is one batched launch sequence."""
@@ -1840,6 +1868,27 @@ class Rig(_Handle):
     @property
     def out_height(self):
         return self._out_size()[1]
+
+    def set_output_scale(self, ow, oh):
+        """stitch_rig_set_output_scale (host only): every later stitch() writes ow x oh per set -- the exact area average
+        (include/stitch_rig_scale.h) of what it writes without the scale, in the output format; 1 <= ow <= w <= 8 ow and likewise
+        for oh against the rig's present output size (the crop's, else the canvas).  Returns self."""
+        _chk(lib().stitch_rig_set_output_scale(self._h, int(ow), int(oh)))
+        return self
+
+    def clear_output_scale(self):
+        """stitch_rig_clear_output_scale: back to the crop's or the canvas's size.  Returns self."""
+        _chk(lib().stitch_rig_clear_output_scale(self._h))
+        return self
+
+    @property
+    def output_scale(self):
+        """stitch_rig_output_scale: (ow, oh), or None when no scale is set."""
+        if not hasattr(lib(), "stitch_rig_output_scale"):  # an A/B build of an earlier tree, STITCH_LIB
+            return None
+        w, h = C.c_int(), C.c_int()
+        _chk(lib().stitch_rig_output_scale(self._h, C.byref(w), C.byref(h)))
+        return (w.value, h.value) if w.value else None
 
     def set_formats(self, in_fmt, out_fmt, matrix=0):
         """stitch_rig_set_formats (host only): every later stitch() takes its frames as Images of in_fmt and returns Images of

@@ -37,6 +37,7 @@
 #include "stitch_rig_formats.h"
 #include "stitch_rig_formats_yuv.h"
 #include "stitch_rig_monitor.h"
+#include "stitch_rig_scale.h"
 #include "stitch_seam_path.h"
 #include "stitch_seam_anchor.h"
 #include "stitch_kernels.hpp"
@@ -2630,3 +2631,4 @@ int stitch_dev_quantize_u8(const float* d_src, uint8_t* d_dst, size_t n, void* s
 #include "stitch_rig_monitor.inc"
 #include "stitch_seam_path.inc"
 #include "stitch_rig_seam_paths.inc"
+#include "stitch_rig_scale.inc"

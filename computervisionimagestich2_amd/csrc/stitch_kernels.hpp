@@ -103,6 +103,7 @@ __device__ __forceinline__ void bilinear3(const PX* __restrict__ src, int w, int
 #include "k_rig_seams.inc"  // fixed seams for a rig: seam records from given integers, coverage bit planes and their mid-row scan
 #include "k_rig_crop.inc"  // the crop of a rig's output: the largest rectangle inside a coverage mask, the copy of a rectangle
 #include "k_rig_formats.inc"  // a rig's frames and mosaics in camera layouts: packed RGB and NV12 to and from planar, many images per launch
+#include "k_rig_scale.inc"  // a rig's output scale: the exact area-average downscale of many images inside the pack, any layout out
 #include "k_rig_monitor.inc"  // a rig's alignment monitor: the domain of a step from its coverage planes, residuals of many pairs over integer shifts
 #include "k_seam_path.inc"  // path seams: the level-0 mask from a column per row, the cost pass and the dynamic programme of the finder
 #include "k_exposure.inc"  // exact float running sums by scan: the colour transfer's statistics at GPU speed

@@ -88,6 +88,8 @@ struct stitch_rig {
     int32_t* sa_dev = nullptr;                // the anchor: sp_rows columns, step after step
     unsigned long long* sa_moved = nullptr;   // `moved` of the sequence in flight, max_sets sets of one word per step
     std::vector<uint64_t> sa_last_moved;      // ... and of the last replay with paths, beside sp_last_cost
+    // ---- the output scale (include/stitch_rig_scale.h; stitch_rig_scale.inc): 0, 0 is no scale, the replay as it is ----
+    int scale_w = 0, scale_h = 0;             // (its planar calls use fmt_out / crop_full as a formatted output does)
     bool sa_active() const { return sp_mode == 1 && sa_opts.policy != 0; }
     const stitch_blend_opts* blend_ptr() const { return has_blend ? &blend : nullptr; }
     ~stitch_rig() {
@@ -149,6 +151,12 @@ int rig_fmt_unpack(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int
 int rig_fmt_project(const stitch_rig* R, const FmtImage* d_tab, int m, int w, int h, hipStream_t s);  // the fused form of rig_project_many
 // the end of a sequence with a formatted output: histogram and LUT where the rig finishes, the crop copy of mode 2, then the one pack
 int rig_fmt_finish_pack(const stitch_rig* R, const RigImage* h_tab, const RigImage* d_tab, const FmtImage* d_fmt, int32_t* d_eq, int m, hipStream_t s);
+
+// The output scale of a rig that has one (stitch_rig_scale.inc): the size rule against the rig's present source size, and the one
+// launch that ends a sequence in place of the pack -- m images' rectangle rc, finished where d_eq holds their LUTs, scaled and written
+// in the rig's output format (planar included).
+int rig_scale_check(const stitch_rig* R, const char* who);
+int rig_scale_pack(const stitch_rig* R, const FmtImage* d_fmt, int m, const FmtRect& rc, const int32_t* d_eq, const MixK& mk, hipStream_t s);
 
 // The monitor of a rig that has one (stitch_rig_monitor.inc): its domains and record buffer, the zeroing of a sequence's records,
 // step k's residual launch over the m sets in flight from the step's pair descriptors, the copy of a sequence's records to the host.
@@ -457,16 +465,19 @@ namespace {
 // stitch_dev_rig_stitch_u8, and stitch_dev_rig_stitch_exposure_u8 with its statistics (a host array, or NULL)
 int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8_t* const* d_out, int32_t* set_status, stitch_seam* seams, float* stats,
                void* stream, RigFmtCall* fc = nullptr) {
-    int rc = need_device();
-    if (rc) return rc;
+    int rc;
+    if (rig && rig->scale_w && (rc = rig_scale_check(rig, "rig_stitch"))) return rc;  // include/stitch_rig_scale.h: before a device is needed
+    if ((rc = need_device())) return rc;
     if (!rig || !frames || !d_out || !set_status || n_sets < 1) return fail(STITCH_ERR_ARG, "rig_stitch: null argument or %d sets", n_sets);
     stitch_rig* R = rig;
     if (stats && !R->ex.mode) return fail(STITCH_ERR_ARG, "rig_stitch: statistics asked of a rig made without a transfer (mode 0)");
     const int n = R->n, ns = (int)R->steps.size();
     // include/stitch_rig_crop.h: a cropped rig writes the rectangle to d_out, and its last step a full canvas of the rig's own
     const bool cropped = R->crop_mode != 0;
-    const size_t out_bytes = cropped ? (size_t)3 * R->crop.w * R->crop.h : (size_t)3 * R->out_w * R->out_h;
-    const bool fin = fc && rig->in_fmt, fout = fc && rig->out_fmt;  // (a call with images has checked them itself)
+    const bool scaled = R->scale_w != 0;  // include/stitch_rig_scale.h: d_out takes the scaled size
+    const size_t out_bytes = scaled ? (size_t)3 * R->scale_w * R->scale_h : cropped ? (size_t)3 * R->crop.w * R->crop.h : (size_t)3 * R->out_w * R->out_h;
+    const bool with_images = fc != nullptr;
+    const bool fin = fc && rig->in_fmt, fout = (fc && rig->out_fmt) || scaled;  // (a call with images has checked them itself)
     for (int i = 0; i < n_sets && !fc; ++i) {
         if (!d_out[i]) return fail(STITCH_ERR_ARG, "rig_stitch: set %d has no output buffer", i);
         for (int f = 0; f < n; ++f) {
@@ -483,6 +494,15 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         }
         for (int j = 0; j < i; ++j)
             if (ranges_overlap(d_out[j], out_bytes, d_out[i], out_bytes)) return fail(STITCH_ERR_ARG, "rig_stitch: the outputs of sets %d and %d overlap", j, i);
+    }
+    // a planar call of a rig with a scale ends as a call with images does: its outputs are planar images of the scaled size, which
+    // the one scaled pack launch per sequence writes from the rig's own buffers
+    std::vector<stitch_image> scaled_out;
+    RigFmtCall scaled_call{nullptr, nullptr, {}, {}, nullptr};
+    if (scaled && !fc) {
+        for (int i = 0; i < n_sets; ++i) scaled_out.push_back(stitch_image{d_out[i], nullptr, R->scale_w, R->scale_h, 0, 0});
+        scaled_call.out = scaled_out.data();
+        fc = &scaled_call;
     }
     if ((rc = rig_workspaces(R))) return rc;
     if ((rc = rig_et_workspaces(R))) return rc;
@@ -687,7 +707,7 @@ int rig_stitch(stitch_rig* rig, const stitch_frame_u8* frames, int n_sets, uint8
         R->et_state.swap(et_state);
         R->et_has.swap(et_has);
     }
-    if (fc) {  // include/stitch_rig_formats_yuv.h: the form each frame index took, kept once the replay has completed
+    if (with_images) {  // include/stitch_rig_formats_yuv.h: the form each frame index took, kept once the replay has completed
         R->fmt_form.assign((size_t)n, (char)STITCH_RIG_INPUT_NONE);
         if (fin)
             for (int f : R->needed) R->fmt_form[f] = (char)(fc->fused[f] ? STITCH_RIG_INPUT_FUSED : STITCH_RIG_INPUT_CONVERTED);

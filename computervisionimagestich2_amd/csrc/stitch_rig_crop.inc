@@ -140,8 +140,9 @@ int stitch_rig_crop(const stitch_rig* rig, stitch_rect* rect_out, int* mode_out)
 
 int stitch_rig_output_size(const stitch_rig* rig, int* width, int* height) {
     if (!rig) return fail(STITCH_ERR_ARG, "rig_output_size: null handle");
-    if (width) *width = rig->crop_mode ? rig->crop.w : rig->out_w;
-    if (height) *height = rig->crop_mode ? rig->crop.h : rig->out_h;
+    // (include/stitch_rig_scale.h: a rig with an output scale writes that size)
+    if (width) *width = rig->scale_w ? rig->scale_w : rig->crop_mode ? rig->crop.w : rig->out_w;
+    if (height) *height = rig->scale_h ? rig->scale_h : rig->crop_mode ? rig->crop.h : rig->out_h;
     return STITCH_OK;
 }
 

@@ -146,7 +146,7 @@ int rig_fmt_workspace(stitch_rig* R, RigFmtCall* fc, int n_sets) {
             if (!fc->fused[f] && !R->fmt_in[f]) HIPCHK(hipMalloc((void**)&R->fmt_in[f], (size_t)R->max_sets * 3 * R->fw[f] * R->fh[f]));
         }
     }
-    if (R->out_fmt && !rig_fmt_pack_from_full(R)) {  // (else nothing reads them.)  Of the canvas's size: a crop is inside it
+    if ((R->out_fmt || R->scale_w) && !rig_fmt_pack_from_full(R)) {  // (else nothing reads them.)  Of the canvas's size: a crop is inside it
         R->fmt_out_bytes = align256((size_t)3 * R->out_w * R->out_h);
         if (!R->fmt_out) HIPCHK(hipMalloc((void**)&R->fmt_out, (size_t)R->max_sets * R->fmt_out_bytes));
     }
@@ -169,7 +169,7 @@ void rig_fmt_tables(const stitch_rig* R, RigFmtCall* fc, const RigImage* h_tab, 
                 fc->tab.push_back(FmtImage{im.data, im.data2, planar, im.pitch, im.pitch2});
             }
         at += (size_t)m * (R->crop_mode ? 2 : 1);
-        if (R->out_fmt)
+        if (R->out_fmt || R->scale_w)  // (include/stitch_rig_scale.h: a scaled planar output is an image of the table as well)
             for (int i = 0; i < m; ++i) {
                 const stitch_image& im = fc->out[set0 + i];
                 uint8_t* planar = rig_fmt_pack_from_full(R) ? R->crop_full + (size_t)i * R->crop_full_bytes : R->fmt_out + (size_t)i * R->fmt_out_bytes;
@@ -233,6 +233,7 @@ int rig_fmt_finish_pack(const stitch_rig* R, const RigImage* h_tab, const RigIma
         return rc;
     }
     const MixK mk = mix_params(R->num, R->den);
+    if (R->scale_w) return rig_scale_pack(R, d_fmt, m, r, R->finish ? d_eq : nullptr, mk, s);  // include/stitch_rig_scale.h: in place of the pack
     return R->finish ? fmt_launch_pack_as<true>(R->out_fmt, R->matrix, d_fmt, m, r, d_eq, mk, s) : fmt_launch_pack_as<false>(R->out_fmt, R->matrix, d_fmt, m, r, nullptr, mk, s);
 }
 
@@ -315,8 +316,9 @@ int stitch_dev_rig_stitch_fmt_u8(stitch_rig* rig, const stitch_image* frames, in
     if (!rig || !frames || !out || !set_status || n_sets < 1) return fail(STITCH_ERR_ARG, "%s: null argument or %d sets", who, n_sets);
     if (stats && !rig->ex.mode) return fail(STITCH_ERR_ARG, "%s: statistics asked of a rig made without a transfer (mode 0)", who);
     const stitch_rig* R = rig;
-    const int n = R->n, ow = R->crop_mode ? R->crop.w : R->out_w, oh = R->crop_mode ? R->crop.h : R->out_h;
     int rc;
+    if (R->scale_w && (rc = rig_scale_check(R, who))) return rc;  // include/stitch_rig_scale.h: the outputs have the scaled size
+    const int n = R->n, ow = R->scale_w ? R->scale_w : R->crop_mode ? R->crop.w : R->out_w, oh = R->scale_w ? R->scale_h : R->crop_mode ? R->crop.h : R->out_h;
     for (int i = 0; i < n_sets; ++i) {
         if ((rc = fmt_check_image(R->out_fmt, out[i], ow, oh, who, "the output of set", i))) return rc;
         for (int f = 0; f < n; ++f) {

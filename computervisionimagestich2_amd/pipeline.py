@@ -171,7 +171,7 @@ def exposure_match_temporal(proj_dst, proj_src, result, exposure, keep_black, op
 
 
 def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plans=None, exposure=0, keep_black=True, seams=None, crop=None, formats=None,
-                 residuals=None, seam_paths=None, exposure_temporal=None):
+                 residuals=None, seam_paths=None, exposure_temporal=None, scale=None):
     """The hot-path calls of ImageProcess::matching for a recorded stitch order, device resident.
 
     frames: list of (3,H,W) uint8 device tensors (unprojected).  steps: list of dicts with keys
@@ -210,7 +210,18 @@ def stitch_chain(frames, steps, opts=None, finish=True, num=19.0, den=20.0, plan
     applies the given record and measures nothing.  The return value grows by a last element, dict(state=[per step 12 floats or
     None], measured=[...], used=[...]) (measured None per step with fixed=): a caller that feeds a set's state into the next
     set's call states a rig that smooths.  With exposure_temporal=None the return value and every byte stay as they are.
+    scale: (ow, oh) (include/stitch_rig_scale.h): the chain's planar output -- cropped and finished as above -- through
+    capi.dev_scale_pack_many into out_fmt (planar without formats): the single-set statement of a rig with an output scale.  A planar
+    result stays a tensor, now (3, oh, ow).  With scale=None the return value and every byte stay as they are.
     Returns the final uint8 mosaic tensor (after equalisation + luminance mix when finish=True, :237-268)."""
+    if scale is not None:
+        in_fmt, out_fmt, matrix = formats if formats is not None else (capi.PIX_PLANAR, capi.PIX_PLANAR, 0)
+        result = stitch_chain(frames, steps, opts, finish, num, den, plans, exposure, keep_black, seams, crop,
+                              None if formats is None else (in_fmt, capi.PIX_PLANAR, matrix), residuals, seam_paths, exposure_temporal)
+        result, *extras = result if isinstance(result, tuple) else (result,)
+        image = capi.dev_scale_pack_many([result], scale, out_fmt, matrix)[0]
+        result = image.data if out_fmt == capi.PIX_PLANAR else image
+        return (result, *extras) if extras else result
     if formats is not None:
         in_fmt, out_fmt, matrix = formats
         if in_fmt != capi.PIX_PLANAR:
