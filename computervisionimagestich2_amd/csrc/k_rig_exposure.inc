@@ -128,17 +128,25 @@ __global__ __launch_bounds__(256) void k_ex_transfer_given_many(const ExGiven* _
 // i is read at m + i * m_stride and its filtered twin written at u + i * u_stride (a rig's records are 16 floats apart, dense ones
 // 12).  A record is valid when every lane's value is finite and the sds' (lanes 3 .. 5, 9 .. 11) are > 0: a wave vote.  The state
 // stays in a register across the loop and is written back once, with the flag.
+// A rig's replay (failed != NULL): failed[i] says whether record i's set was refused by the seam scan of an earlier step of this
+// sequence -- `prev` holds the scans of the step before (NULL at step 0, which clears the flags; NULL too where no scan can refuse).
+// What such a set measures from then on means nothing: its record passes through unfiltered and never enters the state.
 __global__ __launch_bounds__(64) void k_ex_stats_filter(const float* m, size_t m_stride, float* u, size_t u_stride, int count, float kf, float* __restrict__ state12,
-                                                        int32_t* __restrict__ has_io) {
+                                                        int32_t* __restrict__ has_io, int32_t* failed, const SeamDev* prev, int first_step) {
     const int lane = threadIdx.x;
     const bool active = lane < 12, is_sd = active && (lane % 6) >= 3;
     bool has = *has_io != 0;
     float p = active && has ? state12[lane] : 0.0f;
     for (int i = 0; i < count; ++i) {
+        bool out = false;  // wave-uniform
+        if (failed) {
+            out = !first_step && (failed[i] != 0 || (prev && prev[i].status != 0));
+            if (lane == 0) failed[i] = out ? 1 : 0;
+        }
         const float v = active ? m[(size_t)i * m_stride + lane] : 1.0f;
         const bool bad = active && (!(fabsf(v) <= 3.402823466e38f) || (is_sd && !(v > 0.0f)));
         float w = v;
-        if (!__any(bad)) {
+        if (!out && !__any(bad)) {
             if (has) w = v + kf * (p - v);
             p = w;
             has = true;

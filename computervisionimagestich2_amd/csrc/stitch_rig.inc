@@ -35,6 +35,7 @@ struct stitch_rig {
     std::vector<float> et_state;          // ... its state between replays, 12 floats per step, and per step whether it has one
     std::vector<int32_t> et_has;          //     (both empty: no step has; a replay takes them up and a completed one leaves them)
     float* ex_used = nullptr;             // ... the records the apply passes read, laid out as ex_stats; from the first smoothed replay on
+    int32_t* et_failed = nullptr;         // ... per set of a sequence whether an earlier step's seam scan refused it (k_ex_stats_filter)
     std::vector<float> et_fixed;          // fixed statistics, 12 floats per step (empty: none); they win over smoothing
     std::vector<float> et_last_used;      // what the apply passes of the last replay with an option read: 12 floats per set and step
     int et_last_sets = 0;
@@ -103,7 +104,7 @@ struct stitch_rig {
         if (cover) (void)hipFree(cover);
         if (mon_dom) (void)hipFree(mon_dom);
         if (mon_rec) (void)hipFree(mon_rec);
-        for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table, (void*)ex_used})
+        for (void* p : {(void*)ex_lab, (void*)ex_stats, (void*)ex_sums, ex_table, (void*)ex_used, (void*)et_failed})
             if (p) (void)hipFree(p);
         for (stitch_plan* p : plans) stitch_plan_destroy(p);  // waits for the plan's last call
         for (uint8_t* p : proj)

@@ -71,9 +71,10 @@ int ex_transfer_given_many(const ExGiven* d_img, int count, size_t n, const floa
     return launch_check("k_ex_transfer_given_many");
 }
 
-// ... and the filter of `count` records, one wavefront.
-int ex_stats_filter(const float* d_m, size_t m_stride, float* d_u, size_t u_stride, int count, int keep, float* d_state12, int32_t* d_has, hipStream_t s) {
-    k_ex_stats_filter<<<1, 64, 0, s>>>(d_m, m_stride, d_u, u_stride, count, (float)keep / 256.0f, d_state12, d_has);
+// ... and the filter of `count` records, one wavefront.  d_failed, d_prev, first_step: a rig's (k_ex_stats_filter); NULL, NULL, 0 otherwise.
+int ex_stats_filter(const float* d_m, size_t m_stride, float* d_u, size_t u_stride, int count, int keep, float* d_state12, int32_t* d_has, int32_t* d_failed,
+                    const SeamDev* d_prev, int first_step, hipStream_t s) {
+    k_ex_stats_filter<<<1, 64, 0, s>>>(d_m, m_stride, d_u, u_stride, count, (float)keep / 256.0f, d_state12, d_has, d_failed, d_prev, first_step);
     return launch_check("k_ex_stats_filter");
 }
 
@@ -126,6 +127,7 @@ int rig_et_workspaces(stitch_rig* R) {
     const int rc = rig_ex_workspaces(R);  // (takes only what is missing)
     if (rc) return rc;
     if (rig_et_smoothed(R) && !R->ex_used) HIPCHK(hipMalloc((void**)&R->ex_used, sizeof(float) * 16 * (size_t)R->max_sets * R->steps.size()));
+    if (rig_et_smoothed(R) && !R->et_failed) HIPCHK(hipMalloc((void**)&R->et_failed, sizeof(int32_t) * (size_t)R->max_sets));
     return STITCH_OK;
 }
 
@@ -204,8 +206,11 @@ int rig_ex_transfer(stitch_rig* R, unsigned char* d_tables, int k, int m, hipStr
     if (rc) return rc;
     float* d_state = reinterpret_cast<float*>(d_tables + rig_ex_images_bytes(R));
     const size_t rec = (size_t)16 * K;  // from a set's record of step k to the next set's
+    // a set that the content seam scan of an earlier step refused takes no further part in the filter: the scans of step k - 1 are
+    // still in its plan (step k's blend, which may run on the same plan, is queued behind this launch)
+    const SeamDev* d_prev = k > 0 && !R->sp_mode && R->fixed.empty() ? R->plans[R->plan_of_step[k - 1]]->d_seam : nullptr;
     if ((rc = ex_stats_filter(R->ex_stats + (size_t)16 * k, rec, R->ex_used + (size_t)16 * k, rec, m, R->et_keep, d_state + (size_t)12 * k,
-                              reinterpret_cast<int32_t*>(d_state + (size_t)12 * K) + k, s)))
+                              reinterpret_cast<int32_t*>(d_state + (size_t)12 * K) + k, R->et_failed, d_prev, k == 0, s)))
         return rc;
     return ex_apply_many(d_img, m, ns, R->ex.keep_black, s);
 }
@@ -319,7 +324,7 @@ int stitch_dev_stats_filter_f32(const float* d_measured, int count, int keep, fl
     if (keep < 0 || keep > STITCH_EXPOSURE_KEEP_MAX) return fail(STITCH_ERR_ARG, "stats_filter: keep %d (0 .. %d)", keep, STITCH_EXPOSURE_KEEP_MAX);
     const int rc = need_device();
     if (rc) return rc;
-    return ex_stats_filter(d_measured, 12, d_used, 12, count, keep, d_state12, d_has, as_stream(stream));
+    return ex_stats_filter(d_measured, 12, d_used, 12, count, keep, d_state12, d_has, nullptr, nullptr, 0, as_stream(stream));
 }
 
 int stitch_rig_set_exposure_smoothing(stitch_rig* rig, int keep) {

@@ -56,12 +56,13 @@ int stitch_dev_stats_filter_f32(const float *d_measured, int count, int keep, fl
 /* ---- the rig: HOST ONLY, no device needed.  Valid on a rig made with mode 1 or 2; on any other STITCH_ERR_ARG ------------------
  * Smoothing.  From the next replay on every step filters the statistics of its sets through the filter above, one state per step,
  * set after set across launch sequences and calls; the apply pass reads u.  What it adds to the rig's workspaces: a second buffer of
- * 64 * max_sets * n_steps bytes and 64 * n_steps bytes of state, allocated by the first replay with the option set; per step and
- * launch sequence ONE launch of one wavefront between the statistics and the apply pass.
+ * 64 * max_sets * n_steps bytes, 4 * max_sets bytes of flags and 64 * n_steps bytes of state, allocated by the first replay with the
+ * option set; per step and launch sequence ONE launch of one wavefront between the statistics and the apply pass.
  *
  * A replay that returns an error, or in which any set's status is not STITCH_OK, leaves the rig WITHOUT a state (the option stays).
- * Within that call the sets behind a failed set may already have been filtered against its statistics where those were finite but
- * meaningless; a set whose statistics are not valid never enters the state. */
+ * Within that call a set that a step's seam scan refuses enters the filter up to and including that step -- its statistics there are
+ * measured before the scan, on a mosaic that still means something -- and at no later step: the sets behind it are filtered as if the
+ * refused set had ended there.  A set whose statistics are not valid never enters the state. */
 int stitch_rig_set_exposure_smoothing(stitch_rig *rig, int keep);
 /* forgets the option and the state */
 int stitch_rig_clear_exposure_smoothing(stitch_rig *rig);

@@ -280,8 +280,10 @@ def _form_of(ctx, level):
     return NONE if not fmt else FUSED if not pad and ctx.sizes[0][0] % 4 == 0 else CONVERTED
 
 
-def _run_row(rig, ctx, opt, oracle, plans, chain=None, host=None, check=True, state=None, **frames_kw):
-    """A row's calls on `rig` -> per call _stitch's dict; held to both references where `check`."""
+def _run_row(rig, ctx, opt, oracle, plans, chain=None, host=None, check=True, state=None, forms_host=None, **frames_kw):
+    """A row's calls on `rig` -> per call _stitch's dict; held to both references where `check`.  forms_host: the frames the bare rig of
+    _bare_forms is asked with instead of `host` (the form depends on layout, pitch and address, not on bytes; a bare rig refuses what
+    content seams refuse)."""
     chain = ctx.chain_options(opt) if chain is None else chain
     _apply(rig, ctx, opt, chain)
     host = ctx.frames(opt["input"], opt["calls"][0], ctx.matrix_of(opt), **frames_kw) if host is None else host
@@ -299,7 +301,7 @@ def _run_row(rig, ctx, opt, oracle, plans, chain=None, host=None, check=True, st
             if res["forms_rest"] is not None:
                 assert res["forms"] == res["forms_rest"], what
             else:
-                assert res["forms"] == [_form_of(ctx, opt["input"])] * 3 == _bare_forms(ctx, opt, host)[c], what
+                assert res["forms"] == [_form_of(ctx, opt["input"])] * 3 == _bare_forms(ctx, opt, host if forms_host is None else forms_host)[c], what
     return out
 
 
